@@ -14,13 +14,19 @@ Workload (BASELINE.json configs[1..3] combined = the metric's "ORB extract + mat
      1 x local BA, 10 keyframes x 3000 landmarks (~26k observations), nIters=5 (+10), fp64 — a FRESH problem every step, the three
          phases of the plugin: setParams + optimize on the mapper thread (mapmanager.cpp:11388-11405), getResults on the tracker
          thread (:1267-1305); the flattened arrays live in pageable host memory, the results return to host arrays
-  value = frames / second over all ranks (median of R repetitions of the K-step loop; min / max beside it).  The resident-loop figure
+  value = frames / second over all ranks of exactly K timed steps (with --reps R: the median of R repetitions of the K-step loop, min /
+  max beside it).  The resident-loop figure
   of rounds 1-2 (frames already in HBM, one problem re-optimised, nothing copied back) is stages.kernel_only_frames_per_s.  Multi-GPU: frame streams are independent, so every rank runs the same per-GPU
   workload on its own frames ("weak" scaling, no data-path collective); only the timing reduction crosses ranks.  With N > 1 the
-  line also carries stages.sharded_*: ONE frame stream over all N GPUs (BASELINE config 5) — pyramid levels and train tiles
+  --full line also carries stages.sharded_*: ONE frame stream over all N GPUs (BASELINE config 5) — pyramid levels and train tiles
   sharded, every rank holding only its tile, one fused RCCL all-gather per frame (ucoslam_cv3_amd.parallel.ShardedFrameStream).
-Extra objects: "roofline" (dominant kernel, HIP events on its launch stream; SURVEY §8(d) bytes per unit x units per launch) and
-"cpu_baseline" (rank 0, N=1: oracle ORB at 1 / 2 / all threads, real xflann at 1 / all threads, real g2o).
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line.  --full adds the side
+measurements (15 repetitions of the K-step loop by default, "stages", "tracker_chain", "single_frame_latency", "roofline" — dominant
+kernel, HIP events on its launch stream; SURVEY §8(d) bytes per unit x units per launch — and "cpu_baseline": rank 0, N=1, oracle ORB
+at 1 / 2 / all threads, real xflann at 1 / all threads, real g2o).
+--dump-outputs DIR writes what rank 0's last timed step handed back to the host (keypoints, descriptors, counts, match rows, the local
+BA's poses, points, bad flags and iterations) as DIR/<name>.npy in float32 / float64; the inputs are seeded, so two builds compare
+output for output.
 """
 import argparse
 import json
@@ -91,9 +97,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--knn-qpw", type=int, default=1, help="queries per wave of the exact matcher (1, 2, 4)")
-    ap.add_argument("--quick", action="store_true", help="headline step only: skip the per-stage and side measurements")
-    ap.add_argument("--reps", type=int, default=15, help="repetitions of the timed K-step loop (median / min / max are reported)")
+    ap.add_argument("--quick", action="store_true", help="headline step only, compact line (profiling passes)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: stages, tracker chain, roofline, CPU baseline, sharded stream")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed K-step loop (median / min / max are reported); default 1, 15 with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 15 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -197,16 +208,6 @@ def main():
         check(L.uh_ba_wait(ba._h))
         check(L.uh_ba_get_results(*get_args))                       # tracker thread: getResults of the mapper's BA
 
-    # rounds 1-2's step, kept as stages.kernel_only_*: frames resident in HBM, ONE problem re-optimised, nothing returns to the host
-    ba_res = GlobalOptimizer.create(ctx_ba).wantChi2(False)
-    ba_res.setParams(ba_pr, ba_ps)
-
-    def step_resident():
-        ba_res.optimize_async()
-        ext.extract_batch(frames, fp, orb_out)
-        check(L.uh_knn_search_dev(index._h, dev_ptr(desc_v), F * NQ, NN, dev_ptr(knn_idx), dev_ptr(knn_dist), 0, -1))
-        ba_res.wait()
-
     def sync_all():
         torch.cuda.synchronize()
         if dist is not None:
@@ -234,14 +235,45 @@ def main():
     value = total_frames / t_max
     ms_per_step = 1e3 * t_max / args.steps
     ms_min, ms_max = 1e3 * min(reps_s) / args.steps, 1e3 * max(reps_s) / args.steps
+    ba_iters = [int(v) for v in ba_out["iters"]]   # (of the last step's problem)
 
-    # ---- per-stage split and roofline (rank 0; separate passes so event overhead never enters the headline number)
+    # ---- what the last timed step handed back to the host (the side measurements below reuse these buffers: written before them)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last_E = ba_problems[(step_no[0] - 1) % N_PROB]["E"]
+        # keypoint records: x, y, size, angle, response (float32), octave, class_id (int32) -> 7 float32 values
+        kp_raw = out_host[o_kps:o_desc].numpy()
+        kp = kp_raw.view(np.float32).reshape(F, MAX_FEATURES, 7).copy()
+        kp[..., 5:] = kp_raw.view(np.int32).reshape(F, MAX_FEATURES, 7)[..., 5:]
+        np.save(os.path.join(args.dump_outputs, "keypoints.npy"), kp)
+        dumps = {"descriptors": (desc_v, np.float32), "keypoint_counts": (cnt_v, np.float64), "match_idx": (knn_idx, np.float64),
+                 "match_dist": (knn_dist, np.float32)}
+        for name, (v, dt) in dumps.items():   # (device views into out_dev: their bytes in out_host, as the host received them)
+            off = v.data_ptr() - out_dev.data_ptr()
+            host = out_host[off:off + v.numel() * v.element_size()].view(v.dtype).view(v.shape)
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), host.numpy().astype(dt))
+        for name, a, dt in (("ba_poses", ba_out["poses"], np.float32), ("ba_points", ba_out["points"], np.float32),
+                            ("ba_bad", ba_out["bad"][:last_E], np.float32), ("ba_iters", ba_out["iters"], np.float64)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(dt))
+
+    # ---- per-stage split and roofline (rank 0, --full; separate passes so event overhead never enters the headline number)
     roofline = None
     stage_ms = {}
+    tracker = single = None
     if rank == 0 and args.quick:
         print(json.dumps({"value": round(value, 1), "ms_per_step": round(ms_per_step, 4), "ms_per_step_min": round(ms_min, 4), "ms_per_step_max": round(ms_max, 4), "reps": len(reps_s), "knn_qpw": args.knn_qpw, "knn_form": os.environ.get("UH_KNN_FORM", "auto (nn >= 6: scan + replay in one launch)")}), flush=True)
         return
-    if rank == 0:
+    if rank == 0 and args.full:
+        # rounds 1-2's step, kept as stages.kernel_only_*: frames resident in HBM, ONE problem re-optimised, nothing returns to the host
+        ba_res = GlobalOptimizer.create(ctx_ba).wantChi2(False)
+        ba_res.setParams(ba_pr, ba_ps)
+
+        def step_resident():
+            ba_res.optimize_async()
+            ext.extract_batch(frames, fp, orb_out)
+            check(L.uh_knn_search_dev(index._h, dev_ptr(desc_v), F * NQ, NN, dev_ptr(knn_idx), dev_ptr(knn_dist), 0, -1))
+            ba_res.wait()
+
         def timed(fn, reps):
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -652,7 +684,7 @@ def main():
     # ---- sharded frame stream (N > 1): levels + train tiles sharded, each rank holding ONLY its tile, ONE fused all-gather per frame
     def run_sharded():
         sharded = None
-        if dist is not None and (world > 1 or os.environ.get("UH_BENCH_SHARDED")):   # (the env switch exercises the stage with one rank)
+        if args.full and dist is not None and (world > 1 or os.environ.get("UH_BENCH_SHARDED")):   # (the env switch exercises the stage with one rank)
             from ucoslam_cv3_amd import parallel
 
             b = parallel.shard_bounds(NT, world)
@@ -706,13 +738,16 @@ def main():
                 sharded["single_gpu_frame_ms"] = round(1e3 * (time.perf_counter() - t0) / n_s, 4)
         return sharded
 
-    # ---- CPU baseline (rank 0, N=1 only): bounded sample of the same workload on the host cores, in the shapes SURVEY §8(d) asks for
+    # ---- CPU baseline (rank 0, N=1 only, --full): bounded sample of the same workload on the host cores, in the shapes SURVEY §8(d) asks for
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import oracle_lib
 
         O = oracle_lib.load_oracle()
-        ncores = os.cpu_count() or 1
+        # the cores this process may use (its affinity mask, capped by OMP_NUM_THREADS where the host sets it), not the machine's count
+        ncores = len(os.sched_getaffinity(0))
+        if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+            ncores = max(1, min(ncores, int(os.environ["OMP_NUM_THREADS"])))
 
         import threading
 
@@ -852,7 +887,7 @@ def main():
 
     # The sharded stage is a SIDE measurement whose collective has never run on more than one GPU anywhere: it runs last, under a
     # watchdog, so that neither an exception nor a hang in it can cost the headline line (measured above, assembled already).
-    if dist is not None and (world > 1 or os.environ.get("UH_BENCH_SHARDED")):
+    if args.full and dist is not None and (world > 1 or os.environ.get("UH_BENCH_SHARDED")):
         import threading
 
         dog = threading.Timer(120.0, lambda: (line["stages"].update({"sharded_error": "timed out after 120 s"}) if rank == 0 else None, emit_and_exit(0)))

@@ -14,13 +14,13 @@ rm -rf $OUT; mkdir -p $OUT/mfma
 cd /tmp && export TMPDIR=/tmp
 Q="python $R/bench.py --quick --steps 20 --warmup 5 --reps 15"
 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/quick -o bench -- $Q > $OUT/quick.log 2>&1
-F="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+F="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o bench -- $F > $OUT/stats.log 2>&1
 Q3="python $R/bench.py --quick --steps 6 --warmup 2 --reps 1"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -f csv -d $OUT/pmc_fetch -o bench -- $Q3 > $OUT/pmc_fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -f csv -d $OUT/pmc_write -o bench -- $Q3 > $OUT/pmc_write.log 2>&1
 UH_BENCH_SHARDED=1 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/shard -o bench -- python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-  --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 1 --steps 5 --warmup 2 --reps 2 --no-cpu-baseline --no-roofline > $OUT/shard.log 2>&1
+  --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --full --gpus 1 --steps 5 --warmup 2 --reps 2 --no-cpu-baseline --no-roofline > $OUT/shard.log 2>&1
 # ---- MFMA evidence
 $R/scripts/micro/mfma_f64_rate.bin > $OUT/mfma/rate.txt 2>&1
 rocprofv3 --list-avail 2>/dev/null | grep -i -E "mfma" | head -40 > $OUT/mfma/counters_available.txt

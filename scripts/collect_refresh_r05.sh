@@ -11,7 +11,7 @@ python scripts/fuzz_parity.py 45 orb,knn_exact,knn_twophase,knn_stream,kmeans_in
 bash scripts/knn_pmc_r05.sh 2>&1 | grep -E "^8000|^2000" > $O/knn_pmc.txt
 python scripts/ba_ab.py 10 3000 0 2 2>&1 | grep -v "^/opt" > $O/ba_ab.txt
 scripts/micro/solve48.bin > $O/solve48.txt 2>&1
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 UH_COLLECT_PARTS="headline tracker" bash scripts/collect_profiles_r05.sh > $O/collect.log 2>&1
 find $R/gpurun_out/prof_r05 -name "*kernel_trace.csv" -delete
 find $R/gpurun_out/prof_r05 -name "*.csv" -size +20M -delete

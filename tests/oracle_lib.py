@@ -38,6 +38,72 @@ def load_ref(name):
     return C.CDLL(path)
 
 
+REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "ref_outputs.npz")
+
+
+def digest(*arrays):
+    """SHA-256 (uint8[32]) over the arrays' dtypes, shapes and bytes: what the recording keeps of outputs compared for exact equality."""
+    import hashlib
+
+    import numpy as np
+
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(f"{a.dtype.str}{a.shape}".encode())
+        h.update(a.tobytes())
+    return np.frombuffer(h.digest(), np.uint8).copy()
+
+
+def pack_arrays(arrays):
+    """{key: array} -> (index, data): uint8 arrays holding a JSON list of (key, dtype, shape, byte offset) and the arrays' bytes end to
+    end, so that a recording of many small arrays takes two .npz entries (each entry costs a zip and an .npy header)."""
+    import json
+
+    import numpy as np
+
+    index, chunks, off = [], [], 0
+    for k, v in arrays.items():
+        v = np.ascontiguousarray(v)
+        index.append([k, v.dtype.str, list(v.shape), off])
+        chunks.append(v.tobytes())
+        off += v.nbytes
+    return np.frombuffer(json.dumps(index).encode(), np.uint8).copy(), np.frombuffer(b"".join(chunks), np.uint8).copy()
+
+
+def unpack_arrays(index, data):
+    """Inverse of pack_arrays."""
+    import json
+
+    import numpy as np
+
+    out = {}
+    for k, dt, shape, off in json.loads(index.tobytes().decode()):
+        dt = np.dtype(dt)
+        n = int(np.prod(shape, dtype=np.int64))
+        out[k] = data[off:off + n * dt.itemsize].view(dt).reshape(shape)
+    return out
+
+
+def reference_outputs(group, name, compute):
+    """What the real reference returned for one test's seeded inputs, as {key: array}.  Recorded in tests/golden/ref_outputs.npz
+    (entries '<group>__index' and '<group>__data' of pack_arrays, written by tests/golden/make_ref_outputs.py) so that the test runs
+    where oracle/_ref cannot be built; where oracle/_ref/lib<name>_ref.so exists, compute(lib) recomputes them and they must equal
+    the recording."""
+    import numpy as np
+
+    g = np.load(REF_OUTPUTS)
+    assert group + "__index" in g.files, f"{REF_OUTPUTS} holds nothing for {group}: rerun tests/golden/make_ref_outputs.py"
+    rec = unpack_arrays(g[group + "__index"], g[group + "__data"])
+    ref = load_ref(name)
+    if ref is not None:
+        live = compute(ref)
+        assert sorted(live) == sorted(rec), f"{group}: the recording's keys differ from the live reference's"
+        for k, v in live.items():
+            np.testing.assert_array_equal(np.asarray(v), rec[k], err_msg=f"{group}: live reference != recording at {k}")
+    return rec
+
+
 def knn_search(L, train, queries, nn, sorted_=0, max_dist=-1, t_begin=0, t_end=-1):
     import numpy as np
 

@@ -24,30 +24,63 @@ def _sets():
     return out
 
 
-@pytest.mark.parametrize("name", list(_sets().keys()))
-def test_hkmeans_restatement_matches_real_xflann(oracle, name):
-    ref = oracle_lib.load_ref("xflann")
-    if ref is None or not hasattr(ref, "xflann_ref_hkmeans_stream"):
-        pytest.skip("oracle/_ref/libxflann_ref.so not built (reference tree absent)")
+KMI = ((32, 0), (8, 0), (32, 11), (8, 3), (8, -1))
+SEARCHES = ((10, 16, 0), (10, 16, 1), (5, 1, 0), (3, 40, 0), (10, 200, 1), (2, 3, 0), (1, 2, 0), (10, -1, 0))
+
+
+def _train_queries(name):
     a, b = _sets()[name]
     train, queries = (b, a) if name.startswith(("match", "ties")) else (a, b)   # synth returns (train, query) for match sets
     if name.startswith(("match", "ties")):
         train, queries = a, b
-    for k, mi in ((32, 0), (8, 0), (32, 11), (8, 3), (8, -1)):
+    return train, queries
+
+
+def xflann_hkmeans_outputs(name):
+    """compute(ref) for oracle_lib.reference_outputs: the real xflann's serialised index (its 64-byte header, the length and SHA-256 of
+    the block data) and search rows (oracle_lib.digest of indices and distances) on set `name`, for every (k, maxIters) whose build the reference finishes ("built"; recorded in
+    tests/golden/ref_outputs.npz, group xflann_hkmeans_<name>)."""
+    import hashlib
+
+    def compute(ref):
+        train, queries = _train_queries(name)
+        out = {"built": np.array([not isinstance(oracle_lib.hkmeans_blob(oracle_lib.load_oracle(), train, k, mi), int) for k, mi in KMI])}
+        for (k, mi), built in zip(KMI, out["built"]):
+            if not built:
+                continue   # > k identical rows: the reference recurses without end
+            stream = oracle_lib.ref_hkmeans_stream(ref, train, k, mi)
+            out[f"k{k}_mi{mi}_head"] = stream[:64].copy()
+            out[f"k{k}_mi{mi}_blob_size"] = np.array([len(stream) - 64], np.int64)
+            out[f"k{k}_mi{mi}_blob_sha256"] = np.frombuffer(hashlib.sha256(stream[64:].tobytes()).digest(), np.uint8)
+            for nn, mc, srt in SEARCHES:
+                i1, d1 = oracle_lib.ref_hkmeans_search(ref, train, queries, nn, k, mi, mc, srt)
+                out[f"k{k}_mi{mi}_nn{nn}_mc{mc}_s{srt}"] = oracle_lib.digest(i1, d1)
+        return out
+
+    return compute
+
+
+@pytest.mark.parametrize("name", list(_sets().keys()))
+def test_hkmeans_restatement_matches_real_xflann(oracle, name):
+    import hashlib
+
+    rec = oracle_lib.reference_outputs(f"xflann_hkmeans_{name}", "xflann", xflann_hkmeans_outputs(name))
+    train, queries = _train_queries(name)
+    for (k, mi), built in zip(KMI, rec["built"]):
         blob = oracle_lib.hkmeans_blob(oracle, train, k, mi)
+        assert built == (not isinstance(blob, int))
         if isinstance(blob, int):
             assert blob == -2      # > k identical rows: the reference recurses without end; nothing to compare
             continue
-        stream = oracle_lib.ref_hkmeans_stream(ref, train, k, mi)
-        params = np.frombuffer(stream[24:64].tobytes(), np.uint32)
+        head = rec[f"k{k}_mi{mi}_head"]
+        params = np.frombuffer(head[24:64].tobytes(), np.uint32)
         assert params[0] == 8 and params[7] == 32 and params[8] == len(train)      # alignment, descriptor size, npoints
-        assert int(np.frombuffer(stream[40:48].tobytes(), np.uint64)[0]) == len(blob)
-        assert stream[64:].tobytes() == blob.tobytes()
-        for nn, mc, srt in ((10, 16, 0), (10, 16, 1), (5, 1, 0), (3, 40, 0), (10, 200, 1), (2, 3, 0), (1, 2, 0), (10, -1, 0)):
+        assert int(np.frombuffer(head[40:48].tobytes(), np.uint64)[0]) == len(blob) == int(rec[f"k{k}_mi{mi}_blob_size"][0])
+        assert hashlib.sha256(blob.tobytes()).digest() == rec[f"k{k}_mi{mi}_blob_sha256"].tobytes()
+        for nn, mc, srt in SEARCHES:
             i0, d0 = oracle_lib.hkmeans_search(oracle, blob, queries, nn, mc, srt)
-            i1, d1 = oracle_lib.ref_hkmeans_search(ref, train, queries, nn, k, mi, mc, srt)
-            np.testing.assert_array_equal(i0, i1, err_msg=f"{name} k={k} maxIters={mi} nn={nn} maxChecks={mc} sorted={srt}")
-            np.testing.assert_array_equal(d0, d1)
+            np.testing.assert_array_equal(oracle_lib.digest(i0, d0), rec[f"k{k}_mi{mi}_nn{nn}_mc{mc}_s{srt}"],
+                                          err_msg=f"{name} k={k} maxIters={mi} nn={nn} maxChecks={mc} sorted={srt}")
 
 
 GOLD = __import__("os").path.join(__import__("os").path.dirname(__file__), "golden", "hkmeans_golden.npz")

@@ -21,20 +21,28 @@ def test_oracle_matches_reference_golden(oracle, case, nn, s):
     np.testing.assert_array_equal(dist, g[f"{case}_nn{nn}_s{s}_dist"])
 
 
-def test_oracle_matches_live_reference_build(oracle):
-    ref = oracle_lib.load_ref("xflann")
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent on this box)")
+def xflann_linear_outputs(ref):
+    """The real xflann's Linear search rows on seeded sets, as oracle_lib.digest of (indices, distances) (recorded in
+    tests/golden/ref_outputs.npz, group xflann_linear)."""
     P = oracle_lib.P
+    out = {}
     for seed in range(3):
         train, q = synth.match_set(150, 2000, seed=100 + seed)
         for nn, s in [(2, 1), (10, 0), (7, 1)]:
             i2 = np.empty((len(q), nn), np.int32)
             d2 = np.empty_like(i2)
             assert ref.xflann_ref_linear_search(P(train), len(train), P(q), len(q), nn, s, 1, P(i2), P(d2)) == 0
+            out[f"s{seed}_nn{nn}_sorted{s}"] = oracle_lib.digest(i2, d2)
+    return out
+
+
+def test_oracle_matches_live_reference_build(oracle):
+    rec = oracle_lib.reference_outputs("xflann_linear", "xflann", xflann_linear_outputs)
+    for seed in range(3):
+        train, q = synth.match_set(150, 2000, seed=100 + seed)
+        for nn, s in [(2, 1), (10, 0), (7, 1)]:
             i1, d1 = oracle_lib.knn_search(oracle, train, q, nn, s)
-            np.testing.assert_array_equal(i1, i2)
-            np.testing.assert_array_equal(d1, d2)
+            np.testing.assert_array_equal(oracle_lib.digest(i1, d1), rec[f"s{seed}_nn{nn}_sorted{s}"], err_msg=f"seed {seed} nn {nn} sorted {s}")
 
 
 def test_oracle_shard_superset_property(oracle):

@@ -25,35 +25,50 @@ def _clouds():
     return out
 
 
-@pytest.mark.parametrize("name", list(_clouds().keys()))
-def test_restated_kdtree_matches_real_picoflann(oracle, name):
-    ref = oracle_lib.load_ref("picoflann")
-    if ref is None:
-        pytest.skip("oracle/_ref/libpicoflann_ref.so not built (reference tree absent)")
-    xy = _clouds()[name]
-    if len(xy) == 0:
-        pytest.skip("the reference indexes an empty node vector for an empty cloud; the restatement returns no hits")
-    mine = oracle_lib.KdOracle(oracle, "oracle_kd", xy)
-    real = oracle_lib.KdOracle(ref, "picoflann_ref", xy)
+def _queries(xy):
+    """400 seeded radius queries around the cloud: on data points / split values (every third), elsewhere at random."""
     rng = np.random.default_rng(11)
     lo, hi = xy.min(0) - 30, xy.max(0) + 30
-    nhits = 0
     for t in range(400):
         if t % 3 == 0 and len(xy):   # queries sitting exactly on a data point / on split values
             q = xy[rng.integers(len(xy))]
         else:
             q = (lo + rng.random(2) * (hi - lo)).astype(np.float32)
-        r = [3.0, 15.0, 15.0 * 1.2 ** 3 * 1.6, 80.0, 1e4][t % 5]
+        yield q, [3.0, 15.0, 15.0 * 1.2 ** 3 * 1.6, 80.0, 1e4][t % 5]
+
+
+def picoflann_radius_outputs(name):
+    """compute(ref) for oracle_lib.reference_outputs: per query of _queries, the real picoflann's hit count, and oracle_lib.digest of
+    every query's hits in order with their squared distances (recorded in tests/golden/ref_outputs.npz, group picoflann_radius_<name>;
+    the r = 1e4 queries return every point)."""
+    def compute(ref):
+        xy = _clouds()[name]
+        real = oracle_lib.KdOracle(ref, "picoflann_ref", xy)
+        hits = [real.radius(q[0], q[1], np.float32(r)) for q, r in _queries(xy)]
+        return {"count": np.array([len(i) for i, _ in hits], np.int64), "hits": oracle_lib.digest(*[a for h in hits for a in h])}
+
+    return compute
+
+
+@pytest.mark.parametrize("name", list(_clouds().keys()))
+def test_restated_kdtree_matches_real_picoflann(oracle, name):
+    xy = _clouds()[name]
+    if len(xy) == 0:
+        pytest.skip("the reference indexes an empty node vector for an empty cloud; the restatement returns no hits")
+    rec = oracle_lib.reference_outputs(f"picoflann_radius_{name}", "picoflann", picoflann_radius_outputs(name))
+    mine = oracle_lib.KdOracle(oracle, "oracle_kd", xy)
+    nhits, hits = 0, []
+    for t, (q, r) in enumerate(_queries(xy)):
         i0, d0 = mine.radius(q[0], q[1], np.float32(r))
-        i1, d1 = real.radius(q[0], q[1], np.float32(r))
-        assert i0.tolist() == i1.tolist(), (name, t)
-        assert d0.tolist() == d1.tolist()
+        assert len(i0) == rec["count"][t], (name, t)
+        hits += [i0, d0]
         nhits += len(i0)
         # the hit SET is the brute-force disc (strict <, float difference, double square)
         dx = (np.float32(q[0]) - xy[:, 0]).astype(np.float64)
         dy = (np.float32(q[1]) - xy[:, 1]).astype(np.float64)
         inside = np.nonzero(dx * dx + dy * dy < float(np.float32(r)) ** 2)[0]
         assert sorted(i0.tolist()) == inside.tolist()
+    assert (oracle_lib.digest(*hits) == rec["hits"]).all(), name     # same hits, same order, same squared distances
     assert nhits > 0
 
 
