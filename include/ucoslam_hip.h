@@ -613,6 +613,18 @@ int  uh_pnp_solve(uh_pnp* pnp, const float* pose_f2g, const float* intr4, int n,
 int  uh_pnp_solve_dev(uh_pnp* pnp, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                       const float* d_inv_sigma, const float* d_weight, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
                       int32_t* d_result5, double* d_state7);
+/* Stereo / RGB-D observations (pnpsolver.cpp:205-276): depth[i] = Frame::getDepth(queryIdx) of match i; depth <= 0 keeps the monocular
+ * edge, depth > 0 gives EdgeStereoSE3ProjectXYZOnlyPose (typesg2o.h:521-590) with the measurement (x, y, x - bl * fx / depth), the same
+ * information, the robust weight doubled, Huber sqrt(7.815) and outliers above chi2 7.815.  bl = imageParams.bl; must be > 0 when any
+ * depth is > 0.  The caller passes the same weights as for uh_pnp_solve (the doubling happens inside).  depth == NULL, or every depth
+ * <= 0, returns what uh_pnp_solve returns, bit for bit. */
+int  uh_pnp_solve_stereo(uh_pnp* pnp, const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp,
+                         const float* inv_sigma, const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out,
+                         int32_t* iters_out4, double* state_out7);
+/* device-resident form: d_depth (n floats, device) or NULL (= uh_pnp_solve_dev); with d_depth, bl must be > 0 and d_work holds n*36 bytes */
+int  uh_pnp_solve_stereo_dev(uh_pnp* pnp, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
+                             const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, void* d_work,
+                             float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7);
 
 /* ------------------------------------------------------------------------
  * Projection matcher — replaces Map::matchFrameToMapPoints (src/map.cpp:651-770) on flattened inputs:
@@ -705,6 +717,20 @@ typedef struct uh_track_result {
     float pose1[16], pose2[16];
 } uh_track_result;
 int  uh_track_pose(uh_projmatch* pm, uh_pnp* pnp, const uh_track_args* args, uh_track_result* result);
+/* uh_track_pose for stereo / RGB-D frames: both solves are uh_pnp_solve_stereo's, with depth[queryIdx] gathered per match on the device.
+ *   depth        the frame's n keypoints: Frame::getDepth per keypoint (<= 0: none); NULL = monocular (the solves of uh_track_pose)
+ *   bl           imageParams.bl; > 0 when any depth is > 0
+ *   prev_weight  prev->n: the solver weight (MapPoint::isStable: 1 or 0.5) of each previous-frame item, or NULL (= uh_track_pose: weight 1,
+ *                except the second solve's items with prev_map_row >= 0, which take map_weight).  Given, an item's weight in both solves is
+ *                map_weight[prev_map_row] when that row is >= 0, else prev_weight[i] (pnpsolver.cpp:210-211 in every solvePnp call).
+ * The caller passes the same weights as for monocular frames (the stereo edges double theirs inside the solver).  Also refuses a
+ * prev_map_row outside [-1, map->n).  With depth == NULL and prev_weight == NULL the results equal uh_track_pose's. */
+typedef struct uh_track_stereo {
+    const float* depth;
+    float bl;
+    const float* prev_weight;
+} uh_track_stereo;
+int  uh_track_pose_stereo(uh_projmatch* pm, uh_pnp* pnp, const uh_track_args* args, const uh_track_stereo* stereo, uh_track_result* result);
 /* test hook: the flattened kd-tree of the current frame (24-byte nodes {float divlow, divhigh; int32 left, right, leaf_begin;
  * int16 leaf_count, col}), the leaf index list, the root box {x.min, x.max, y.min, y.max} and the tree depth */
 int  uh_projmatch_debug_tree(uh_projmatch* pm, int32_t* n_nodes, const void** nodes24, const uint32_t** leaf_idx,

@@ -278,6 +278,19 @@ class PnPSolver {
         bad.resize(n);
         return rc;
     }
+    // stereo / RGB-D frames (pnpsolver.cpp:205-276): depth[i] = frame.getDepth(queryIdx) of match i (<= 0: monocular match),
+    // bl = frame.imageParams.bl; the weights are the monocular ones (the solver doubles those of stereo matches)
+    int solvePnp(float* pose_io, const float intr4[4], int n, const float* p3d, const float* kp, const float* inv_sigma, const float* weight,
+                 const float* depth, float bl, std::vector<uint8_t>& bad) {
+        bad.assign(n > 0 ? n : 1, 0);
+        float out[16];
+        int32_t iters[4];
+        const int rc = uh_pnp_solve_stereo(p_, pose_io, intr4, n, p3d, kp, inv_sigma, weight, depth, bl, out, bad.data(), iters, nullptr);
+        if (rc < 0) check(rc);
+        std::copy(out, out + 16, pose_io);
+        bad.resize(n);
+        return rc;
+    }
    private:
     std::shared_ptr<Context> ctx_;
     uh_pnp* p_ = nullptr;

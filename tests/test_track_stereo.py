@@ -1,0 +1,152 @@
+"""uh_track_pose_stereo: the one-call tracker with stereo / RGB-D depths and per-item previous-frame weights, against the operators
+one after the other (uh_projmatch_match_prev -> look-ups -> uh_pnp_solve_stereo -> uh_projmatch_match -> union, uh_filter_ambiguous ->
+look-ups -> uh_pnp_solve_stereo), bit for bit, with both kd-tree builders."""
+import numpy as np
+import pytest
+
+from test_track import _same, _scene
+
+BL = 0.54
+
+
+def _depths(sc, seed, n_map=3000):
+    """Per keypoint of the frame: the camera z of a map point _scene placed behind it (its draws of `pick` and `z` are the first of its
+    generator) with 0.5 % noise, a grossly wrong depth for a few, none (0 or < 0) for about a third and for keypoints without a point."""
+    rng = np.random.default_rng(seed)
+    n = len(sc["ukp"])
+    pick = rng.integers(0, n, n_map)
+    z = rng.uniform(4, 40, n_map)
+    depth = np.zeros(n, np.float64)
+    depth[pick] = z
+    r2 = np.random.default_rng(1000 + seed)
+    depth *= 1 + r2.normal(0, 0.005, n)
+    depth[r2.random(n) < 0.05] *= 2.5
+    depth[r2.random(n) < 0.35] = 0.0
+    depth[r2.random(n) < 0.02] = -1.0
+    return depth.astype(np.float32)
+
+
+def _sequence_stereo(sc, pnp, depth, prev_weight, min_inliers=30, d1=75.0, r1=15.0, d2=100.0, rt=4.0, rl=15.0):
+    """The operators one after the other, with the host's list handling and look-ups in between (the stereo form of
+    tests/test_track.py::_sequence): depth[queryIdx] per match in both solves; a previous-frame item's weight is map_weight[row] for
+    row >= 0, else prev_weight[i] (or 1 without prev_weight, and then 1 for every item of the first solve)."""
+    from ucoslam_cv3_amd._lib import lib, np_ptr
+    from ucoslam_cv3_amd.projmatch import DMATCH_DTYPE
+
+    pm, prev, mp, ukp = sc["pm"], sc["prev"], sc["mp"], sc["ukp"]
+    row_of = sc["prev_row"]
+    a = pm.matchFrameToPrevFrame(sc["pose0"], prev["ids"], prev["pos3d"], prev["octave"], prev["desc"], d1, r1)
+    m1 = a["matches"]
+    pid_to_i = {int(v): i for i, v in enumerate(prev["ids"])}
+    it1 = np.array([pid_to_i[int(t)] for t in m1["trainIdx"]], np.int64)
+    q1 = m1["queryIdx"]
+    if prev_weight is None:
+        w1 = np.ones(len(m1), np.float32)
+    else:
+        w1 = np.array([sc["weight"][row_of[i]] if row_of[i] >= 0 else prev_weight[i] for i in it1], np.float32)
+    s1 = pnp.solvePnp(sc["pose0"], sc["intr"], prev["pos3d"][it1].reshape(-1, 3), np.stack([ukp["x"][q1], ukp["y"][q1]], 1).reshape(-1, 2),
+                      sc["inv_sf"][ukp["octave"][q1]], w1, depth=depth[q1], bl=BL)
+    tracked = s1["ngood"] >= min_inliers
+    pose_map = s1["pose"] if tracked else sc["pose0"]
+    b = pm.matchFrameToMapPoints(pose_map, mp["ids"], mp["pos3d"], mp["normal"], mp["min_dist"], mp["max_dist"], mp["desc"], d2, rt if tracked else rl)
+    m2 = b["matches"]
+    union = np.concatenate([m1[s1["bad"][: len(m1)] == 0] if tracked else m1[:0], m2]).astype(DMATCH_DTYPE)
+    if len(union):
+        union = np.ascontiguousarray(union)
+        k = lib().uh_filter_ambiguous(np_ptr(union), len(union), 0)
+        assert k >= 0
+        union = union[:k]
+    mid_to_row = {int(v): i for i, v in enumerate(mp["ids"])}
+    p3d = np.zeros((len(union), 3), np.float32)
+    w = np.ones(len(union), np.float32)
+    for i, tr in enumerate(union["trainIdx"]):
+        row = mid_to_row.get(int(tr), -1)
+        if row >= 0:
+            p3d[i] = mp["pos3d"][row]; w[i] = sc["weight"][row]
+        else:
+            p3d[i] = prev["pos3d"][pid_to_i[int(tr)]]
+            if prev_weight is not None:
+                w[i] = prev_weight[pid_to_i[int(tr)]]
+    qa = union["queryIdx"]
+    s2 = pnp.solvePnp(pose_map, sc["intr"], p3d, np.stack([ukp["x"][qa], ukp["y"][qa]], 1).reshape(-1, 2), sc["inv_sf"][ukp["octave"][qa]], w,
+                      depth=depth[qa], bl=BL)
+    return dict(matches_prev=m1, bad_prev=s1["bad"][: len(m1)], inliers1=s1["ngood"], iters1=s1["iters"], pose1=s1["pose"], tracked=bool(tracked), matches_map=m2,
+                matches_all=union, bad_all=s2["bad"][: len(union)], inliers2=s2["ngood"], iters2=s2["iters"], pose2=s2["pose"])
+
+
+def _prev_weight(sc, seed):
+    rng = np.random.default_rng(100 + seed)
+    return np.where(rng.random(len(sc["prev"]["ids"])) < 0.4, np.float32(0.5), np.float32(1.0)).astype(np.float32)
+
+
+def _fused(sc, pnp, **kw):
+    return sc["pm"].trackPoseStereo(pnp, sc["pose0"], sc["intr"], sc["inv_sf"], sc["prev"], sc["mp"], prev_map_row=sc["prev_row"], map_weight=sc["weight"], **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("host_tree", [False, True], ids=["device_tree", "host_tree"])
+def test_track_pose_stereo_equals_the_operators(hip_ctx, host_tree):
+    from ucoslam_cv3_amd.pnp import PnPSolver
+
+    pnp = PnPSolver(hip_ctx)
+    for seed, kw in ((5, {}), (7, dict(n_prev=300, n_map=1200)), (8, dict(pose_noise=0.8)), (11, dict(n_prev=1500, n_map=6500))):
+        sc = _scene(hip_ctx, seed, host_tree, **kw)
+        depth = _depths(sc, seed, kw.get("n_map", 3000))
+        assert (depth > 0).mean() > 0.2
+        for pw in (None, _prev_weight(sc, seed)):
+            s = _sequence_stereo(sc, pnp, depth, pw)
+            f = _fused(sc, pnp, depth=depth, bl=BL, prev_weight=pw)
+            _same(f, s, f"seed {seed} prev_weight {pw is not None}")
+        if not kw.get("pose_noise"):
+            assert f["tracked"] and f["inliers2"] > 30
+
+
+@pytest.mark.gpu
+def test_track_pose_stereo_without_depth_equals_track_pose(hip_ctx):
+    from ucoslam_cv3_amd.pnp import PnPSolver
+
+    pnp = PnPSolver(hip_ctx)
+    for seed in (5, 8):
+        sc = _scene(hip_ctx, seed, False, **(dict(pose_noise=0.8) if seed == 8 else {}))
+        a = sc["pm"].trackPose(pnp, sc["pose0"], sc["intr"], sc["inv_sf"], sc["prev"], sc["mp"], prev_map_row=sc["prev_row"], map_weight=sc["weight"])
+        b = _fused(sc, pnp)
+        _same(b, a, f"seed {seed}")
+        assert b["pose1"].tobytes() == a["pose1"].tobytes()
+
+
+@pytest.mark.gpu
+def test_track_pose_stereo_prev_weight_reaches_the_solves(hip_ctx):
+    """A previous-frame item outside the local map weighs prev_weight[i] (not 1) in the solves, exactly as the operator sequence with the
+    reference's per-edge weights.  (The robust weight scales the chi2 sums only, not the normal equations: it changes Levenberg's damping
+    and stopping decisions, so some scene / weight pairs move the result and others leave it bit-identical — at least one must move.)"""
+    from ucoslam_cv3_amd.pnp import PnPSolver
+
+    pnp = PnPSolver(hip_ctx)
+    moved = 0
+    for seed, kw in ((5, {}), (8, dict(pose_noise=0.8)), (6, dict(pose_noise=0.3))):
+        sc = _scene(hip_ctx, seed, False, **kw)
+        assert (sc["prev_row"] < 0).any()
+        base = _fused(sc, pnp)
+        for wv in (0.5, 1e-3):
+            pw = np.full(len(sc["prev"]["ids"]), np.float32(wv))
+            got = _fused(sc, pnp, prev_weight=pw)
+            _same(got, _sequence_stereo(sc, pnp, np.zeros(len(sc["ukp"]), np.float32), pw), f"seed {seed} prev_weight {wv}")
+            moved += any(got[k].tobytes() != base[k].tobytes() for k in ("pose1", "pose2", "iters1", "iters2", "bad_prev", "bad_all"))
+    assert moved > 0
+
+
+@pytest.mark.gpu
+def test_track_pose_stereo_refuses_bad_rows_and_baseline(hip_ctx):
+    from ucoslam_cv3_amd._lib import UcoslamHipError
+    from ucoslam_cv3_amd.pnp import PnPSolver
+
+    pnp = PnPSolver(hip_ctx)
+    sc = _scene(hip_ctx, 7, False, n_prev=300, n_map=1200)
+    for bad_row in (len(sc["mp"]["ids"]), -2):
+        rows = sc["prev_row"].copy()
+        rows[len(rows) // 2] = bad_row
+        with pytest.raises(UcoslamHipError):
+            sc["pm"].trackPoseStereo(pnp, sc["pose0"], sc["intr"], sc["inv_sf"], sc["prev"], sc["mp"], prev_map_row=rows, map_weight=sc["weight"])
+    with pytest.raises(UcoslamHipError):
+        _fused(sc, pnp, depth=_depths(sc, 7, 1200), bl=0.0)
+    _fused(sc, pnp, depth=_depths(sc, 7, 1200), bl=BL)   # the session is still usable

@@ -48,6 +48,9 @@ struct PnpArgs {
     unsigned long long done_word;
     long long* clk;          // NULL, or 8 timestamps (s_memtime) for scripts/time_pnp.py
     uh::PnpDecide dec;       // dyn17 != NULL: the tracker's decision rides on this solve (common.hpp)
+    // stereo instantiation only (kept behind the monocular fields: those instantiations read the same offsets as before)
+    const float* depth;      // n: Frame::getDepth(queryIdx), <= 0 = monocular match
+    float bl;                // imageParams.bl (stereo baseline)
 };
 
 // one thread: the decision of system.cpp:6762-6881 from this solve's inlier count; M = the pose it returns (16 floats)
@@ -218,14 +221,17 @@ constexpr int kPnpLdsMatches = 3000;
 // Wave 0 owns the Levenberg state and is alone on its SIMD during the serial steps (the other waves wait at the barrier).
 constexpr int kPnpThreads = 512, kPnpWaves = kPnpThreads / 64;
 constexpr int kNS = 29;               // sums per pass: H (21), b (6), robust chi2, inlier count
-constexpr unsigned kActive = 1, kRobust = 2, kBad = 4;
+constexpr unsigned kActive = 1, kRobust = 2, kBad = 4, kStereo = 8;
 enum : int { kModeEval = 0, kModeClassify = 1, kModeExit = 2, kModeLadder = 3 };
 constexpr int kLadderMax = 8;         // candidates per ladder pass (one per wave; Levenberg's inner loop tries at most ten damping factors per iteration)
 
 struct __attribute__((aligned(16))) MatchRec { float X, Y, Z, u, v, invsig, weight; unsigned flags; };
 static_assert(sizeof(MatchRec) == 32, "match record");
+// STEREO: the records are followed by one float per match, the right-image measurement kp_ur (pnpsolver.cpp:245-246; 0 for a monocular
+// match); kStereo in flags selects EdgeStereoSE3ProjectXYZOnlyPose for the match.  36 bytes per match: 3000 matches = 105.5 KiB of LDS.
+constexpr int kPnpRecBytesStereo = 36;
 
-template <bool CACHED>
+template <bool CACHED, bool STEREO = false>
 __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_cache[];
     __shared__ __attribute__((aligned(16))) double s_part[kPnpWaves * 32];
@@ -253,14 +259,31 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     if (A.clk && tid == 0) A.clk[0] = __builtin_readcyclecounter();
     const double fx = A.intr[0], fy = A.intr[1], cx = A.intr[2], cy = A.intr[3];
     const double delta = (double)sqrtf(5.99f), dsqr = delta * delta;
+    // stereo edges (pnpsolver.cpp:175-181, 248-274): thHuber3D = (float)sqrt(7.815), relabelled above Chi3D = 7.815f, bf = mbf as a double
+    double delta3 = 0, dsqr3 = 0, bf = 0;
+    if constexpr (STEREO) { delta3 = (double)(float)sqrt(7.815); dsqr3 = delta3 * delta3; bf = (double)(A.bl * A.intr[0]); }
     // one name for both instantiations; in each the pointer has a single provenance (LDS or HBM): ds_* or global_* accesses, never flat
     MatchRec* rec;
     if constexpr (CACHED) rec = reinterpret_cast<MatchRec*>(s_cache);
     else rec = reinterpret_cast<MatchRec*>(A.work);
+    float* urs = nullptr;   // STEREO: kp_ur per match, behind the n records
+    if constexpr (STEREO) urs = reinterpret_cast<float*>(rec + n);
     for (int e = tid; e < n; e += kPnpThreads) {
         MatchRec r;
         r.X = A.p3d[3 * e]; r.Y = A.p3d[3 * e + 1]; r.Z = A.p3d[3 * e + 2]; r.u = A.kp[2 * e]; r.v = A.kp[2 * e + 1];
         r.invsig = A.invsig[e]; r.weight = A.weight[e]; r.flags = kActive | kRobust;
+        if constexpr (STEREO) {
+            // pnpsolver.cpp:239-246: depth <= 0 keeps the monocular edge; else mbf = bl * fx and kp_ur = x - mbf / depth, all float
+            // (a correctly rounded float division: the build does not use fast math)
+            const float depth = A.depth[e];
+            float ur = 0.f;
+            if (!(depth <= 0.f)) {
+                const float mbf = A.bl * A.intr[0];
+                ur = r.u - mbf / depth;
+                r.flags |= kStereo;
+            }
+            urs[e] = ur;
+        }
         rec[e] = r;
     }
     {
@@ -291,6 +314,24 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         ey = (double)m.v - fma(yz, fy, cy);
         return (double)m.invsig * fma(ex, ex, ey * ey);
     };
+    // EdgeStereoSE3ProjectXYZOnlyPose (typesg2o.h:521-590): cam_project divides in double and ROUNDS 1/z TO FLOAT before it uses it in
+    // double, un-fused; the Jacobian uses the double 1/z (invz, as the monocular edge's).  er = kp_ur - (u_proj - bf / z).
+    auto project_st = [&](const MatchRec& m, float ur, const double* Rt, double& ex, double& ey, double& er, double& xz, double& yz,
+                          double& invz) -> double {
+        const double X0 = m.X, X1 = m.Y, X2 = m.Z;
+        const double p0 = fma(Rt[2], X2, fma(Rt[1], X1, fma(Rt[0], X0, Rt[9])));
+        const double p1 = fma(Rt[5], X2, fma(Rt[4], X1, fma(Rt[3], X0, Rt[10])));
+        const double p2 = fma(Rt[8], X2, fma(Rt[7], X1, fma(Rt[6], X0, Rt[11])));
+        invz = rcp_nr(p2);
+        xz = p0 * invz; yz = p1 * invz;
+        const double izf = (double)(float)(1.0 / p2);
+        const double r0 = p0 * izf * fx + cx, r1 = p1 * izf * fy + cy;
+        const double r2 = r0 - bf * izf;
+        ex = (double)m.u - r0;
+        ey = (double)m.v - r1;
+        er = (double)ur - r2;
+        return (double)m.invsig * fma(er, er, fma(ex, ex, ey * ey));
+    };
 
     // One pass over this thread's matches (every wave).  classify: first the reclassification that ends a round
     // (pnpsolver.cpp:358-371): a match that was excluded gets a fresh chi2 at RtC, the others the chi2 of the LAST pose the optimiser
@@ -305,24 +346,46 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
             const MatchRec m = rec[e];
             unsigned f = m.flags;
             double ex, ey, xz, yz, invz;
+            bool st = false;   // STEREO: this match has the three-row edge
+            float ur = 0.f;
+            double er = 0;
+            if constexpr (STEREO) { st = (f & kStereo) != 0; ur = urs[e]; }
             if (classify) {
                 double Rs[12];
 #pragma unroll
                 for (int i = 0; i < 12; i++) Rs[i] = s_pose[(f & kBad) ? 1 : 2][i];   // (read per match: four classifying passes per solve)
-                const double c = project(m, Rs, ex, ey, xz, yz, invz);
-                const bool b = c > (double)5.99f;
+                double c;
+                bool b;
+                if constexpr (STEREO) {
+                    c = st ? project_st(m, ur, Rs, ex, ey, er, xz, yz, invz) : project(m, Rs, ex, ey, xz, yz, invz);
+                    b = c > (st ? (double)7.815f : (double)5.99f);
+                } else {
+                    c = project(m, Rs, ex, ey, xz, yz, invz);
+                    b = c > (double)5.99f;
+                }
                 f = (b ? kBad : kActive) | (drop_robust ? 0u : (f & kRobust));
+                if constexpr (STEREO) f |= m.flags & kStereo;
                 rec[e].flags = f;
                 acc[28] += b ? 0.0 : 1.0;
             }
             if (!(f & kActive) || !accumulate) continue;
-            const double c = project(m, RtA, ex, ey, xz, yz, invz);
+            double c;
+            if constexpr (STEREO) c = st ? project_st(m, ur, RtA, ex, ey, er, xz, yz, invz) : project(m, RtA, ex, ey, xz, yz, invz);
+            else c = project(m, RtA, ex, ey, xz, yz, invz);
             const double w = m.invsig;
             double rho1 = 1.0, rc = c;
             if (f & kRobust) {
-                const double wt = m.weight;
-                if (c <= dsqr) rc = wt * c;
-                else { const double rs = rsq_nr(c); rc = wt * fma(2 * (c * rs), delta, -dsqr); rho1 = delta * rs; }
+                if constexpr (STEREO) {
+                    // the stereo edge's kernel weight is doubled in float (pnpsolver.cpp:258) and its threshold is thHuber3D
+                    const double wt = st ? (double)(m.weight * 2.f) : (double)m.weight;
+                    const double dl = st ? delta3 : delta, ds = st ? dsqr3 : dsqr;
+                    if (c <= ds) rc = wt * c;
+                    else { const double rs = rsq_nr(c); rc = wt * fma(2 * (c * rs), dl, -ds); rho1 = dl * rs; }
+                } else {
+                    const double wt = m.weight;
+                    if (c <= dsqr) rc = wt * c;
+                    else { const double rs = rsq_nr(c); rc = wt * fma(2 * (c * rs), delta, -dsqr); rho1 = delta * rs; }
+                }
             }
             acc[27] += rc;
             // 2x6 Jacobian rows (typesg2o.h:614-650): j = d ex / d xi, k = d ey / d xi; j[4] = k[3] = 0
@@ -347,6 +410,22 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
                 if (a != 4) v = fma(-sJ[a], ex, v);
                 if (a != 3) v = fma(-sK[a], ey, v);
                 acc[21 + a] = v;
+            }
+            if constexpr (STEREO) {
+                if (st) {
+                    // third Jacobian row (typesg2o.h:563-568): row 0 with the bf terms; l[2], l[3] = j[2], j[3]; l[4] = 0
+                    const double bi = bf * invz;
+                    const double L[6] = {j0 - bi * yz, j1 + bi * xz, j2, j3, 0.0, j5 - bi * invz};
+                    const double sL[6] = {s * L[0], s * L[1], s * L[2], s * L[3], 0.0, s * L[5]};
+#pragma unroll
+                    for (int a = 0; a < 6; a++)
+#pragma unroll
+                        for (int cc = a; cc < 6; cc++)
+                            if (a != 4 && cc != 4) acc[tri(a, cc)] = fma(sL[a], L[cc], acc[tri(a, cc)]);
+#pragma unroll
+                    for (int a = 0; a < 6; a++)
+                        if (a != 4) acc[21 + a] = fma(-sL[a], er, acc[21 + a]);
+                }
             }
         }
         int off = 0, real = kNS;
@@ -406,12 +485,26 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
                     const MatchRec m = rec[e];
                     if (!(m.flags & kActive)) continue;
                     double ex, ey, xz, yz, invz;
-                    const double c = project(m, Rt, ex, ey, xz, yz, invz);
-                    double rc = c;
-                    if (m.flags & kRobust) {
-                        const double wt = m.weight;
-                        if (c <= dsqr) rc = wt * c;
-                        else rc = wt * fma(2 * (c * rsq_nr(c)), delta, -dsqr);
+                    double rc;
+                    if constexpr (STEREO) {
+                        const bool st = (m.flags & kStereo) != 0;
+                        double er;
+                        const double c = st ? project_st(m, urs[e], Rt, ex, ey, er, xz, yz, invz) : project(m, Rt, ex, ey, xz, yz, invz);
+                        rc = c;
+                        if (m.flags & kRobust) {
+                            const double wt = st ? (double)(m.weight * 2.f) : (double)m.weight;
+                            const double dl = st ? delta3 : delta, ds = st ? dsqr3 : dsqr;
+                            if (c <= ds) rc = wt * c;
+                            else rc = wt * fma(2 * (c * rsq_nr(c)), dl, -ds);
+                        }
+                    } else {
+                        const double c = project(m, Rt, ex, ey, xz, yz, invz);
+                        rc = c;
+                        if (m.flags & kRobust) {
+                            const double wt = m.weight;
+                            if (c <= dsqr) rc = wt * c;
+                            else rc = wt * fma(2 * (c * rsq_nr(c)), delta, -dsqr);
+                        }
                     }
                     chi[k] += rc;
                 }
@@ -677,7 +770,7 @@ struct uh_pnp {
     uh::DevBuf d_work;
     uh::MappedBuf h_io;      // pinned, device-visible: [inputs | results | completion word]
     unsigned long long seq = 0;
-    bool attr_set = false;
+    bool attr_set = false, attr_set_st = false;
     long long* d_clk = nullptr;   // measurement hook (uh_pnp_debug_clocks)
     ~uh_pnp() { if (d_clk) (void)hipFree(d_clk); }
 };
@@ -687,6 +780,21 @@ namespace {
 int launch(uh_pnp* p, PnpArgs& A) {
     const int n = A.n;
     A.clk = p->d_clk;
+    if (A.depth) {   // stereo / RGB-D observations: the three-row edge where depth > 0
+        if (n <= kPnpLdsMatches) {
+            const size_t lds = (size_t)std::max(n, 1) * kPnpRecBytesStereo;
+            if (!p->attr_set_st) {
+                UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_solve_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 kPnpLdsMatches * kPnpRecBytesStereo));
+                p->attr_set_st = true;
+            }
+            UH_LAUNCH(p->ctx, (pnp_solve_kernel<true, true>), dim3(1), dim3(kPnpThreads), lds, A);
+        } else {
+            UH_LAUNCH(p->ctx, (pnp_solve_kernel<false, true>), dim3(1), dim3(kPnpThreads), 0, A);
+        }
+        UH_HIP_CHECK(hipGetLastError());
+        return UH_OK;
+    }
     if (n <= kPnpLdsMatches) {
         const size_t lds = (size_t)std::max(n, 1) * 32;
         if (!p->attr_set) {
@@ -706,17 +814,19 @@ int launch(uh_pnp* p, PnpArgs& A) {
 namespace uh {
 uh_ctx* pnp_ctx(uh_pnp* p) { return p->ctx; }
 // the solve behind uh_track_pose: everything resident, the match count decided by an earlier launch of the same stream
+// d_depth != NULL: the stereo form (per-match depth, baseline bl)
 int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec) {
+                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl) {
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     int rc;
-    if (n_cap > kPnpLdsMatches && (rc = p->d_work.reserve((size_t)n_cap * 32))) return rc;
+    if (n_cap > kPnpLdsMatches && (rc = p->d_work.reserve((size_t)n_cap * (d_depth ? kPnpRecBytesStereo : 32)))) return rc;
     PnpArgs A{};
     A.pose_in = d_pose; A.intr = d_intr4; A.n = n_cap; A.n_dev = d_n; A.p3d = d_p3d; A.kp = d_kp; A.invsig = d_inv_sigma; A.weight = d_weight;
     A.work = p->d_work.p;
     A.pose_out = d_pose_out; A.bad_out = d_bad_out; A.result = d_result5; A.state_out = nullptr;
     A.host_done = nullptr; A.done_word = 0;
     if (dec) A.dec = *dec;
+    A.depth = d_depth; A.bl = bl;
     return launch(p, A);
 }
 }  // namespace uh
@@ -749,23 +859,57 @@ int uh_pnp_solve_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, i
     return launch(p, A);
 }
 
+// Stereo / RGB-D form of uh_pnp_solve_dev: d_depth (n floats, device) as in uh_pnp_solve_stereo; d_work = n * 36 bytes when d_depth is given.
+// The depths are not read on the host, so a non-NULL d_depth needs bl > 0.  d_depth == NULL is uh_pnp_solve_dev itself.
+int uh_pnp_solve_stereo_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
+                            const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, void* d_work, float* d_pose_out,
+                            uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
+    if (!d_depth)
+        return uh_pnp_solve_dev(p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    UH_REQUIRE(p && d_pose_f2g && d_intr4 && d_pose_out && d_result5, "uh_pnp_solve_stereo_dev: NULL argument");
+    UH_REQUIRE(n >= 0, "uh_pnp_solve_stereo_dev: negative match count");
+    UH_REQUIRE(bl > 0.f, "uh_pnp_solve_stereo_dev: a depth array needs a baseline > 0 (bl = %g)", (double)bl);
+    if (n > 0) UH_REQUIRE(d_p3d && d_kp && d_inv_sigma && d_weight && d_work && d_bad_out, "uh_pnp_solve_stereo_dev: NULL match arrays");
+    UH_HIP_CHECK(hipSetDevice(p->ctx->device));
+    PnpArgs A{};
+    A.pose_in = d_pose_f2g; A.intr = d_intr4; A.n = n; A.p3d = d_p3d; A.kp = d_kp; A.invsig = d_inv_sigma; A.weight = d_weight;
+    A.work = d_work;
+    A.pose_out = d_pose_out; A.bad_out = d_bad_out; A.result = d_result5; A.state_out = d_state7;
+    A.host_done = nullptr; A.done_word = 0;
+    A.depth = d_depth; A.bl = bl;
+    return launch(p, A);
+}
+
 // Host-pointer form: PnPSolver::solvePnp(frame, map, matches, pose): returns the inlier count (>= 0) or a negative error.
 // The caller's arrays are packed into the object's pinned staging block (a few KB), the kernel reads them from there and writes
 // pose / flags / counters back into the same block; the host polls the completion word the kernel posts last.
 int uh_pnp_solve(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* inv_sigma,
                  const float* weight, float* pose_out, uint8_t* bad_out, int32_t* iters_out4, double* state_out7) {
-    UH_REQUIRE(p && pose_f2g && intr4 && pose_out, "uh_pnp_solve: NULL argument");
-    UH_REQUIRE(n >= 0, "uh_pnp_solve: negative match count");
+    return uh_pnp_solve_stereo(p, pose_f2g, intr4, n, p3d, kp, inv_sigma, weight, nullptr, 0.f, pose_out, bad_out, iters_out4, state_out7);
+}
+
+// Stereo / RGB-D form of uh_pnp_solve: depth[i] = Frame::getDepth(queryIdx) (<= 0: monocular match), bl = imageParams.bl.  depth == NULL
+// is uh_pnp_solve itself.
+int uh_pnp_solve_stereo(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* inv_sigma,
+                        const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out, int32_t* iters_out4, double* state_out7) {
+    const char* fn = depth ? "uh_pnp_solve_stereo" : "uh_pnp_solve";
+    UH_REQUIRE(p && pose_f2g && intr4 && pose_out, "%s: NULL argument", fn);
+    UH_REQUIRE(n >= 0, "%s: negative match count", fn);
     if (n == 0) { memcpy(pose_out, pose_f2g, 64); if (iters_out4) memset(iters_out4, 0, 16); return 0; }   // pnpsolver.cpp:149-150
-    UH_REQUIRE(p3d && kp && inv_sigma && weight && bad_out, "uh_pnp_solve: NULL match arrays");
+    UH_REQUIRE(p3d && kp && inv_sigma && weight && bad_out, "%s: NULL match arrays", fn);
+    if (depth) {
+        bool any = false;
+        for (int i = 0; i < n && !any; i++) any = !(depth[i] <= 0.f);
+        UH_REQUIRE(!any || bl > 0.f, "uh_pnp_solve_stereo: stereo matches need a baseline > 0 (bl = %g)", (double)bl);
+    }
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     const size_t nf = (size_t)n;
     auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
     const size_t o_done = 0, o_pout = 64, o_res = 128, o_state = 192, o_pose = 256, o_intr = 320, o_p3d = 384, o_kp = al(o_p3d + nf * 12), o_is = al(o_kp + nf * 8),
-                 o_w = al(o_is + nf * 4), o_bad = al(o_w + nf * 4), total = al(o_bad + nf);
+                 o_w = al(o_is + nf * 4), o_bad = al(o_w + nf * 4), o_dep = al(o_bad + nf), total = al(o_dep + (depth ? nf * 4 : 0));
     int rc;
     if ((rc = p->h_io.reserve(total))) return rc;
-    if (n > kPnpLdsMatches && (rc = p->d_work.reserve(nf * 32))) return rc;
+    if (n > kPnpLdsMatches && (rc = p->d_work.reserve(nf * (depth ? kPnpRecBytesStereo : 32)))) return rc;
     char* h = p->h_io.host<char>();
     char* d = p->h_io.dev<char>();
     memcpy(h + o_pose, pose_f2g, 64);
@@ -774,7 +918,9 @@ int uh_pnp_solve(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, co
     memcpy(h + o_kp, kp, nf * 8);
     memcpy(h + o_is, inv_sigma, nf * 4);
     memcpy(h + o_w, weight, nf * 4);
+    if (depth) memcpy(h + o_dep, depth, nf * 4);
     PnpArgs A{};
+    A.depth = depth ? (const float*)(d + o_dep) : nullptr; A.bl = bl;
     A.pose_in = (const float*)(d + o_pose); A.intr = (const float*)(d + o_intr); A.n = n;
     A.p3d = (const float*)(d + o_p3d); A.kp = (const float*)(d + o_kp); A.invsig = (const float*)(d + o_is); A.weight = (const float*)(d + o_w);
     A.work = p->d_work.p;
@@ -783,7 +929,7 @@ int uh_pnp_solve(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, co
     A.done_word = ++p->seq;
     std::atomic_thread_fence(std::memory_order_release);
     if ((rc = launch(p, A))) return rc;
-    if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(h + o_done), A.done_word, p->ctx->stream, "uh_pnp_solve"))) return rc;
+    if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(h + o_done), A.done_word, p->ctx->stream, fn))) return rc;
     int32_t res[5];
     memcpy(res, h + o_res, 20);
     memcpy(pose_out, h + o_pout, 64);

@@ -994,7 +994,7 @@ struct PmPending {
 int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn* dyn, int n, const float* pos3d, const float* normal,
                   const float* mn_dist, const float* mx_dist, const uint8_t* desc, const int32_t* octave, float min_desc_dist, float max_repj_dist, PmPending* pend,
                   float4* pos_out = nullptr, const uint32_t* ids = nullptr, const int32_t* rows = nullptr, const float* weights = nullptr, const float* weights_by_row = nullptr,
-                  uint4* aux_out = nullptr) {
+                  uint4* aux_out = nullptr, const float* prev_weights = nullptr) {
     const bool prev = octave != nullptr;
     uh_projmatch::Slot& S = h->slot[slot];
     UH_HIP_CHECK(hipSetDevice(h->ctx->device));
@@ -1023,7 +1023,8 @@ int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn*
             uint32_t* ax = reinterpret_cast<uint32_t*>(hi + o_pos + 64 * (size_t)n);
             for (int i = 0; i < n; i++, ax += 4) {
                 const int row = prev ? (rows ? rows[i] : -1) : i;
-                const float w = prev ? (row >= 0 && weights_by_row ? weights_by_row[row] : 1.f) : (weights ? weights[i] : 1.f);
+                // (prev_weights: uh_track_pose_stereo's weight of a previous-frame item outside the local map)
+                const float w = prev ? (row >= 0 ? (weights_by_row ? weights_by_row[row] : 1.f) : (prev_weights ? prev_weights[i] : 1.f)) : (weights ? weights[i] : 1.f);
                 ax[0] = ids[i]; std::memcpy(ax + 1, &row, 4); std::memcpy(ax + 2, &w, 4); ax[3] = 0;
             }
         }

@@ -23,7 +23,8 @@
 
 namespace uh {
 int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec);
+                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec,
+                    const float* d_depth = nullptr, float bl = 0.f);
 uh_ctx* pnp_ctx(uh_pnp* p);
 }
 
@@ -53,6 +54,9 @@ struct TrkSelect {
     int n_kpts;
     TrkElem* scratch_a; TrkElem* scratch_b;
     long long* clk;   // UH_TRK_CLK: 8 wall-clock stamps (10 ns) of thread 0
+    // uh_track_pose_stereo: the frame's per-keypoint depth (dep_src: pinned, copied once into dep_kp in HBM by the first launch; NULL in the
+    // second) and the per-match depth of the solve (dep); aux_weight: a previous-frame candidate's weight is its aux record's too
+    const float* dep_src; float* dep_kp; float* dep; int aux_weight;
 };
 
 // Exclusive prefix over the workgroup's per-thread counts; returns the thread's offset and (total) the sum.  Two barriers.
@@ -115,6 +119,8 @@ __global__ __launch_bounds__(kTrkThreads) void track_select_kernel(TrkSelect a, 
     const int tid = threadIdx.x;
 #define UH_TRK_STAMP(j) do { if (a.clk && tid == 0) a.clk[j] = wall_clock64(); } while (0)
     UH_TRK_STAMP(0);
+    if (a.dep_src)   // (read by this launch's look-ups after the barriers below, and by the second select launch)
+        for (int k = tid; k < a.n_kpts; k += kTrkThreads) a.dep_kp[k] = a.dep_src[k];
     UH_TRK_STAMP(1);
     // ---- the search's hits in candidate order
     int nF = 0;
@@ -181,7 +187,8 @@ __global__ __launch_bounds__(kTrkThreads) void track_select_kernel(TrkSelect a, 
         const int row = a.prefer_map_row ? (int)ax.y : -1;   // (first solve: the candidate's own position, weight 1)
         const float4 pos = row >= 0 ? a.pos_map[row] : a.pos_prev[idx];
         a.p3d[3 * p] = pos.x; a.p3d[3 * p + 1] = pos.y; a.p3d[3 * p + 2] = pos.z;
-        a.wgt[p] = row >= 0 ? __uint_as_float(ax.z) : 1.f;
+        a.wgt[p] = (row >= 0 || a.aux_weight) ? __uint_as_float(ax.z) : 1.f;
+        if (a.dep) a.dep[p] = a.dep_kp[e.query];
         const float4 k = a.kp_xyo[e.query];
         a.kp[2 * p] = k.x; a.kp[2 * p + 1] = k.y;
         const int oct = (int)(__float_as_uint(k.z) & 15u);
@@ -234,9 +241,10 @@ struct uh_track_state {
 
 uh_projmatch::~uh_projmatch() { delete track; }
 
-extern "C" {
+namespace {
 
-int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track_result* r) {
+// uh_track_pose (sx == NULL) and uh_track_pose_stereo
+int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, uh_track_result* r) {
     UH_REQUIRE(h && pnp && a && r, "uh_track_pose: NULL argument");
     UH_REQUIRE(h->have_frame && h->dev, "uh_track_pose: needs a device-resident frame (uh_orb_extract_frame_dev + uh_projmatch_set_frame_dev)");
     UH_REQUIRE(a->pose0 && a->intr4 && a->prev && a->map && a->inv_sigma_levels, "uh_track_pose: NULL input");
@@ -249,6 +257,17 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     if (nm) UH_REQUIRE(a->map->ids && a->map->pos3d && a->map->normal && a->map->min_dist && a->map->max_dist && a->map->desc, "uh_track_pose: map point arrays missing");
     for (int i = 0; i < np; i++)
         UH_REQUIRE(a->prev->octave[i] >= 0 && a->prev->octave[i] < h->n_levels, "uh_track_pose: octave %d of item %d outside [0,%d)", a->prev->octave[i], i, h->n_levels);
+    const bool stereo = sx && sx->depth;
+    if (sx) {
+        if (a->prev_map_row)
+            for (int i = 0; i < np; i++)
+                UH_REQUIRE(a->prev_map_row[i] >= -1 && a->prev_map_row[i] < nm, "uh_track_pose_stereo: prev_map_row %d of item %d outside [-1,%d)", a->prev_map_row[i], i, nm);
+        if (stereo) {
+            bool any = false;
+            for (int k = 0; k < nk && !any; k++) any = !(sx->depth[k] <= 0.f);
+            UH_REQUIRE(!any || sx->bl > 0.f, "uh_track_pose_stereo: stereo keypoints need a baseline > 0 (bl = %g)", (double)sx->bl);
+        }
+    }
     UH_REQUIRE(r->matches_prev && r->bad_prev && r->matches_map && r->matches_all && r->bad_all, "uh_track_pose: output buffers missing");
     UH_REQUIRE(h->ctx == uh::pnp_ctx(pnp), "uh_track_pose: matcher and solver belong to different contexts");
     UH_HIP_CHECK(hipSetDevice(h->ctx->device));
@@ -270,17 +289,20 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     const size_t o_sa = o; o = al(o + sizeof(TrkElem) * (size_t)capa); const size_t o_sb = o; o = al(o + sizeof(TrkElem) * (size_t)capa);
     const size_t o_posp = o; o = al(o + 16 * (size_t)cap1); const size_t o_posm = o; o = al(o + 16 * (size_t)cap2);
     const size_t o_auxp = o; o = al(o + 16 * (size_t)cap1); const size_t o_auxm = o; o = al(o + 16 * (size_t)cap2);
+    const size_t o_depk = o; o = al(o + (stereo ? 4 * (size_t)std::max(nk, 1) : 0)); const size_t o_dep = o; o = al(o + (stereo ? 4 * (size_t)capa : 0));
     if ((rc = T.d.reserve(o))) return rc;
     char* D = T.d.as<char>();
     // ---- pinned parameter block (read by the launches in place)
     size_t q = 64;
     const size_t q_pose0 = q; q += 64; const size_t q_intr = q; q += 64; const size_t q_isl = q; q += 64;
+    const size_t q_dep = q; q += stereo ? 4 * (size_t)nk : 0;
     if ((rc = T.h_par.reserve(q))) return rc;   // (the previous call's launches are complete: its results were awaited)
     char* hp = T.h_par.host<char>();
     char* dp = T.h_par.dev<char>();
     std::memcpy(hp + q_pose0, a->pose0, 64);
     std::memcpy(hp + q_intr, a->intr4, 16);
     std::memcpy(hp + q_isl, a->inv_sigma_levels, 4 * (size_t)a->n_levels);
+    if (stereo && nk) std::memcpy(hp + q_dep, sx->depth, 4 * (size_t)nk);
     // ---- pinned result block
     size_t w = 0;
     const size_t w_hdr = w; w = al(w + 4 * kTrkHdrInts); const size_t w_pose1 = w; w += 64; const size_t w_pose2 = w; w = al(w + 64);
@@ -297,7 +319,8 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     PmPending pd1, pd2;
     if (np) {
         if ((rc = match_enqueue(h, 0, a->pose0, nullptr, np, a->prev->pos3d, nullptr, nullptr, nullptr, a->prev->desc, a->prev->octave, a->prev_min_desc_dist, a->prev_max_repj_dist, &pd1,
-                                reinterpret_cast<float4*>(D + o_posp), a->prev->ids, a->prev_map_row, nullptr, a->map_weight, reinterpret_cast<uint4*>(D + o_auxp)))) return rc;
+                                reinterpret_cast<float4*>(D + o_posp), a->prev->ids, a->prev_map_row, nullptr, a->map_weight, reinterpret_cast<uint4*>(D + o_auxp),
+                                sx ? sx->prev_weight : nullptr))) return rc;
     }
     // (the map candidates are staged now, while the device works on the first search: slot 1 has its own pinned block)
     TrkSelect s1{};
@@ -312,6 +335,10 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     static const bool trk_clk = getenv("UH_TRK_CLK") != nullptr;
     if (trk_clk && !T.d_clk.p) { if ((rc = T.d_clk.reserve(16 * 8))) return rc; }
     s1.clk = trk_clk ? T.d_clk.as<long long>() : nullptr;
+    s1.dep_src = stereo ? reinterpret_cast<const float*>(dp + q_dep) : nullptr; s1.dep_kp = stereo ? reinterpret_cast<float*>(D + o_depk) : nullptr;
+    s1.dep = stereo ? reinterpret_cast<float*>(D + o_dep) : nullptr;
+    s1.aux_weight = sx && sx->prev_weight ? 1 : 0;
+    const float bl = stereo ? sx->bl : 0.f;
     // the select launches' working lists: in LDS while two lists of capa elements fit beside the per-keypoint table
     const size_t sel_lds = 2 * sizeof(TrkElem) * (size_t)capa;
     const bool sel_in_lds = sel_lds <= 120 * 1024;
@@ -326,7 +353,7 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     PmDyn* dyn = reinterpret_cast<PmDyn*>(D + o_dyn);
     const uh::PnpDecide dec{a->min_inliers, a->map_radius_tracked, a->map_radius_lost, reinterpret_cast<float*>(dyn), reinterpret_cast<float*>(D + o_posem), hdr + kTrkTracked};
     if ((rc = uh::pnp_enqueue_dev(pnp, reinterpret_cast<const float*>(dp + q_pose0), reinterpret_cast<const float*>(dp + q_intr), std::min(cap1, capn), hdr + kTrkN1, s1.p3d, s1.kp, s1.isg, s1.wgt,
-                                  reinterpret_cast<float*>(D + o_pose1), reinterpret_cast<unsigned char*>(D + o_bad1), hdr + kTrkRes1, &dec))) return rc;
+                                  reinterpret_cast<float*>(D + o_pose1), reinterpret_cast<unsigned char*>(D + o_bad1), hdr + kTrkRes1, &dec, s1.dep, bl))) return rc;
     // ---- 2: the search of the local map at the decided pose / radius (slot 1), the union, the second solve
     if (nm) {
         if ((rc = match_enqueue(h, 1, nullptr, dyn, nm, a->map->pos3d, a->map->normal, a->map->min_dist, a->map->max_dist, a->map->desc, nullptr, a->map_min_desc_dist, a->map_radius_tracked, &pd2,
@@ -339,10 +366,11 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     if (trk_clk) s2.clk = T.d_clk.as<long long>() + 8;
     s2.fresh_out = reinterpret_cast<uh_dmatch*>(D + o_m2); s2.fresh_src = reinterpret_cast<int*>(D + o_src2); s2.final_out = reinterpret_cast<uh_dmatch*>(D + o_ma); s2.final_src = reinterpret_cast<int*>(D + o_srca);
     s2.prefer_map_row = 1;
+    s2.dep_src = nullptr;   // (the first select launch left the frame's depths in dep_kp)
     if (sel_in_lds) UH_LAUNCH(h->ctx, track_select_kernel<true>, dim3(1), dim3(kTrkThreads), sel_lds, s2, capa);
     else UH_LAUNCH(h->ctx, track_select_kernel<false>, dim3(1), dim3(kTrkThreads), 0, s2, capa);
     if ((rc = uh::pnp_enqueue_dev(pnp, reinterpret_cast<const float*>(D + o_posem), reinterpret_cast<const float*>(dp + q_intr), capn, hdr + kTrkNA, s2.p3d, s2.kp, s2.isg, s2.wgt,
-                                  reinterpret_cast<float*>(D + o_pose2), reinterpret_cast<unsigned char*>(D + o_bada), hdr + kTrkRes2, nullptr))) return rc;
+                                  reinterpret_cast<float*>(D + o_pose2), reinterpret_cast<unsigned char*>(D + o_bada), hdr + kTrkRes2, nullptr, s2.dep, bl))) return rc;
     // ---- 3: everything back in one block
     char* ho = T.h_out.host<char>();
     char* dout = T.h_out.dev<char>();
@@ -387,6 +415,17 @@ int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track
     if (n2) std::memcpy(r->matches_map, ho + w_m2, 16 * (size_t)n2);
     if (na) { std::memcpy(r->matches_all, ho + w_ma, 16 * (size_t)na); std::memcpy(r->bad_all, ho + w_bada, (size_t)na); }
     return UH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track_result* r) { return track_pose(h, pnp, a, nullptr, r); }
+
+int uh_track_pose_stereo(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* stereo, uh_track_result* r) {
+    UH_REQUIRE(stereo, "uh_track_pose_stereo: NULL stereo argument");
+    return track_pose(h, pnp, a, stereo, r);
 }
 
 }  // extern "C"

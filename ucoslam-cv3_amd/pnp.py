@@ -1,9 +1,10 @@
-"""Host-side mirror of ucoslam::PnPSolver::solvePnp (monocular matches) on top of the C ABI.
+"""Host-side mirror of ucoslam::PnPSolver::solvePnp (monocular, stereo and RGB-D matches) on top of the C ABI.
 
 Reference: src/optimization/pnpsolver.h:30-38 / pnpsolver.cpp:116-409: `solvePnp(frame, map, matches, pose)` refines `pose`
 in place, marks outlier matches (DMatch::imgIdx = -1, inliers = 1) and returns the number of inliers.
 Here the frame/map lookups are already done: the caller passes, per match, the map point, the undistorted keypoint,
-1/scaleFactor[octave] and the stability weight (1, or 0.5 for MapPoint::isStable() == false).
+1/scaleFactor[octave] and the stability weight (1, or 0.5 for MapPoint::isStable() == false).  Stereo / RGB-D frames also pass
+Frame::getDepth(queryIdx) per match (<= 0: monocular match) and imageParams.bl (pnpsolver.cpp:205-276).
 """
 from __future__ import annotations
 
@@ -20,6 +21,8 @@ def _declare(L, sig):
     sig("uh_pnp_destroy", None, VP)
     sig("uh_pnp_solve", I, VP, VP, VP, I, VP, VP, VP, VP, VP, VP, VP, VP)
     sig("uh_pnp_solve_dev", I, VP, VP, VP, I, VP, VP, VP, VP, VP, VP, VP, VP, VP)
+    sig("uh_pnp_solve_stereo", I, VP, VP, VP, I, VP, VP, VP, VP, VP, C.c_float, VP, VP, VP, VP)
+    sig("uh_pnp_solve_stereo_dev", I, VP, VP, VP, I, VP, VP, VP, VP, VP, C.c_float, VP, VP, VP, VP, VP)
     sig("uh_pnp_debug_clocks", I, VP, I, VP)
 
 
@@ -32,13 +35,21 @@ class PnPSolver:
         self._h = VP()
         check(lib().uh_pnp_create(ctx.handle, C.byref(self._h)))
 
-    def solvePnp(self, pose_f2g, intr, p3d, kp, inv_sigma, weight):
-        """Returns dict(pose [16] float32, bad [n] uint8, iters [4], state [7] fp64, ngood)."""
+    def solvePnp(self, pose_f2g, intr, p3d, kp, inv_sigma, weight, depth=None, bl=0.0):
+        """Returns dict(pose [16] float32, bad [n] uint8, iters [4], state [7] fp64, ngood).  depth: None (monocular) or [n] float32
+        Frame::getDepth per match, with bl = imageParams.bl (> 0 when any depth is > 0)."""
         a = [np.ascontiguousarray(x, np.float32) for x in (pose_f2g, intr, p3d, kp, inv_sigma, weight)]
         n = len(a[4])
         out = dict(pose=np.zeros(16, np.float32), bad=np.zeros(max(n, 1), np.uint8), iters=np.zeros(4, np.int32), state=np.zeros(7, np.float64))
-        rc = lib().uh_pnp_solve(self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]), np_ptr(out["pose"]),
-                                np_ptr(out["bad"]), np_ptr(out["iters"]), np_ptr(out["state"]))
+        if depth is None:
+            rc = lib().uh_pnp_solve(self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]), np_ptr(out["pose"]),
+                                    np_ptr(out["bad"]), np_ptr(out["iters"]), np_ptr(out["state"]))
+        else:
+            d = np.ascontiguousarray(depth, np.float32)
+            if d.shape != (n,):
+                raise ValueError(f"depth: expected {n} values, got shape {d.shape}")
+            rc = lib().uh_pnp_solve_stereo(self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]), np_ptr(d),
+                                           float(bl), np_ptr(out["pose"]), np_ptr(out["bad"]), np_ptr(out["iters"]), np_ptr(out["state"]))
         if rc < 0:
             check(rc)
         out["ngood"] = rc

@@ -45,8 +45,13 @@ class _TrackResult(C.Structure):
                 ("iters1", C.c_int32 * 4), ("iters2", C.c_int32 * 4), ("pose1", C.c_float * 16), ("pose2", C.c_float * 16)]
 
 
+class _TrackStereo(C.Structure):
+    _fields_ = [("depth", VP), ("bl", C.c_float), ("prev_weight", VP)]
+
+
 def _declare(L, sig):
     sig("uh_track_pose", I, VP, VP, C.POINTER(_TrackArgs), C.POINTER(_TrackResult))
+    sig("uh_track_pose_stereo", I, VP, VP, C.POINTER(_TrackArgs), C.POINTER(_TrackStereo), C.POINTER(_TrackResult))
     sig("uh_projmatch_create", I, VP, C.POINTER(VP))
     sig("uh_projmatch_destroy", None, VP)
     sig("uh_projmatch_set_frame", I, VP, C.POINTER(_ProjFrame))
@@ -171,6 +176,20 @@ class ProjectionMatcher:
         frame as ONE call (system.cpp:5930-6954).  prev: dict(ids, pos3d, octave, desc); mp: dict(ids, pos3d, normal, min_dist, max_dist, desc);
         the frame is the device-resident one given to setFrameDev.  Returns dict(matches_prev, bad_prev, matches_map, matches_all, bad_all,
         tracked, inliers1, inliers2, iters1, iters2, pose1, pose2)."""
+        return self._track(pnp, pose0, intr4, inv_sigma_levels, prev, mp, prev_map_row, map_weight, prev_min_desc_dist, prev_max_repj_dist,
+                           map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, None)
+
+    def trackPoseStereo(self, pnp, pose0, intr4, inv_sigma_levels, prev, mp, depth=None, bl=0.0, prev_weight=None, prev_map_row=None, map_weight=None,
+                        prev_min_desc_dist=75.0, prev_max_repj_dist=15.0, map_min_desc_dist=100.0, map_radius_tracked=4.0, map_radius_lost=15.0,
+                        min_inliers=30):
+        """uh_track_pose_stereo: trackPose for stereo / RGB-D frames.  depth: [n_kpts] Frame::getDepth per keypoint of the frame (<= 0: none)
+        or None; bl: imageParams.bl; prev_weight: [prev n] MapPoint::isStable weight (1 / 0.5) of each previous-frame item or None.
+        Same result dict as trackPose."""
+        return self._track(pnp, pose0, intr4, inv_sigma_levels, prev, mp, prev_map_row, map_weight, prev_min_desc_dist, prev_max_repj_dist,
+                           map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, (depth, bl, prev_weight))
+
+    def _track(self, pnp, pose0, intr4, inv_sigma_levels, prev, mp, prev_map_row, map_weight, prev_min_desc_dist, prev_max_repj_dist,
+               map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, stereo):
         pose = np.ascontiguousarray(pose0, np.float32).reshape(16)
         intr = np.ascontiguousarray(intr4, np.float32).reshape(4)
         isl = np.ascontiguousarray(inv_sigma_levels, np.float32)
@@ -192,7 +211,15 @@ class ProjectionMatcher:
         m2 = np.zeros(max(n_m, 1), DMATCH_DTYPE)
         mA = np.zeros(max(n_p + n_m, 1), DMATCH_DTYPE); bA = np.zeros(max(n_p + n_m, 1), np.uint8)
         res = _TrackResult(np_ptr(m1), np_ptr(b1), len(m1), np_ptr(m2), len(m2), np_ptr(mA), np_ptr(bA), len(mA))
-        check(lib().uh_track_pose(self._h, pnp._h, C.byref(args), C.byref(res)))
+        if stereo is None:
+            check(lib().uh_track_pose(self._h, pnp._h, C.byref(args), C.byref(res)))
+        else:
+            dep = np.ascontiguousarray(stereo[0], np.float32) if stereo[0] is not None else None
+            pw = np.ascontiguousarray(stereo[2], np.float32) if stereo[2] is not None else None
+            if pw is not None and pw.shape != (n_p,):
+                raise ValueError(f"prev_weight: expected {n_p} values, got shape {pw.shape}")
+            sx = _TrackStereo(np_ptr(dep) if dep is not None else None, float(stereo[1]), np_ptr(pw) if pw is not None and n_p else None)
+            check(lib().uh_track_pose_stereo(self._h, pnp._h, C.byref(args), C.byref(sx), C.byref(res)))
         return dict(matches_prev=m1[: res.n_prev].copy(), bad_prev=b1[: res.n_prev].copy(), matches_map=m2[: res.n_map].copy(), matches_all=mA[: res.n_all].copy(),
                     bad_all=bA[: res.n_all].copy(), tracked=bool(res.tracked), inliers1=res.inliers1, inliers2=res.inliers2, iters1=np.array(res.iters1[:], np.int32),
                     iters2=np.array(res.iters2[:], np.int32), pose1=np.array(res.pose1[:], np.float32), pose2=np.array(res.pose2[:], np.float32))
