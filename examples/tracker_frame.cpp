@@ -8,12 +8,16 @@
 //                                    tree, no host CPU time, but ~105 us on one compute unit
 //                                    against ~50 us on a host core: not the default
 //   tracker: previous-frame search   project the previous frame's map points, match          uh_projmatch_match_prev  utils/system.cpp:5930-6460 (call :6559-6565)
-//   PnPSolver::solvePnp              pose from those matches (4 x 10 LM iterations)           uh_pnp_solve             optimization/pnpsolver.cpp:116-409 (call system.cpp:6626)
-//   Map::matchFrameToMapPoints       the local map projected with the refined pose, 4-px disc  uh_projmatch_match       map.cpp:651-770 (call system.cpp:6897; radius :6762-6881)
+//   PnPSolver::solvePnp              pose from those matches (4 x 10 LM iterations), run       uh_pnp_solve             optimization/pnpsolver.cpp:116-409 (call system.cpp:6626)
+//                                    only with more than 30 of them (:6595)
+//   Map::matchFrameToMapPoints       the local map projected with the refined pose, 4-px disc, uh_projmatch_match       map.cpp:651-770 (call system.cpp:6897; radius :6813-6877)
+//                                    without the points the first search matched (:6842)
 //   PnPSolver::solvePnp              pose from the union of both match sets                   uh_pnp_solve             (call system.cpp:6954)
 //
-// The host glue between the calls is the reference's own (keypoint / map point look-ups per DMatch, pnpsolver.cpp:199-232; the second
-// match set is appended to the first and filter_ambiguous_query runs over the union, system.cpp:6897-6954).
+// The host glue between the calls is the reference's own (keypoint / map point look-ups per DMatch, pnpsolver.cpp:199-232; with more than
+// 30 inliers every first match is kept and its point marked seen, the second match set is appended to the first and filter_ambiguous_query
+// runs over the union, system.cpp:6813-6954).  The FrameMatcher fallback of a frame with 30 matches or fewer (:6664-6780) is not run here:
+// it is taken to find nothing.
 // Scene: a synthetic 1241 x 376 frame (rectangles + noise); its map is made FROM the frame's own features — a map point behind most
 // keypoints (back-projected with a ground-truth pose, descriptor = the keypoint's with a few flipped bits), plus unrelated points —
 // so every stage works on data the previous one produced.  Prints one JSON line with the median per-stage and per-frame latencies.
@@ -224,6 +228,8 @@ int main(int argc, char** argv) {
 
     // ---- the per-frame chain
     std::vector<uh_dmatch> m_prev(N_PREV), m_map(N_MAP), m_all;
+    std::vector<int32_t> best_kp(N_MAP);
+    std::vector<float> best_d(N_MAP);
     std::vector<float> p3d, kp2, isg, wgt;
     std::vector<uint8_t> bad;
     // uh_track_pose's view of the map bookkeeping: per previous-frame item its row in the local map (TheMap->map_points[id]), per map point its solver weight
@@ -296,25 +302,45 @@ int main(int argc, char** argv) {
                 while (sc.prev_ids[cur] != (uint32_t)m_prev[i].trainIdx) ++cur;
                 const uh_keypoint& k = kps[m_prev[i].queryIdx];
                 for (int c2 = 0; c2 < 3; c2++) p3d[3 * i + c2] = sc.prev_pos[3 * cur + c2];
-                kp2[2 * i] = k.x; kp2[2 * i + 1] = k.y; isg[i] = inv_sf[k.octave]; wgt[i] = 1.f;
+                // (pnpsolver.cpp:210-211: a point of the local map weighs as its map entry, one outside it as stable here)
+                const int row = (size_t)m_prev[i].trainIdx < sc.id_to_map.size() ? sc.id_to_map[m_prev[i].trainIdx] : -1;
+                kp2[2 * i] = k.x; kp2[2 * i + 1] = k.y; isg[i] = inv_sf[k.octave]; wgt[i] = row >= 0 && sc.map_unstable[row] ? 0.5f : 1.f;
             }
         }
         const double t4 = now_us();
         float pose1[16]; int32_t iters[4];
-        const int in1 = uh_pnp_solve(pnp, sc.pose0, intr, n1, p3d.data(), kp2.data(), isg.data(), wgt.data(), pose1, bad.data(), iters, nullptr);
+        // system.cpp:6595-6646: the first solve runs with more than 30 matches (else the FrameMatcher fallback, here: nothing found, 0 inliers)
+        int in1 = 0;
+        if (n1 > 30) in1 = uh_pnp_solve(pnp, sc.pose0, intr, n1, p3d.data(), kp2.data(), isg.data(), wgt.data(), pose1, bad.data(), iters, nullptr);
         CHECK(in1);
         const double t5 = now_us();
         const uh_map_points mp{N_MAP, sc.map_ids.data(), sc.map_pos.data(), sc.map_nrm.data(), sc.map_min.data(), sc.map_max.data(), sc.map_desc.data()};
-        // system.cpp:6762-6881: with at least 30 inliers the refined pose is kept and the local map is searched in a 4-pixel disc; otherwise
-        // the first matches are dropped, the predicted pose stays and the search radius is projDistThr again
-        const bool tracked = in1 >= 30;
+        // system.cpp:6813-6877: with more than 30 inliers the refined pose is kept, every first match stays and its point counts as seen, and
+        // the local map is searched in a 4-pixel disc; otherwise the first matches are dropped, the predicted pose stays and the search radius
+        // is projDistThr again
+        const bool tracked = in1 > 30;
         const float* pose_for_map = tracked ? pose1 : sc.pose0;
-        const int n2 = uh_projmatch_match(pm, pose_for_map, &mp, MAX_DESC_DIST * 2.f, tracked ? 4.f : PROJ_DIST_THR, m_map.data(), (int)m_map.size(), nullptr, nullptr, nullptr);
+        int n2 = uh_projmatch_match(pm, pose_for_map, &mp, MAX_DESC_DIST * 2.f, tracked ? 4.f : PROJ_DIST_THR, m_map.data(), (int)m_map.size(), best_kp.data(), best_d.data(), nullptr);
         CHECK(n2);
+        if (tracked) {
+            // map.cpp:657-668: the points seen this frame are not searched — their hits go before filter_ambiguous_query (each point is searched
+            // on its own, so that is the same)
+            bool any = false;
+            for (int i = 0; i < n1; i++) {
+                const int row = (size_t)m_prev[i].trainIdx < sc.id_to_map.size() ? sc.id_to_map[m_prev[i].trainIdx] : -1;
+                if (row >= 0 && best_kp[row] >= 0) { best_kp[row] = -1; any = true; }
+            }
+            if (any) {
+                n2 = 0;
+                for (int r = 0; r < N_MAP; r++) if (best_kp[r] >= 0) m_map[n2++] = uh_dmatch{best_kp[r], (int32_t)sc.map_ids[r], -1, best_d[r]};
+                n2 = n2 ? uh_filter_ambiguous(m_map.data(), n2, 0) : 0;
+                CHECK(n2);
+            }
+        }
         const double t6 = now_us();
-        // system.cpp:6897-6954: inliers of the first set + the new matches, filter_ambiguous_query over the union, then the per-match look-ups
+        // system.cpp:6913-6954: the first set (when tracked) + the new matches, filter_ambiguous_query over the union, then the per-match look-ups
         m_all.clear();
-        if (tracked) for (int i = 0; i < n1; i++) if (!bad[i]) m_all.push_back(m_prev[i]);
+        if (tracked) m_all.insert(m_all.end(), m_prev.begin(), m_prev.begin() + n1);
         const int kept1 = (int)m_all.size();
         m_all.insert(m_all.end(), m_map.begin(), m_map.begin() + n2);
         const int na = m_all.empty() ? 0 : uh_filter_ambiguous(m_all.data(), (int)m_all.size(), 0);

@@ -685,16 +685,27 @@ typedef struct uh_prev_points {
 int  uh_projmatch_match_prev(uh_projmatch* pm, const float* pose_f2g /* row-major 4x4 */, const uh_prev_points* points,
                              float min_desc_dist, float max_repj_dist, uh_dmatch* matches_out, int32_t cap,
                              int32_t* best_kp_out /* n or NULL */, float* best_dist_out /* n or NULL */);
-/* The tracker's pose estimation for one frame as ONE call: the search against the previous frame, PnPSolver::solvePnp, the decision
- * (>= min_inliers inliers: refined pose + small disc, else predicted pose + wide radius), Map::matchFrameToMapPoints, the union of the first
- * solve's inliers with the new matches under filter_ambiguous_query, the per-match look-ups and the second solvePnp (src/utils/system.cpp
- * :5930-6460, :6559-6566, :6762-6881, :6897-6954 after preprocessing; pnpsolver.cpp:116-409) — exactly what
- *     uh_projmatch_match_prev -> look-ups -> uh_pnp_solve -> uh_projmatch_match -> union, uh_filter_ambiguous, look-ups -> uh_pnp_solve
- * return, bit for bit, with the look-ups and list handling done on the device between the launches and ONE wait at the end (seven launches on
- * the context stream; csrc/track.hpp).  The look-ups: first solve — the candidate's own position, weight 1; second solve — the position and
- * weight of row prev_map_row[i] of `map` when that is >= 0 (a previous-frame item that is also in the local map), else the candidate's own;
- * keypoint = the frame's undistorted keypoint, inv_sigma = inv_sigma_levels[its octave].  Needs a device-resident frame
- * (uh_orb_extract_frame_dev + uh_projmatch_set_frame_dev, either tree builder) of <= 4096 keypoints; pm and pnp on the same context. */
+/* The tracker's pose estimation for one frame as ONE call (src/utils/system.cpp:6559-6954, raw line numbers of the statement starts;
+ * pnpsolver.cpp:116-409; map.cpp:651-770), on the device between the launches with ONE wait at the end (csrc/track.hpp):
+ *   - the search against the previous frame (uh_projmatch_match_prev);
+ *   - with MORE than min_inliers matches (:6595) the first PnPSolver::solvePnp from pose0 (:6626).  With min_inliers matches or fewer the
+ *     reference runs its FrameMatcher fallback against the reference keyframe (:6664-6780), which this call does not: it reports no first
+ *     solve (inliers1 = 0, iters1 = 0, pose1 = pose0, bad_prev all 0), as if the fallback had found nothing.  A caller that has the
+ *     fallback runs it itself when n_prev <= min_inliers;
+ *   - the decision (:6646, :6813): tracked iff inliers1 is MORE than min_inliers — the refined pose and map_radius_tracked, and EVERY match
+ *     of the first search (its outliers too: solvePnp only flags them, :6842) is kept and its map point marked as seen this frame; else
+ *     pose0, map_radius_lost and the first matches are dropped (:6877);
+ *   - Map::matchFrameToMapPoints over `map` (:6897) without the points seen this frame (map.cpp:657-668): a candidate whose row is the
+ *     prev_map_row of a first-search match cannot match; matches_map is that search's list after this exclusion;
+ *   - the union of the kept first matches and matches_map under filter_ambiguous_query (:6913, :6931) and the second solvePnp from the
+ *     decided pose (:6954).
+ * The same as uh_projmatch_match_prev -> look-ups -> uh_pnp_solve -> uh_projmatch_match -> exclusion, union, uh_filter_ambiguous,
+ * look-ups -> uh_pnp_solve one after the other, bit for bit.  Look-ups: keypoint = the frame's undistorted keypoint, inv_sigma =
+ * inv_sigma_levels[its octave]; first solve — the candidate's own position; second solve — the position of row prev_map_row[i] of `map`
+ * when that is >= 0, else the candidate's own.  Weight, in both solves (pnpsolver.cpp:210-211): map_weight[prev_map_row[i]] for an item
+ * with prev_map_row[i] >= 0, map_weight of its row for a map candidate, 1 for a previous-frame item outside the local map — this entry has
+ * no input for those items' stability (uh_track_pose_stereo's prev_weight has).  Needs a device-resident frame (uh_orb_extract_frame_dev +
+ * uh_projmatch_set_frame_dev, either tree builder) of <= 4096 keypoints; pm and pnp on the same context. */
 typedef struct uh_track_args {
     const float* pose0;                 /* predicted pose f2g, row-major 4x4 */
     const float* intr4;                 /* fx fy cx cy */
@@ -706,11 +717,11 @@ typedef struct uh_track_args {
     const float* map_weight;            /* map->n: the solver weight of each map point (0.5 for unstable ones); NULL = all 1 */
     float prev_min_desc_dist, prev_max_repj_dist;   /* system.cpp:6559-6565: maxDescDistance * 1.5, projDistThr */
     float map_min_desc_dist, map_radius_tracked, map_radius_lost;   /* :6762-6881: maxDescDistance * 2, 4 px, projDistThr */
-    int32_t min_inliers;                /* 30 */
+    int32_t min_inliers;                /* 30: the first solve runs with MORE matches than this, the frame is tracked with MORE inliers */
 } uh_track_args;
 typedef struct uh_track_result {
     uh_dmatch* matches_prev; uint8_t* bad_prev; int32_t cap_prev;    /* in: buffers (>= prev->n); out: the first search's matches and the first solve's outlier flags */
-    uh_dmatch* matches_map; int32_t cap_map;                          /* >= map->n: the second search's own matches */
+    uh_dmatch* matches_map; int32_t cap_map;                          /* >= map->n: the second search's own matches (points seen by the first search excluded) */
     uh_dmatch* matches_all; uint8_t* bad_all; int32_t cap_all;        /* >= prev->n + map->n: the union the second solve ran on, its outlier flags */
     int32_t n_prev, n_map, n_all, tracked, inliers1, inliers2;
     int32_t iters1[4], iters2[4];
@@ -720,9 +731,9 @@ int  uh_track_pose(uh_projmatch* pm, uh_pnp* pnp, const uh_track_args* args, uh_
 /* uh_track_pose for stereo / RGB-D frames: both solves are uh_pnp_solve_stereo's, with depth[queryIdx] gathered per match on the device.
  *   depth        the frame's n keypoints: Frame::getDepth per keypoint (<= 0: none); NULL = monocular (the solves of uh_track_pose)
  *   bl           imageParams.bl; > 0 when any depth is > 0
- *   prev_weight  prev->n: the solver weight (MapPoint::isStable: 1 or 0.5) of each previous-frame item, or NULL (= uh_track_pose: weight 1,
- *                except the second solve's items with prev_map_row >= 0, which take map_weight).  Given, an item's weight in both solves is
- *                map_weight[prev_map_row] when that row is >= 0, else prev_weight[i] (pnpsolver.cpp:210-211 in every solvePnp call).
+ *   prev_weight  prev->n: the solver weight (MapPoint::isStable: 1 or 0.5) of each previous-frame item, or NULL (= uh_track_pose: weight 1
+ *                for items outside the local map).  An item's weight in both solves is map_weight[prev_map_row] when that row is >= 0, else
+ *                prev_weight[i] (pnpsolver.cpp:210-211 in every solvePnp call).
  * The caller passes the same weights as for monocular frames (the stereo edges double theirs inside the solver).  Also refuses a
  * prev_map_row outside [-1, map->n).  With depth == NULL and prev_weight == NULL the results equal uh_track_pose's. */
 typedef struct uh_track_stereo {

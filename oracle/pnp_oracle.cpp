@@ -8,6 +8,9 @@
 //           3rdparty/g2o: BaseUnaryEdge::constructQuadraticForm (base_unary_edge.hpp:55-78), Levenberg (as ba_oracle.cpp),
 //           SparseOptimizer::optimize(iterations, minChi2BetweenIter = 0)  (sparse_optimizer.h:120).
 // Pinned against the real g2o (oracle/_ref/libg2o_ref.so, driver g2o_ref_pnp_solve) by tests/test_pnp.py.
+// oracle_pnp_solve_stereo adds  typesg2o.h:521-588  EdgeStereoSE3ProjectXYZOnlyPose (cam_project rounds 1/z to float, the Jacobian uses
+// the double 1/z) for matches with depth > 0, built as pnpsolver.cpp:205-276 does (kp_ur = x - mbf / depth in float, weight doubled,
+// Huber sqrt(7.815), relabelling at 7.815); pinned against tests/golden/pnp_stereo_golden.npz (real g2o) by tests/test_track_oracle.py.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -71,6 +74,10 @@ struct PnP {
     int n;
     const float* p3d; const float* kp; const float* invsig; const float* weight;
     double fx, fy, cx, cy, delta;
+    // stereo form: per edge 0 = monocular, 1 = stereo; its measured right x (kp_ur), bf = mbf, the 3-D Huber width and its doubled weights
+    std::vector<char> st;
+    std::vector<float> ur, w3;
+    double bf = 0, delta3 = 0;
     Pose T;
     std::vector<char> active, robust;
     std::vector<double> err, chi2;
@@ -82,22 +89,43 @@ struct PnP {
         ex = kp[2 * e] - ((pc[0] / pc[2]) * fx + cx);
         ey = kp[2 * e + 1] - ((pc[1] / pc[2]) * fy + cy);
     }
+    // EdgeStereoSE3ProjectXYZOnlyPose::computeError: obs - cam_project(pc), invz = (float)(1 / z)
+    void edge_error3(int e, const double R[9], double* ev, double pc[3]) const {
+        const float* X = p3d + 3 * e;
+        for (int r = 0; r < 3; r++) pc[r] = R[r * 3] * X[0] + R[r * 3 + 1] * X[1] + R[r * 3 + 2] * X[2] + T.t[r];
+        const float invz = 1.0f / pc[2];
+        const double u = pc[0] * invz * fx + cx, v = pc[1] * invz * fy + cy;
+        ev[0] = kp[2 * e] - u;
+        ev[1] = kp[2 * e + 1] - v;
+        ev[2] = ur[e] - (u - bf * invz);
+    }
+    bool stereo(int e) const { return !st.empty() && st[e]; }
+    double& chi2_of(int e, const double R[9]) {   // the edge's error and chi2 at rotation R (information = invsigma * I)
+        double pc[3];
+        double* ev = &err[3 * e];
+        if (stereo(e)) {
+            edge_error3(e, R, ev, pc);
+            chi2[e] = (double)invsig[e] * (ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2]);
+        } else {
+            edge_error(e, R, ev[0], ev[1], pc);
+            chi2[e] = (double)invsig[e] * (ev[0] * ev[0] + ev[1] * ev[1]);
+        }
+        return chi2[e];
+    }
     void compute_errors() {
         double R[9]; quat_to_R(T.q, R);
         for (int e = 0; e < n; e++) {
             if (!active[e]) continue;
-            double pc[3];
-            edge_error(e, R, err[2 * e], err[2 * e + 1], pc);
-            chi2[e] = (double)invsig[e] * (err[2 * e] * err[2 * e] + err[2 * e + 1] * err[2 * e + 1]);
+            chi2_of(e, R);
         }
     }
     double robust_chi2() const {
-        const double dsqr = delta * delta;
         double s = 0;
         for (int e = 0; e < n; e++) {
             if (!active[e]) continue;
             const double c = chi2[e];
-            if (robust[e]) s += (c <= dsqr) ? (double)weight[e] * c : (double)weight[e] * (2 * std::sqrt(c) * delta - dsqr);
+            const double d = stereo(e) ? delta3 : delta, dsqr = d * d, w = stereo(e) ? (double)w3[e] : (double)weight[e];
+            if (robust[e]) s += (c <= dsqr) ? w * c : w * (2 * std::sqrt(c) * d - dsqr);
             else s += c;
         }
         return s;
@@ -105,20 +133,32 @@ struct PnP {
     void build() {
         std::memset(H, 0, sizeof(H)); std::memset(b, 0, sizeof(b));
         double R[9]; quat_to_R(T.q, R);
-        const double dsqr = delta * delta;
         for (int e = 0; e < n; e++) {
             if (!active[e]) continue;
-            double pc[3], ex, ey;
-            edge_error(e, R, ex, ey, pc);
+            const bool s3 = stereo(e);
+            const double d = s3 ? delta3 : delta, dsqr = d * d;
+            double pc[3], ev[3];
+            if (s3) edge_error3(e, R, ev, pc);
+            else edge_error(e, R, ev[0], ev[1], pc);
             const double X = pc[0], Y = pc[1], invz = 1.0 / pc[2], invz2 = invz * invz;
-            const double J[12] = {X * Y * invz2 * fx, -(1 + (X * X * invz2)) * fx, Y * invz * fx, -invz * fx, 0, X * invz2 * fx,
-                                  (1 + Y * Y * invz2) * fy, -X * Y * invz2 * fy, -X * invz * fy, 0, -invz * fy, Y * invz2 * fy};
+            double J[18] = {X * Y * invz2 * fx, -(1 + (X * X * invz2)) * fx, Y * invz * fx, -invz * fx, 0, X * invz2 * fx,
+                                  (1 + Y * Y * invz2) * fy, -X * Y * invz2 * fy, -X * invz * fy, 0, -invz * fy, Y * invz2 * fy,
+                                  0, 0, 0, 0, 0, 0};
+            double* J2 = J + 12;
+            if (s3) {   // typesg2o.h: the third row
+                J2[0] = J[0] - bf * Y * invz2; J2[1] = J[1] + bf * X * invz2; J2[2] = J[2]; J2[3] = J[3]; J2[4] = 0; J2[5] = J[5] - bf * invz2;
+            }
             const double w = invsig[e];
             double rho1 = 1.0;
-            if (robust[e] && chi2[e] > dsqr) rho1 = delta / std::sqrt(chi2[e]);
+            if (robust[e] && chi2[e] > dsqr) rho1 = d / std::sqrt(chi2[e]);
             for (int a = 0; a < 6; a++) {
-                b[a] -= rho1 * (J[a] * w * err[2 * e] + J[6 + a] * w * err[2 * e + 1]);
-                for (int c = 0; c < 6; c++) H[a * 6 + c] += (rho1 * w) * (J[a] * J[c] + J[6 + a] * J[6 + c]);
+                if (s3) {
+                    b[a] -= rho1 * (J[a] * w * ev[0] + J[6 + a] * w * ev[1] + J2[a] * w * ev[2]);
+                    for (int c = 0; c < 6; c++) H[a * 6 + c] += (rho1 * w) * (J[a] * J[c] + J[6 + a] * J[6 + c] + J2[a] * J2[c]);
+                } else {
+                    b[a] -= rho1 * (J[a] * w * ev[0] + J[6 + a] * w * ev[1]);
+                    for (int c = 0; c < 6; c++) H[a * 6 + c] += (rho1 * w) * (J[a] * J[c] + J[6 + a] * J[6 + c]);
+                }
             }
         }
     }
@@ -187,22 +227,18 @@ struct PnP {
 
 }  // namespace
 
-extern "C" int oracle_pnp_solve(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
-                                const float* weight, float* pose_out, uint8_t* bad_out, int32_t* iters_out /*4*/, double* state_out /*7*/) {
-    PnP s;
-    s.n = n; s.p3d = p3d; s.kp = kp; s.invsig = invsigma; s.weight = weight;
-    s.fx = intr4[0]; s.fy = intr4[1]; s.cx = intr4[2]; s.cy = intr4[3];
-    s.delta = (double)(float)std::sqrt(5.99);   // const float thHuber2D = sqrt(5.99)
+// the loop of PnPSolver::solvePnp (pnpsolver.cpp:116-409) over the prepared edges
+static int pnp_run(PnP& s, const float* pose_f2g, int n, float* pose_out, uint8_t* bad_out, int32_t* iters_out, double* state_out) {
     const double R0[9] = {pose_f2g[0], pose_f2g[1], pose_f2g[2], pose_f2g[4], pose_f2g[5], pose_f2g[6], pose_f2g[8], pose_f2g[9], pose_f2g[10]};
     Pose T0;
     quat_from_R(R0, T0.q);
     quat_norm_pos(T0.q);
     T0.t[0] = pose_f2g[3]; T0.t[1] = pose_f2g[7]; T0.t[2] = pose_f2g[11];
     s.T = T0;
-    s.active.assign(n, 1); s.robust.assign(n, 1); s.err.assign(2 * (size_t)n, 0.0); s.chi2.assign(n, 0.0);
+    s.active.assign(n, 1); s.robust.assign(n, 1); s.err.assign(3 * (size_t)n, 0.0); s.chi2.assign(n, 0.0);
     std::vector<char> bad(n, 0);
     for (int it = 0; it < 4; it++) iters_out[it] = 0;
-    const float Chi2D = 5.99f;
+    const float Chi2D = 5.99f, Chi3D = 7.815f;
     if (n > 0)
         for (int it = 0; it < 4; it++) {
             s.T = T0;                                   // every round restarts from the input pose (:354)
@@ -210,12 +246,8 @@ extern "C" int oracle_pnp_solve(const float* pose_f2g, const float* intr4, int n
             int nGood = 0;
             double R[9]; quat_to_R(s.T.q, R);
             for (int e = 0; e < n; e++) {
-                if (bad[e]) {                           // excluded edges get a fresh error at the new pose (:364)
-                    double pc[3];
-                    s.edge_error(e, R, s.err[2 * e], s.err[2 * e + 1], pc);
-                    s.chi2[e] = (double)invsigma[e] * (s.err[2 * e] * s.err[2 * e] + s.err[2 * e + 1] * s.err[2 * e + 1]);
-                }
-                bad[e] = s.chi2[e] > (double)Chi2D;
+                if (bad[e]) s.chi2_of(e, R);            // excluded edges get a fresh error at the new pose (:364)
+                bad[e] = s.chi2[e] > (double)(s.stereo(e) ? Chi3D : Chi2D);
                 s.active[e] = !bad[e];
                 if (it >= 2) s.robust[e] = 0;
                 if (!bad[e]) nGood++;
@@ -229,4 +261,38 @@ extern "C" int oracle_pnp_solve(const float* pose_f2g, const float* intr4, int n
     for (int e = 0; e < n; e++) { bad_out[e] = bad[e]; good += !bad[e]; }
     if (state_out) { std::memcpy(state_out, s.T.q, 32); std::memcpy(state_out + 4, s.T.t, 24); }
     return good;
+}
+
+extern "C" int oracle_pnp_solve(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
+                                const float* weight, float* pose_out, uint8_t* bad_out, int32_t* iters_out /*4*/, double* state_out /*7*/) {
+    PnP s;
+    s.n = n; s.p3d = p3d; s.kp = kp; s.invsig = invsigma; s.weight = weight;
+    s.fx = intr4[0]; s.fy = intr4[1]; s.cx = intr4[2]; s.cy = intr4[3];
+    s.delta = (double)(float)std::sqrt(5.99);   // const float thHuber2D = sqrt(5.99)
+    return pnp_run(s, pose_f2g, n, pose_out, bad_out, iters_out, state_out);
+}
+
+// depth: n floats (Frame::getDepth(queryIdx); <= 0 = monocular edge) or NULL (= oracle_pnp_solve); bl = imageParams.bl
+extern "C" int oracle_pnp_solve_stereo(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
+                                       const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out,
+                                       int32_t* iters_out /*4*/, double* state_out /*7*/) {
+    PnP s;
+    s.n = n; s.p3d = p3d; s.kp = kp; s.invsig = invsigma; s.weight = weight;
+    s.fx = intr4[0]; s.fy = intr4[1]; s.cx = intr4[2]; s.cy = intr4[3];
+    s.delta = (double)(float)std::sqrt(5.99);    // thHuber2D
+    s.delta3 = (double)(float)std::sqrt(7.815);  // thHuber3D
+    if (depth) {
+        const float mbf = bl * intr4[0];
+        s.bf = mbf;
+        s.st.assign(n, 0); s.ur.assign(n, 0.f); s.w3.assign(n, 0.f);
+        for (int e = 0; e < n; e++) {
+            if (!(depth[e] > 0)) continue;        // pnpsolver.cpp:205: depth <= 0 -> monocular edge
+            s.st[e] = 1;
+            s.ur[e] = kp[2 * e] - mbf / depth[e];  // kp_ur (float)
+            float w = weight[e];
+            w *= 2;                               // the stereo edge's robust weight is doubled
+            s.w3[e] = w;
+        }
+    }
+    return pnp_run(s, pose_f2g, n, pose_out, bad_out, iters_out, state_out);
 }

@@ -426,6 +426,15 @@ int oracle_proj_match_prev(const oracle_keypoint* und_kpts, int n_kpts, const ui
     return (int)matches.size();
 }
 
+// filter_ambiguous_query_ on a DMatch list in place (n x 4 words); returns the new length (oracle/track_oracle.cpp's union)
+int oracle_filter_ambiguous_query(int32_t* matches, int n) {
+    std::vector<DMatch> v(n);
+    for (int i = 0; i < n; i++) std::memcpy(&v[i], matches + 4 * i, 16);
+    filter_ambiguous_query_(v);
+    for (size_t i = 0; i < v.size(); i++) std::memcpy(matches + 4 * i, &v[i], 16);
+    return (int)v.size();
+}
+
 // libstdc++'s own std::sort on an index array ordered by the keys — the algorithm picoflann's fallback calls (picoflann.h:438-441).
 // tests/test_kdbuild.py holds the product's restatement of its data movement (csrc/kdbuild.hpp) against this.
 void oracle_std_sort_perm(const float* keys, int n, uint32_t* perm) {

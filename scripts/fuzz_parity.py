@@ -277,12 +277,25 @@ def track_case(seed):
     pid = {int(v): i for i, v in enumerate(prev["ids"])}
     it1 = np.array([pid[int(t)] for t in m1["trainIdx"]], np.int64)
     q1 = m1["queryIdx"]
-    s1 = _trk_pnp.solvePnp(pose, intr, prev["pos3d"][it1].reshape(-1, 3), np.stack([ukp["x"][q1], ukp["y"][q1]], 1).reshape(-1, 2), inv_sf[ukp["octave"][q1]], np.ones(len(m1), np.float32))
-    tracked = s1["ngood"] >= mi
+    rows1 = prev_row[it1] if len(it1) else np.zeros(0, np.int32)
+    if len(m1) > mi:   # system.cpp:6595: the first solve only with more than min_inliers matches (weights: map_weight of an in-map item, else 1)
+        s1 = _trk_pnp.solvePnp(pose, intr, prev["pos3d"][it1].reshape(-1, 3), np.stack([ukp["x"][q1], ukp["y"][q1]], 1).reshape(-1, 2), inv_sf[ukp["octave"][q1]],
+                               np.where(rows1 >= 0, weight[np.maximum(rows1, 0)], np.float32(1)).astype(np.float32))
+    else:
+        s1 = dict(ngood=0, pose=pose, bad=np.zeros(len(m1), np.uint8), iters=np.zeros(4, np.int32))
+    tracked = s1["ngood"] > mi
     pose_map = s1["pose"] if tracked else pose
     b = pm.matchFrameToMapPoints(pose_map, mp["ids"], mp["pos3d"], mp["normal"], mp["min_dist"], mp["max_dist"], mp["desc"], d2, rt if tracked else rl)
     m2 = b["matches"]
-    un = np.ascontiguousarray(np.concatenate([m1[s1["bad"][: len(m1)] == 0] if tracked else m1[:0], m2]).astype(_DM))
+    seen = rows1[rows1 >= 0] if tracked else []
+    if len(seen):   # map.cpp:657-668: the points the first search matched are not searched again (their hits go before the filter)
+        keep = b["best_kp"] >= 0
+        keep[seen] = False
+        m2 = np.zeros(int(keep.sum()), _DM)
+        m2["queryIdx"], m2["trainIdx"], m2["imgIdx"], m2["distance"] = b["best_kp"][keep], mp["ids"][keep].astype(np.int32), -1, b["best_dist"][keep]
+        if len(m2):
+            m2 = m2[: lib().uh_filter_ambiguous(np_ptr(m2), len(m2), 0)]
+    un = np.ascontiguousarray(np.concatenate([m1 if tracked else m1[:0], m2]).astype(_DM))
     if len(un):
         un = un[: lib().uh_filter_ambiguous(np_ptr(un), len(un), 0)]
     mrow = {int(v): i for i, v in enumerate(mp["ids"])}
@@ -303,6 +316,62 @@ def track_case(seed):
     return ok, None if ok else (nk, npt, n_prev, le, mi, len(m1), len(m2), len(un))
 
 run("track_pose", track_case)
+
+
+# ---- the same one call against the CPU oracle of system.cpp's control flow (oracle/track_oracle.cpp), on maps held by id
+def track_oracle_case(seed):
+    r = np.random.default_rng(seed)
+    nk, npt = int(r.integers(12, 4000)), int(r.integers(40, 5000))
+    le = bool(r.random() < 0.2)
+    fr, mp, pose = synth.proj_problem(nk, npt, seed % 100000, low_entropy=le, n_levels=int(r.integers(2, 9)), pose_noise=float(r.choice([0.0, 0.002, 0.02, 0.5])))
+    dfr = _trk_frames[int(r.integers(0, 2))]
+    dfr.upload(fr["und_kpts"], fr["desc"])
+    pm.setFrameDev(dfr, fr["scale_factors"], fr["fx"], fr["fy"], fr["cx"], fr["cy"], fr["min_xy"], fr["max_xy"], und_kpts=fr["und_kpts"])
+    # the table: the local map plus copies of some of its points under ids outside it; previous-frame items name ids of the table
+    n_loc = int(r.integers(0, npt + 1))
+    n_out = int(r.integers(0, min(npt, 800) + 1))
+    orow = r.choice(npt, n_out, replace=False) if n_out else np.zeros(0, np.int64)
+    tab = {k: np.ascontiguousarray(np.concatenate([mp[k], mp[k][orow]])) for k in ("pos3d", "normal", "min_dist", "max_dist", "desc", "octave")}
+    tab["ids"] = np.concatenate([mp["ids"], 10 ** 6 + np.arange(n_out)]).astype(np.uint32)
+    tab["stable"] = (r.random(len(tab["ids"])) >= 0.25).astype(np.uint8)
+    local = np.sort(r.choice(npt, n_loc, replace=False)) if n_loc else np.zeros(0, np.int64)
+    n_prev = int(r.integers(0, min(len(tab["ids"]), 1500) + 1))
+    prow = np.sort(r.choice(len(tab["ids"]), n_prev, replace=False)) if n_prev else np.zeros(0, np.int64)
+    prev = dict(ids=tab["ids"][prow], octave=tab["octave"][prow].astype(np.int32), desc=np.ascontiguousarray(tab["desc"][prow]))
+    lrow = {int(t): i for i, t in enumerate(local)}
+    prev_row = np.array([lrow.get(int(t), -1) for t in prow], np.int32)
+    w = np.where(tab["stable"] != 0, np.float32(1), np.float32(0.5)).astype(np.float32)
+    mpl = {k: np.ascontiguousarray(tab[k][local]) for k in ("ids", "pos3d", "normal", "min_dist", "max_dist", "desc")}
+    intr = np.array([fr["fx"], fr["fy"], fr["cx"], fr["cy"]], np.float32)
+    inv_sf = (np.float32(1) / fr["scale_factors"]).astype(np.float32)
+    d1, r1 = (float(r.choice([3.0, 8.0])) if le else float(r.choice([100.0, 75.0]))), float(r.choice([7.5, 15.0, 40.0]))
+    d2, rt, rl = (8.0 if le else float(r.choice([100.0, 50.0]))), float(r.choice([4.0, 2.5])), float(r.choice([15.0, 40.0]))
+    mi = int(r.choice([30, 30, 5, 100000]))
+    depth = None
+    if r.random() < 0.5:
+        depth = np.where(r.random(nk) < 0.6, r.uniform(1, 60, nk), 0.0).astype(np.float32)
+    kw = dict(prev_min_desc_dist=d1, prev_max_repj_dist=r1, map_min_desc_dist=d2, map_radius_tracked=rt, map_radius_lost=rl, min_inliers=mi)
+    p = dict(ids=prev["ids"], pos3d=np.ascontiguousarray(tab["pos3d"][prow].reshape(-1, 3)), octave=prev["octave"], desc=prev["desc"])
+    f = pm.trackPoseStereo(_trk_pnp, pose, intr, inv_sf, p, mpl, depth=depth, bl=0.54, prev_weight=w[prow], prev_map_row=prev_row, map_weight=w[local], **kw)
+    args = (L, fr, tab, prev, tab["ids"][local], pose)
+    o = oracle_lib.track_pose(*args, depth=depth, bl=0.54, **kw)
+    # (a solve over fewer than 8 matches is a rank-deficient 6-DOF problem: the solver's parity is stated from 8 matches on, pnp_case —
+    # below that its result is not compared, and a first solve that small decides nothing comparable after it)
+    n1 = len(o["matches_prev"])
+    ok = f["matches_prev"].tobytes() == o["matches_prev"].tobytes()
+    if ok and mi < n1 < 8:
+        return True, None
+    ok = ok and ((f["bad_prev"] == o["bad_prev"]).all() and (f["iters1"] == o["iters1"]).all() and f["inliers1"] == o["inliers1"]
+                 and np.abs(f["pose1"] - o["pose1"]).max() < 1e-5 and f["tracked"] == o["tracked"])
+    if ok:   # from the map search on: at the fused call's own float pose (one ulp must not move a candidate across a radius)
+        o2 = oracle_lib.track_pose(*args, depth=depth, bl=0.54, pose_for_map=f["pose1"], **kw)
+        ok = f["matches_map"].tobytes() == o2["matches_map"].tobytes() and f["matches_all"].tobytes() == o2["matches_all"].tobytes()
+        if ok and not 0 < len(o2["matches_all"]) < 8:
+            ok = ((f["bad_all"] == o2["bad_all"]).all() and (f["iters2"] == o2["iters2"]).all() and f["inliers2"] == o2["inliers2"]
+                  and np.abs(f["pose2"] - o2["pose2"]).max() < 1e-5)
+    return ok, None if ok else (nk, npt, n_prev, n_loc, le, mi, depth is not None, len(o["matches_prev"]), o["tracked"], len(f["matches_all"]), len(o["matches_all"]))
+
+run("track_oracle", track_oracle_case)
 
 # ---- BA and PnP (tolerance 1e-6 on the se3 state, identical iteration counts / flags)
 from ucoslam_cv3_amd.ba import GlobalOptimizer, ParamSet

@@ -307,6 +307,69 @@ def proj_match_prev(L, fr, mp, pose, minDescDist, maxRepjDist):
     return dict(best_kp=best_kp, best_dist=best_d, matches=dm)
 
 
+def pnp_solve_stereo(L, pr, depth, bl):
+    """oracle_pnp_solve_stereo: pnp_solve with per-match depth (<= 0 = monocular edge; None = pnp_solve) and baseline bl."""
+    import numpy as np
+
+    n = pr["n"]
+    out = dict(pose=np.zeros(16, np.float32), bad=np.zeros(max(n, 1), np.uint8), iters=np.zeros(4, np.int32), state=np.zeros(7, np.float64))
+    f = L.oracle_pnp_solve_stereo
+    f.restype = I
+    f.argtypes = [VP, VP, I, VP, VP, VP, VP, VP, C.c_float, VP, VP, VP, VP]
+    dep = None if depth is None else np.ascontiguousarray(depth, np.float32)
+    out["ngood"] = f(P(pr["pose"]), P(pr["intr"]), n, P(pr["p3d"]), P(pr["kp"]), P(pr["invsig"]), P(pr["weight"]), None if dep is None else P(dep), float(bl),
+                     P(out["pose"]), P(out["bad"]), P(out["iters"]), P(out["state"]))
+    out["bad"] = out["bad"][:n]
+    return out
+
+
+def track_pose(L, fr, table, prev, local_ids, pose0, depth=None, bl=0.0, pose_for_map=None, prev_min_desc_dist=75.0, prev_max_repj_dist=15.0,
+               map_min_desc_dist=100.0, map_radius_tracked=4.0, map_radius_lost=15.0, min_inliers=30):
+    """oracle_track_pose (oracle/track_oracle.cpp): the tracker's control flow of one frame on a map held as the reference holds it.
+    fr: the frame dict of synth.proj_problem (und_kpts, desc, scale_factors, fx, fy, cx, cy, min_xy, max_xy); table: the map points by id,
+    dict(ids, pos3d, normal, min_dist, max_dist, desc, stable); prev: the previous frame's items, dict(ids, octave, desc) (ids name table
+    entries); local_ids: the local map's ids.  Returns the dict keys of ProjectionMatcher.trackPose."""
+    import numpy as np
+
+    DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
+    f = L.oracle_track_pose
+    f.restype = I
+    f.argtypes = [VP, I, VP, VP, I, VP, VP, VP, C.c_float] + [I] + [VP] * 7 + [I, VP, VP, VP] + [I, VP] + [VP, VP, VP, I] + [VP] * 8
+    kp = np.ascontiguousarray(fr["und_kpts"])
+    nk = len(kp)
+    fdesc = np.ascontiguousarray(fr["desc"], np.uint8).reshape(nk, 32) if nk else np.zeros((1, 32), np.uint8)
+    sf = np.ascontiguousarray(fr["scale_factors"], np.float32)
+    intr = np.array([fr["fx"], fr["fy"], fr["cx"], fr["cy"]], np.float32)
+    mm = np.array([fr["min_xy"][0], fr["min_xy"][1], fr["max_xy"][0], fr["max_xy"][1]], np.int32)
+    dep = None if depth is None else np.ascontiguousarray(depth, np.float32)
+    nt = len(table["ids"])
+    t = [np.ascontiguousarray(table["ids"], np.uint32), np.ascontiguousarray(table["pos3d"], np.float32), np.ascontiguousarray(table["normal"], np.float32),
+         np.ascontiguousarray(table["min_dist"], np.float32), np.ascontiguousarray(table["max_dist"], np.float32), np.ascontiguousarray(table["desc"], np.uint8),
+         np.ascontiguousarray(table["stable"], np.uint8)]
+    t = [a if len(a) else np.zeros(1, a.dtype) for a in t]
+    npv = len(prev["ids"])
+    pv = [np.ascontiguousarray(prev["ids"], np.uint32), np.ascontiguousarray(prev["octave"], np.int32), np.ascontiguousarray(prev["desc"], np.uint8)]
+    pv = [a if len(a) else np.zeros(1, a.dtype) for a in pv]
+    loc = np.ascontiguousarray(local_ids, np.uint32)
+    nl = len(loc)
+    loc = loc if nl else np.zeros(1, np.uint32)
+    p0 = np.ascontiguousarray(pose0, np.float32).reshape(16)
+    pfm = None if pose_for_map is None else np.ascontiguousarray(pose_for_map, np.float32).reshape(16)
+    par = np.array([prev_min_desc_dist, prev_max_repj_dist, map_min_desc_dist, map_radius_tracked, map_radius_lost], np.float32)
+    cnt = np.zeros(16, np.int32)
+    pose1, pose2 = np.zeros(16, np.float32), np.zeros(16, np.float32)
+    m1 = np.zeros(max(npv, 1), DMATCH_DTYPE); b1 = np.zeros(max(npv, 1), np.uint8)
+    m2 = np.zeros(max(nl, 1), DMATCH_DTYPE)
+    ma = np.zeros(max(npv + nl, 1), DMATCH_DTYPE); ba = np.zeros(max(npv + nl, 1), np.uint8)
+    rc = f(P(kp) if nk else None, nk, P(fdesc), P(sf), len(sf), P(intr), P(mm), None if dep is None else P(dep), float(bl),
+           nt, *[P(a) for a in t], npv, *[P(a) for a in pv], nl, P(loc), P(p0), None if pfm is None else P(pfm), P(par), int(min_inliers),
+           P(cnt), P(pose1), P(pose2), P(m1), P(b1), P(m2), P(ma), P(ba))
+    assert rc == 0, rc
+    n1, n2, na = int(cnt[0]), int(cnt[1]), int(cnt[2])
+    return dict(matches_prev=m1[:n1].copy(), bad_prev=b1[:n1].copy(), matches_map=m2[:n2].copy(), matches_all=ma[:na].copy(), bad_all=ba[:na].copy(),
+                tracked=bool(cnt[3]), inliers1=int(cnt[4]), inliers2=int(cnt[9]), iters1=cnt[5:9].copy(), iters2=cnt[10:14].copy(), pose1=pose1, pose2=pose2)
+
+
 # ------------------------------------------------------------------------------------------------ hierarchical k-means (a14)
 def hkmeans_blob(L, train, k=32, max_iters=0):
     import numpy as np

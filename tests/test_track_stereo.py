@@ -4,7 +4,7 @@ look-ups -> uh_pnp_solve_stereo), bit for bit, with both kd-tree builders."""
 import numpy as np
 import pytest
 
-from test_track import _same, _scene
+from test_track import _first_solve, _map_matches, _same, _scene
 
 BL = 0.54
 
@@ -29,7 +29,7 @@ def _depths(sc, seed, n_map=3000):
 def _sequence_stereo(sc, pnp, depth, prev_weight, min_inliers=30, d1=75.0, r1=15.0, d2=100.0, rt=4.0, rl=15.0):
     """The operators one after the other, with the host's list handling and look-ups in between (the stereo form of
     tests/test_track.py::_sequence): depth[queryIdx] per match in both solves; a previous-frame item's weight is map_weight[row] for
-    row >= 0, else prev_weight[i] (or 1 without prev_weight, and then 1 for every item of the first solve)."""
+    row >= 0, else prev_weight[i] (or 1 without prev_weight), in both solves."""
     from ucoslam_cv3_amd._lib import lib, np_ptr
     from ucoslam_cv3_amd.projmatch import DMATCH_DTYPE
 
@@ -40,17 +40,14 @@ def _sequence_stereo(sc, pnp, depth, prev_weight, min_inliers=30, d1=75.0, r1=15
     pid_to_i = {int(v): i for i, v in enumerate(prev["ids"])}
     it1 = np.array([pid_to_i[int(t)] for t in m1["trainIdx"]], np.int64)
     q1 = m1["queryIdx"]
-    if prev_weight is None:
-        w1 = np.ones(len(m1), np.float32)
-    else:
-        w1 = np.array([sc["weight"][row_of[i]] if row_of[i] >= 0 else prev_weight[i] for i in it1], np.float32)
-    s1 = pnp.solvePnp(sc["pose0"], sc["intr"], prev["pos3d"][it1].reshape(-1, 3), np.stack([ukp["x"][q1], ukp["y"][q1]], 1).reshape(-1, 2),
-                      sc["inv_sf"][ukp["octave"][q1]], w1, depth=depth[q1], bl=BL)
-    tracked = s1["ngood"] >= min_inliers
+    w1 = np.array([sc["weight"][row_of[i]] if row_of[i] >= 0 else (1.0 if prev_weight is None else prev_weight[i]) for i in it1], np.float32)
+    s1 = _first_solve(pnp, sc, m1, prev["pos3d"][it1].reshape(-1, 3), w1, min_inliers, depth=depth[q1], bl=BL)
+    tracked = s1["ngood"] > min_inliers
     pose_map = s1["pose"] if tracked else sc["pose0"]
     b = pm.matchFrameToMapPoints(pose_map, mp["ids"], mp["pos3d"], mp["normal"], mp["min_dist"], mp["max_dist"], mp["desc"], d2, rt if tracked else rl)
-    m2 = b["matches"]
-    union = np.concatenate([m1[s1["bad"][: len(m1)] == 0] if tracked else m1[:0], m2]).astype(DMATCH_DTYPE)
+    rows1 = row_of[it1] if len(it1) else np.zeros(0, np.int32)
+    m2 = _map_matches(b, mp["ids"], rows1[rows1 >= 0] if tracked else [])
+    union = np.concatenate([m1 if tracked else m1[:0], m2]).astype(DMATCH_DTYPE)
     if len(union):
         union = np.ascontiguousarray(union)
         k = lib().uh_filter_ambiguous(np_ptr(union), len(union), 0)
@@ -85,7 +82,7 @@ def _fused(sc, pnp, **kw):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("host_tree", [False, True], ids=["device_tree", "host_tree"])
-def test_track_pose_stereo_equals_the_operators(hip_ctx, host_tree):
+def test_track_pose_stereo_equals_the_operators_in_reference_order(hip_ctx, host_tree):
     from ucoslam_cv3_amd.pnp import PnPSolver
 
     pnp = PnPSolver(hip_ctx)
@@ -115,7 +112,7 @@ def test_track_pose_stereo_without_depth_equals_track_pose(hip_ctx):
 
 
 @pytest.mark.gpu
-def test_track_pose_stereo_prev_weight_reaches_the_solves(hip_ctx):
+def test_track_pose_stereo_prev_weight_reaches_both_solves(hip_ctx):
     """A previous-frame item outside the local map weighs prev_weight[i] (not 1) in the solves, exactly as the operator sequence with the
     reference's per-edge weights.  (The robust weight scales the chi2 sums only, not the normal equations: it changes Levenberg's damping
     and stopping decisions, so some scene / weight pairs move the result and others leave it bit-identical — at least one must move.)"""

@@ -53,9 +53,10 @@ struct PnpArgs {
     float bl;                // imageParams.bl (stereo baseline)
 };
 
-// one thread: the decision of system.cpp:6762-6881 from this solve's inlier count; M = the pose it returns (16 floats)
+// one thread: the decision of system.cpp:6646 / :6813 from this solve's inlier count (tracked iff MORE than min_inliers); M = the pose it
+// returns (16 floats)
 __device__ void pnp_decide(const PnpArgs& A, int inliers, const float* M) {
-    const int tracked = inliers >= A.dec.min_inliers ? 1 : 0;
+    const int tracked = inliers > A.dec.min_inliers ? 1 : 0;
     const float* T = tracked ? M : A.pose_in;
     float* d = A.dec.dyn17;
     for (int i = 0; i < 12; i++) d[i] = T[i];
@@ -248,9 +249,13 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     if (A.n_dev) {   // (uh_track_pose: the matches were chosen on the device)
         const int nd = __builtin_amdgcn_readfirstlane(*A.n_dev);
         n = nd < n ? nd : n;
-        if (n <= 0) {   // pnpsolver.cpp:149-150: without matches the pose comes back as it went in
+        // pnpsolver.cpp:149-150: without matches the pose comes back as it went in.  The tracker's first solve (dec.dyn17) runs only with
+        // MORE than min_inliers matches (system.cpp:6595); otherwise the reference tries its FrameMatcher fallback, which is the caller's:
+        // taken to find nothing, nInliers = 0 and no solve is reported (pose in, no iterations, no outlier flags)
+        if (n <= 0 || (A.dec.dyn17 && n <= A.dec.min_inliers)) {
             if (tid < 16) A.pose_out[tid] = A.pose_in[tid];
             if (tid < 5) A.result[tid] = 0;
+            for (int e = tid; e < n; e += kPnpThreads) A.bad_out[e] = 0;
             if (A.dec.dyn17 && tid == 0) pnp_decide(A, 0, A.pose_in);
             return;
         }

@@ -1,23 +1,26 @@
 // uh_track_pose: the tracker's pose estimation for one frame as ONE host call — what System does between FrameExtractor::process and the
-// keyframe decision (src/utils/system.cpp, line numbers = statement starts after preprocessing):
-//   :5930-6460 / :6559-6565   projection search against the previous frame            (uh_projmatch_match_prev)
-//   :6566-                    PnPSolver::solvePnp over those matches                   (uh_pnp_solve; pnpsolver.cpp:116-409, look-ups :199-232)
-//   :6762-6881                >= 30 inliers: keep the refined pose, search the local map in a 4 px disc; else predicted pose, projDistThr
-//                             Map::matchFrameToMapPoints                               (uh_projmatch_match)
-//   :6897-6954                inliers of the first set + the new matches, filter_ambiguous_query over the union, per-match look-ups
-//                             PnPSolver::solvePnp                                      (uh_pnp_solve)
+// keyframe decision (src/utils/system.cpp, raw line numbers of the statement starts, read after preprocessing):
+//   :6559-6565   projection search against the previous frame                                 (uh_projmatch_match_prev)
+//   :6595-6646   with MORE than min_inliers matches: PnPSolver::solvePnp over them            (uh_pnp_solve; pnpsolver.cpp:116-409, look-ups :199-232)
+//                (fewer: the reference's FrameMatcher fallback :6664-6780 is the caller's; here it finds nothing, nInliers = 0)
+//   :6813-6877   MORE than min_inliers inliers: keep the refined pose and EVERY first match, mark their points seen (:6842), search the
+//                local map in a 4 px disc; else predicted pose, projDistThr, no first matches
+//   :6897        Map::matchFrameToMapPoints without the points seen this frame (map.cpp:657-668)   (uh_projmatch_match)
+//   :6913-6954   the first matches + the new ones, filter_ambiguous_query over the union, per-match look-ups, PnPSolver::solvePnp (uh_pnp_solve)
 // Called one after the other through the C ABI the four operators cost four host round trips (launch latency + completion word + unpacking +
 // the host's look-ups in between: ~55 of the frame's ~430 us were no kernel's).  Here the host stages both candidate sets, enqueues
 // SIX launches on the context stream and waits once; what the host did between the calls runs on the device:
 //   projmatch_kernel<prev>  ->  track_select_kernel (matches in item order, filter_ambiguous_query, look-ups for the solve)
 //   -> pnp_solve_kernel (match count from device memory; its last thread also takes the decision: pose / radius of the map search)
-//   -> projmatch_kernel<map> (pose and radius read from device memory)  ->  track_select_kernel (its own filter, the union with the
-//   first solve's inliers, filter, look-ups)  ->  pnp_solve_kernel  ->  track_publish_kernel (everything the sequence of calls returns).
+//   -> projmatch_kernel<map> (pose and radius read from device memory)  ->  track_select_kernel (the seen points' hits dropped, its own
+//   filter, the union with every first match when tracked, filter, look-ups)  ->  pnp_solve_kernel  ->  track_publish_kernel (everything the
+//   sequence of calls returns).
 // The look-ups gather from HBM only: the searches leave every candidate's position and its {id, map row, weight} record there again
 // (PmPoints::pos_out / aux_out: one more 16-byte read per candidate inside launches that wait on such reads anyway; gathering from pinned
 // memory in the select launches was one host-link request per match — 31 us for the second one — and staging the tables there 5 us).
-// Same results as the four calls, bit for bit (tests/test_track.py, tests/test_cpp_host.py): the same kernels do the searching and
-// the solving; the list logic is integer work (stable minimum per keypoint = uh_filter_ambiguous, matcher.hip keep_best_per_key).
+// Same results as the four calls, bit for bit (tests/test_track.py, tests/test_cpp_host.py), and as the CPU oracle of system.cpp's control
+// flow (oracle/track_oracle.cpp, tests/test_track_oracle_gpu.py): the same kernels do the searching and the solving; the list logic is
+// integer work (stable minimum per keypoint = uh_filter_ambiguous, matcher.hip keep_best_per_key).
 // This file is included at the end of projmatch.hip (it uses that unit's internals).
 #pragma once
 
@@ -39,8 +42,11 @@ enum : int { kTrkN1 = 0, kTrkN2 = 1, kTrkNA = 2, kTrkTracked = 3, kTrkRes1 = 4 /
 struct TrkSelect {
     // the search whose results become a list (candidate order)
     int nB; const int* bk; const float* bd; const uint4* aux; int map_kind;   // aux: {id, map row, weight} per candidate (HBM, left by the search)
-    // second form only: the list carried over from the first solve (its inliers enter the union when the frame counts as tracked)
-    const uh_dmatch* carry; const int* carry_src; const unsigned char* carry_bad; int carry_cap;
+    // second form only: the list carried over from the first search (all of it enters the union when the frame counts as tracked)
+    const uh_dmatch* carry; const int* carry_src; int carry_cap;
+    // one byte per map row: 1 = the point was matched by the first search of a tracked frame (lastFIdxSeen, system.cpp:6842); the first
+    // form clears it, the second sets it from the carried list and drops those rows' hits before its filter (map.cpp:657-668)
+    unsigned char* seen; int n_map_rows;
     int* hdr;                       // counts in / out (see the enum)
     int fresh_n_slot, final_n_slot; // hdr slots of the fresh list's and the final list's length (equal in the first form)
     uh_dmatch* fresh_out; int* fresh_src;   // the search's own matches (after filter_ambiguous_query)
@@ -55,8 +61,8 @@ struct TrkSelect {
     TrkElem* scratch_a; TrkElem* scratch_b;
     long long* clk;   // UH_TRK_CLK: 8 wall-clock stamps (10 ns) of thread 0
     // uh_track_pose_stereo: the frame's per-keypoint depth (dep_src: pinned, copied once into dep_kp in HBM by the first launch; NULL in the
-    // second) and the per-match depth of the solve (dep); aux_weight: a previous-frame candidate's weight is its aux record's too
-    const float* dep_src; float* dep_kp; float* dep; int aux_weight;
+    // second) and the per-match depth of the solve (dep)
+    const float* dep_src; float* dep_kp; float* dep;
 };
 
 // Exclusive prefix over the workgroup's per-thread counts; returns the thread's offset and (total) the sum.  Two barriers.
@@ -121,8 +127,19 @@ __global__ __launch_bounds__(kTrkThreads) void track_select_kernel(TrkSelect a, 
     UH_TRK_STAMP(0);
     if (a.dep_src)   // (read by this launch's look-ups after the barriers below, and by the second select launch)
         for (int k = tid; k < a.n_kpts; k += kTrkThreads) a.dep_kp[k] = a.dep_src[k];
+    if (!a.carry)     // (first form: the seen marks of the previous call go; the second launch reads them only after this one ended)
+        for (int k = tid; k < a.n_map_rows; k += kTrkThreads) a.seen[k] = 0;
+    const int tracked = a.carry ? a.hdr[kTrkTracked] : 0;
+    const int nc = tracked ? min(a.hdr[kTrkN1], a.carry_cap) : 0;
+    if (a.carry) {    // ---- tracked: every point of the first search is seen this frame (system.cpp:6842)
+        for (int p = tid; p < nc; p += kTrkThreads) {
+            const int row = (int)a.aux_prev[a.carry_src[p] & 0x3fffffff].y;
+            if (row >= 0 && row < a.n_map_rows) a.seen[row] = 1;
+        }
+        __syncthreads();
+    }
     UH_TRK_STAMP(1);
-    // ---- the search's hits in candidate order
+    // ---- the search's hits in candidate order (second form: without the seen points, whose search map.cpp:657-668 skips)
     int nF = 0;
     for (int p0 = 0; p0 < a.nB; p0 += kTrkThreads * kTrkItems) {
         int kpi[kTrkItems], cnt = 0;
@@ -132,7 +149,7 @@ __global__ __launch_bounds__(kTrkThreads) void track_select_kernel(TrkSelect a, 
         for (int u = 0; u < kTrkItems; u++) {
             const int i = p0 + tid * kTrkItems + u;
             kpi[u] = -1; id[u] = 0; dist[u] = 0.f;
-            if (i < a.nB) { kpi[u] = a.bk[i]; id[u] = a.aux[i].x; dist[u] = a.bd[i]; }
+            if (i < a.nB && !(a.carry && a.seen[i])) { kpi[u] = a.bk[i]; id[u] = a.aux[i].x; dist[u] = a.bd[i]; }
             cnt += kpi[u] >= 0 ? 1 : 0;
         }
         int tot;
@@ -155,25 +172,12 @@ __global__ __launch_bounds__(kTrkThreads) void track_select_kernel(TrkSelect a, 
     int n_fin = n_fresh;
     UH_TRK_STAMP(4);
     if (a.carry) {
-        // ---- the union: inliers of the first solve (when the frame counts as tracked), then the new matches; filter again
-        const int tracked = a.hdr[kTrkTracked];
-        const int nc = tracked ? min(a.hdr[kTrkN1], a.carry_cap) : 0;
-        int nU = 0;
-        for (int p0 = 0; p0 < nc; p0 += kTrkThreads * kTrkItems) {
-            int flag[kTrkItems], cnt = 0;
-#pragma unroll
-            for (int u = 0; u < kTrkItems; u++) { const int p = p0 + tid * kTrkItems + u; flag[u] = p < nc && !a.carry_bad[p] ? 1 : 0; cnt += flag[u]; }
-            int tot;
-            int o = nU + trk_block_offset(cnt, s_wave, tot);
-#pragma unroll
-            for (int u = 0; u < kTrkItems; u++)
-                if (flag[u]) { const int p = p0 + tid * kTrkItems + u; const uh_dmatch m = a.carry[p]; LA[o++] = TrkElem{m.queryIdx, (unsigned)m.trainIdx, m.distance, a.carry_src[p]}; }
-            nU += tot;
-        }
+        // ---- the union (system.cpp:6913): every match of the first search when the frame counts as tracked (the first solve only flagged
+        // its outliers, pnpsolver.cpp:385-400), then the new matches; filter again
+        for (int p = tid; p < nc; p += kTrkThreads) { const uh_dmatch m = a.carry[p]; LA[p] = TrkElem{m.queryIdx, (unsigned)m.trainIdx, m.distance, a.carry_src[p]}; }
+        for (int p = tid; p < n_fresh; p += kTrkThreads) LA[nc + p] = LB[p];
         __syncthreads();
-        for (int p = tid; p < n_fresh; p += kTrkThreads) LA[nU + p] = LB[p];
-        __syncthreads();
-        nU += n_fresh;
+        const int nU = nc + n_fresh;
         // (LB is free again: its content lives in LA now)
         n_fin = trk_filter(LA, nU, LB, s_best, a.n_kpts, s_wave);
         for (int p = tid; p < n_fin; p += kTrkThreads) { const TrkElem e = LB[p]; a.final_out[p] = uh_dmatch{e.query, (int)e.id, -1, e.dist}; }
@@ -184,10 +188,10 @@ __global__ __launch_bounds__(kTrkThreads) void track_select_kernel(TrkSelect a, 
         const TrkElem e = fin[p];
         const int is_map = (e.src >> 30) & 1, idx = e.src & 0x3fffffff;
         const uint4 ax = is_map ? a.aux_map[idx] : a.aux_prev[idx];
-        const int row = a.prefer_map_row ? (int)ax.y : -1;   // (first solve: the candidate's own position, weight 1)
+        const int row = a.prefer_map_row ? (int)ax.y : -1;   // (first solve: the candidate's own position)
         const float4 pos = row >= 0 ? a.pos_map[row] : a.pos_prev[idx];
         a.p3d[3 * p] = pos.x; a.p3d[3 * p + 1] = pos.y; a.p3d[3 * p + 2] = pos.z;
-        a.wgt[p] = (row >= 0 || a.aux_weight) ? __uint_as_float(ax.z) : 1.f;
+        a.wgt[p] = __uint_as_float(ax.z);   // (both solves: map_weight of the point's row, else prev_weight[i] or 1 — match_enqueue's record)
         if (a.dep) a.dep[p] = a.dep_kp[e.query];
         const float4 k = a.kp_xyo[e.query];
         a.kp[2 * p] = k.x; a.kp[2 * p + 1] = k.y;
@@ -290,6 +294,7 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     const size_t o_posp = o; o = al(o + 16 * (size_t)cap1); const size_t o_posm = o; o = al(o + 16 * (size_t)cap2);
     const size_t o_auxp = o; o = al(o + 16 * (size_t)cap1); const size_t o_auxm = o; o = al(o + 16 * (size_t)cap2);
     const size_t o_depk = o; o = al(o + (stereo ? 4 * (size_t)std::max(nk, 1) : 0)); const size_t o_dep = o; o = al(o + (stereo ? 4 * (size_t)capa : 0));
+    const size_t o_seen = o; o = al(o + (size_t)cap2);
     if ((rc = T.d.reserve(o))) return rc;
     char* D = T.d.as<char>();
     // ---- pinned parameter block (read by the launches in place)
@@ -337,7 +342,7 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     s1.clk = trk_clk ? T.d_clk.as<long long>() : nullptr;
     s1.dep_src = stereo ? reinterpret_cast<const float*>(dp + q_dep) : nullptr; s1.dep_kp = stereo ? reinterpret_cast<float*>(D + o_depk) : nullptr;
     s1.dep = stereo ? reinterpret_cast<float*>(D + o_dep) : nullptr;
-    s1.aux_weight = sx && sx->prev_weight ? 1 : 0;
+    s1.seen = reinterpret_cast<unsigned char*>(D + o_seen); s1.n_map_rows = nm;
     const float bl = stereo ? sx->bl : 0.f;
     // the select launches' working lists: in LDS while two lists of capa elements fit beside the per-keypoint table
     const size_t sel_lds = 2 * sizeof(TrkElem) * (size_t)capa;
@@ -361,7 +366,7 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     }
     TrkSelect s2 = s1;
     s2.nB = nm; s2.bk = pd2.d_best_kp; s2.bd = pd2.d_best_dist; s2.aux = reinterpret_cast<const uint4*>(D + o_auxm); s2.map_kind = 1;
-    s2.carry = reinterpret_cast<const uh_dmatch*>(D + o_m1); s2.carry_src = reinterpret_cast<const int*>(D + o_src1); s2.carry_bad = reinterpret_cast<const unsigned char*>(D + o_bad1); s2.carry_cap = cap1;
+    s2.carry = reinterpret_cast<const uh_dmatch*>(D + o_m1); s2.carry_src = reinterpret_cast<const int*>(D + o_src1); s2.carry_cap = cap1;
     s2.fresh_n_slot = kTrkN2; s2.final_n_slot = kTrkNA;
     if (trk_clk) s2.clk = T.d_clk.as<long long>() + 8;
     s2.fresh_out = reinterpret_cast<uh_dmatch*>(D + o_m2); s2.fresh_src = reinterpret_cast<int*>(D + o_src2); s2.final_out = reinterpret_cast<uh_dmatch*>(D + o_ma); s2.final_src = reinterpret_cast<int*>(D + o_srca);
