@@ -661,8 +661,10 @@ typedef struct uh_projmatch uh_projmatch;
 int  uh_projmatch_create(uh_ctx* ctx, uh_projmatch** out);
 void uh_projmatch_destroy(uh_projmatch* pm);
 int  uh_projmatch_set_frame(uh_projmatch* pm, const uh_proj_frame* frame);
-/* the frame uh_orb_extract_frame_dev left on the device; `params` gives scale factors, camera and image bounds (its und_kpts / n_kpts / desc
- * are ignored).  `frame` must stay alive and un-overwritten while the matcher uses it. */
+/* the frame uh_orb_extract_frame_dev left on the device; `params` gives scale factors, camera and image bounds (its desc is ignored; its
+ * und_kpts / n_kpts too unless the frame's tree is built by the host core, uh_dev_frame_set_tree_builder(f, 1): then they are the frame's
+ * undistorted keypoints, exactly as many as its last extraction or upload gave the host, or UH_EINVAL).  `frame` must stay alive and
+ * un-overwritten while the matcher uses it. */
 int  uh_projmatch_set_frame_dev(uh_projmatch* pm, uh_dev_frame* frame, const uh_proj_frame* params);
 int  uh_projmatch_match(uh_projmatch* pm, const float* pose_f2g /* row-major 4x4 */, const uh_map_points* points,
                         float min_desc_dist, float max_repj_dist, uh_dmatch* matches_out, int32_t cap,
@@ -705,7 +707,8 @@ int  uh_projmatch_match_prev(uh_projmatch* pm, const float* pose_f2g /* row-majo
  * when that is >= 0, else the candidate's own.  Weight, in both solves (pnpsolver.cpp:210-211): map_weight[prev_map_row[i]] for an item
  * with prev_map_row[i] >= 0, map_weight of its row for a map candidate, 1 for a previous-frame item outside the local map — this entry has
  * no input for those items' stability (uh_track_pose_stereo's prev_weight has).  Needs a device-resident frame (uh_orb_extract_frame_dev +
- * uh_projmatch_set_frame_dev, either tree builder) of <= 4096 keypoints; pm and pnp on the same context. */
+ * uh_projmatch_set_frame_dev, either tree builder) of <= 4096 keypoints; pm and pnp on the same context.  Refuses a prev_map_row outside
+ * [-1, map->n) before anything is launched. */
 typedef struct uh_track_args {
     const float* pose0;                 /* predicted pose f2g, row-major 4x4 */
     const float* intr4;                 /* fx fy cx cy */
@@ -734,8 +737,8 @@ int  uh_track_pose(uh_projmatch* pm, uh_pnp* pnp, const uh_track_args* args, uh_
  *   prev_weight  prev->n: the solver weight (MapPoint::isStable: 1 or 0.5) of each previous-frame item, or NULL (= uh_track_pose: weight 1
  *                for items outside the local map).  An item's weight in both solves is map_weight[prev_map_row] when that row is >= 0, else
  *                prev_weight[i] (pnpsolver.cpp:210-211 in every solvePnp call).
- * The caller passes the same weights as for monocular frames (the stereo edges double theirs inside the solver).  Also refuses a
- * prev_map_row outside [-1, map->n).  With depth == NULL and prev_weight == NULL the results equal uh_track_pose's. */
+ * The caller passes the same weights as for monocular frames (the stereo edges double theirs inside the solver).  With depth == NULL and
+ * prev_weight == NULL the results equal uh_track_pose's. */
 typedef struct uh_track_stereo {
     const float* depth;
     float bl;

@@ -306,3 +306,51 @@ def test_device_frame_upload_and_split_extraction_protocol(hip_ctx):
     assert len(ext.extractFrameDevBegin(np.full((480, 640), 77, np.uint8), d, fp)) == 0
     k0, d0, u0 = ext.extractFrameDevEnd()
     assert len(k0) == 0
+
+
+@pytest.mark.gpu
+def test_host_tree_needs_the_frames_own_keypoint_count(hip_ctx):
+    """uh_projmatch_set_frame_dev with a host-built tree takes exactly as many keypoints as the frame's extraction (or upload) gave the host:
+    n - 1 and n + 1 are refused before anything is staged (a stale or foreign array would pair leaf ids with other keypoints' descriptors),
+    n is accepted and matches as the host route does."""
+    from ucoslam_cv3_amd._lib import UcoslamHipError
+    from ucoslam_cv3_amd.orb import Camera, DeviceFrame, FeatParams, ORBextractor
+    from ucoslam_cv3_amd.projmatch import ProjectionMatcher
+
+    ext = ORBextractor(hip_ctx)
+    cam = Camera(718.856, 718.856, 607.19, 185.22, ())
+    ext.setCamera(cam)
+    img = synth.frame(640, 480, seed=7)
+    fr = DeviceFrame(hip_ctx).setTreeBuilder(True)
+    kps, desc, und = ext.extractFrameDev(img, fr, FeatParams(maxFeatures=500, nOctaveLevels=8, scaleFactor=1.2))
+    n = len(kps)
+    assert n > 100
+    ukp = kps.copy()
+    ukp["x"], ukp["y"] = und[:, 0], und[:, 1]
+    sf = np.cumprod(np.concatenate([[np.float32(1)], np.full(7, np.float32(1.2))]).astype(np.float32)).astype(np.float32)
+    pm = ProjectionMatcher(hip_ctx)
+    for wrong in (ukp[: n - 1], np.concatenate([ukp, ukp[:1]])):
+        with pytest.raises(UcoslamHipError, match="host-built tree"):
+            pm.setFrameDev(fr, sf, cam.fx, cam.fy, cam.cx, cam.cy, (0, 0), (640, 480), und_kpts=wrong)
+    # a negative count through the C ABI (the Python wrapper always passes len()): refused for the extracted frame and for a host-tree frame
+    # that never received keypoints (whose count is unknown), never taken for the tree's size
+    import ctypes as C
+
+    from ucoslam_cv3_amd._lib import UH_EINVAL, lib, np_ptr
+    from ucoslam_cv3_amd.projmatch import _ProjFrame
+
+    for target in (fr, DeviceFrame(hip_ctx).setTreeBuilder(True)):
+        bad = _ProjFrame(np_ptr(ukp), -1, None, np_ptr(sf), len(sf), cam.fx, cam.fy, cam.cx, cam.cy, 0, 0, 640, 480)
+        assert lib().uh_projmatch_set_frame_dev(pm._h, target._h, C.byref(bad)) == UH_EINVAL
+    pm.setFrameDev(fr, sf, cam.fx, cam.fy, cam.cx, cam.cy, (0, 0), (640, 480), und_kpts=ukp)
+    host = ProjectionMatcher(hip_ctx)
+    host.setFrame(ukp, desc, sf, cam.fx, cam.fy, cam.cx, cam.cy, (0, 0), (640, 480))
+    rng = np.random.default_rng(8)
+    pick = rng.integers(0, n, 300)
+    z = rng.uniform(4, 40, 300)
+    pos3d = np.stack([(und[pick, 0] - cam.cx) / cam.fx * z, (und[pick, 1] - cam.cy) / cam.fy * z, z], 1).astype(np.float32)
+    ids, octv, mdesc = np.arange(300, dtype=np.uint32), kps["octave"][pick].astype(np.int32), np.ascontiguousarray(desc[pick])
+    eye = np.eye(4, dtype=np.float32).reshape(16)
+    a = host.matchFrameToPrevFrame(eye, ids, pos3d, octv, mdesc, 75.0, 15.0)
+    b = pm.matchFrameToPrevFrame(eye, ids, pos3d, octv, mdesc, 75.0, 15.0)
+    assert len(a["matches"]) > 100 and a["matches"].tobytes() == b["matches"].tobytes()

@@ -169,6 +169,36 @@ def test_hip_projmatch_big_frame_path(hip_ctx, oracle, monkeypatch):
 
 
 @pytest.mark.gpu
+def test_hip_projmatch_big_frame_knob_is_read_per_call(oracle, monkeypatch):
+    """UH_PROJMATCH_NO_LDS takes effect in a process whose matcher has already run: the search after it is set launches only the
+    tree-in-HBM instantiations (projmatch_kernel<false, ...>) and still equals the oracle; before it, only the LDS ones ran."""
+    import ucoslam_cv3_amd as u
+    from ucoslam_cv3_amd.projmatch import ProjectionMatcher
+
+    ctx = u.Context(0)   # (its own context: the session's is shared by every test, so its profiling stays off)
+    try:
+        ctx.prof_enable(True)
+        fr, mp, pose = synth.proj_problem(2000, 3000, 9, low_entropy=True)
+        pm = ProjectionMatcher(ctx)
+        pm.setFrame(fr["und_kpts"], fr["desc"], fr["scale_factors"], fr["fx"], fr["fy"], fr["cx"], fr["cy"], fr["min_xy"], fr["max_xy"])
+        ref = oracle_lib.proj_match(oracle, fr, mp, pose, 8.0, 15.0)
+        runs = {}
+        for knob in (False, True):
+            if knob:
+                monkeypatch.setenv("UH_PROJMATCH_NO_LDS", "1")
+            ctx.prof_reset()
+            got = pm.matchFrameToMapPoints(pose, mp["ids"], mp["pos3d"], mp["normal"], mp["min_dist"], mp["max_dist"], mp["desc"], 8.0, 15.0)
+            assert got["matches"].tobytes() == ref["matches"].tobytes() and len(ref["matches"]) > 100
+            np.testing.assert_array_equal(got["best_kp"], ref["best_kp"])
+            runs[knob] = [k for k, (calls, _) in ctx.prof_report().items() if "projmatch_kernel<" in k and calls > 0]   # (a reset keeps the names)
+        assert runs[False] and all("projmatch_kernel<true," in k for k in runs[False]), runs
+        assert runs[True] and all("projmatch_kernel<false," in k for k in runs[True]), runs
+    finally:
+        ctx.prof_enable(False)
+        ctx.close()
+
+
+@pytest.mark.gpu
 def test_hip_projmatch_edge_inputs(hip_ctx, oracle):
     import ucoslam_cv3_amd as u
     from ucoslam_cv3_amd.projmatch import ProjectionMatcher

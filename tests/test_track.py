@@ -160,6 +160,24 @@ def test_track_pose_equals_the_operators_in_reference_order(hip_ctx, host_tree):
 
 
 @pytest.mark.gpu
+def test_track_pose_refuses_bad_rows(hip_ctx):
+    """The monocular entry checks prev_map_row as the stereo one does (a row indexes map_weight on the host and the map search's positions
+    on the device): map n and -2 are refused before anything is launched, and the session goes on."""
+    from ucoslam_cv3_amd._lib import UcoslamHipError
+    from ucoslam_cv3_amd.pnp import PnPSolver
+
+    pnp = PnPSolver(hip_ctx)
+    sc = _scene(hip_ctx, 7, False, n_prev=300, n_map=1200)
+    for bad_row in (len(sc["mp"]["ids"]), -2):
+        rows = sc["prev_row"].copy()
+        rows[len(rows) // 2] = bad_row
+        with pytest.raises(UcoslamHipError, match="prev_map_row"):
+            sc["pm"].trackPose(pnp, sc["pose0"], sc["intr"], sc["inv_sf"], sc["prev"], sc["mp"], prev_map_row=rows, map_weight=sc["weight"])
+    f = sc["pm"].trackPose(pnp, sc["pose0"], sc["intr"], sc["inv_sf"], sc["prev"], sc["mp"], prev_map_row=sc["prev_row"], map_weight=sc["weight"])
+    _same(f, _sequence(sc, pnp), "after the refusals")
+
+
+@pytest.mark.gpu
 def test_track_pose_lost_without_a_first_solve_and_with_empty_sets(hip_ctx):
     from ucoslam_cv3_amd.pnp import PnPSolver
 

@@ -2292,11 +2292,6 @@ void quat_from_R_host(const double* R, double* q) {
     for (int a = 0; a < 4; a++) q[a] /= n;
 }
 
-struct Arena {
-    size_t off = 0;
-    template <typename T> size_t take(size_t count) { off = (off + 255) & ~(size_t)255; size_t o = off; off += count * sizeof(T); return o; }
-};
-
 int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
     hipStream_t st = b->ctx->stream;
     const BADims& d = b->dims;
@@ -2648,7 +2643,7 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr) {
     d.delta = b->params.huber_delta; d.dsqr = d.delta * d.delta; d.chi2_th = b->params.chi2_threshold;
 
     // carve one arena
-    Arena A;
+    uh::Layout A;
     const size_t o_pt_ptr = A.take<int>(P + 1), o_pt_edges = A.take<int>(E), o_cam_ptr = A.take<int>(nfree + 1), o_cam_edges = A.take<int>(cam_edges.size());
     const size_t o_e_pt = A.take<int>(E), o_e_kf = A.take<int>(E), o_uv = A.take<double>(2 * (size_t)E), o_w = A.take<double>(E);
     const size_t o_slot = A.take<int>(K), o_free = A.take<int>(std::max(nfree, 1)), o_intr = A.take<double>(4 * (size_t)K), o_edge_of = A.take<int>(edge_of.size());
@@ -2787,7 +2782,7 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr) {
 // ------------------------------------------------------------------------------------------------ staged setParams (persistent form)
 static StageLayout stage_layout(int Kc, int Pc) {
     StageLayout L;
-    Arena A;
+    uh::Layout A;
     L.pose0 = A.take<double>(7 * (size_t)Kc); L.poseR0 = A.take<double>(12 * (size_t)Kc); L.intr = A.take<double>(4 * (size_t)Kc);
     L.slot = A.take<int>(Kc); L.free_kf = A.take<int>(Kc); L.fix_kf = A.take<int>(Kc);
     L.poses_in = A.take<float>(16 * (size_t)Kc); L.fixed = A.take<unsigned char>(Kc); L.intr_f = A.take<float>(4 * (size_t)Kc);
@@ -2797,7 +2792,7 @@ static StageLayout stage_layout(int Kc, int Pc) {
 }
 static ResLayout res_layout(int Kc, int Pc, int Ec) {
     ResLayout R;
-    Arena A;
+    uh::Layout A;
     R.poses = A.take<float>(16 * (size_t)Kc); R.state = A.take<double>(7 * (size_t)Kc); R.points = A.take<float>(3 * (size_t)Pc);
     R.bad = A.take<unsigned char>(Ec);
     R.bytes_no_chi2 = (A.off + 7) & ~(size_t)7;
@@ -2995,7 +2990,7 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
         UH_HIP_CHECK(hipMemsetAsync(b->dscratch.p, 0, b->dscratch.cap, st));
         b->done_base = 0;
     }
-    Arena PA;
+    uh::Layout PA;
     PA.off = 256;   // [0, 64): the error word — never part of a tagged region
     const size_t o_part = PA.take<unsigned long long>(2 * (size_t)pl.G * pl.G * pl.SL), o_red = PA.take<unsigned long long>(2 * (size_t)pl.G * pl.SL);
     const size_t o_pc = PA.take<unsigned long long>(2 * 4 * (size_t)pl.G);

@@ -105,6 +105,13 @@ struct MappedBuf {
     MappedBuf& operator=(const MappedBuf&) = delete;
 };
 
+// Byte offsets of a block's regions, carved front to back: each region starts at the next multiple of `align` (256 by default; 16 is
+// enough for the 16-byte copies into pinned memory).  Start `off` past any word that must stay at a fixed place.
+struct Layout {
+    size_t off = 0;
+    template <typename T> size_t take(size_t count, size_t align = 256) { off = (off + align - 1) & ~(align - 1); const size_t o = off; off += count * sizeof(T); return o; }
+};
+
 // The device address of a host pointer the runtime knows as pinned (hipHostMalloc / hipHostRegister), NULL for pageable memory.
 inline void* device_alias_of_host(const void* p) {
     if (!p) return nullptr;

@@ -11,6 +11,8 @@ struct uh_dev_frame {
     uh::DevBuf buf;          // [descriptors n_cap x 32 | build input n_cap x 16 {und x, und y, bits(octave), -} | nodes | leaf records n_cap x 16 | scratch of the split build]
     uh::MappedBuf meta;      // uh_kd::Meta, written by the build launch; its word is the completion word the host polls
     int n_cap = 0;
+    int n_known = -1;        // the keypoint count the host last learned for this frame (uh_dev_frame_upload, the extraction's early and final counts);
+                             // -1: none yet, or the extraction failed.  A host-built tree (uh_projmatch_set_frame_dev) must be given exactly this many keypoints
     int threads = 512;       // of the build workgroup (UH_KD_THREADS: 256 / 512; 512 lanes leave each 256 registers: the cached row state of kdbuild.hpp)
     bool host_tree = false;  // uh_dev_frame_set_tree_builder(f, 1): no build launch — uh_projmatch_set_frame_dev builds the tree on the calling core from the host copy of the
                              // undistorted keypoints and uploads nodes + leaf records into this object; the descriptors still never leave the device

@@ -160,6 +160,7 @@ int uh_dev_frame_set_tree_builder(uh_dev_frame* f, int32_t on_host) {
 // Synchronous (a utility, not the per-frame path).
 int uh_dev_frame_upload(uh_dev_frame* f, const uh_keypoint* und_kpts, int32_t n, const uint8_t* desc) {
     UH_REQUIRE(f && n >= 0 && (n == 0 || (und_kpts && desc)), "uh_dev_frame_upload: bad arguments");
+    f->n_known = -1;
     int rc = uh::dev_frame_reserve(f, std::max(n, 1));
     if (rc) return rc;
     UH_HIP_CHECK(hipSetDevice(f->ctx->device));
@@ -176,6 +177,7 @@ int uh_dev_frame_upload(uh_dev_frame* f, const uh_keypoint* und_kpts, int32_t n,
     }
     if (!f->host_tree && (rc = uh::kd_build_launch(f, nullptr, 0, 0, n))) return rc;
     UH_HIP_CHECK(hipStreamSynchronize(f->ctx->stream));
+    f->n_known = n;
     return UH_OK;
 }
 

@@ -1414,6 +1414,7 @@ struct uh_orb {
         uh_keypoint* kps = nullptr; uint8_t* desc = nullptr; float* und_xy = nullptr;
         int cap = 0;
         size_t o_cnt = 0, o_kps = 0, o_desc = 0, o_und = 0;
+        uh_dev_frame* fr = nullptr;   // receives the final keypoint count
     } pending;
     uh::MappedBuf h_out;           // one-frame form: [completion word | count | keypoints | descriptors] when the caller's buffers are not pinned
     unsigned long long seq = 0;
@@ -1944,8 +1945,9 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
     UH_REQUIRE(!o->pending.active, "uh_orb_extract: uh_orb_extract_frame_dev_begin without its _end");
     *n_out = 0;
     if (early) *early = nullptr;
+    if (fr) fr->n_known = -1;   // (its content is replaced below: no count until this call has learned the new one)
     if (img == nullptr || w <= 0 || h <= 0) {   // ORBextractor.cpp:1254 — empty image: silent return (a device frame becomes the empty frame)
-        if (fr) { int rc0 = uh::dev_frame_reserve(fr, 1); if (rc0 || (!fr->host_tree && (rc0 = uh::kd_build_launch(fr, nullptr, 0, 0, 0)))) return rc0; }
+        if (fr) { int rc0 = uh::dev_frame_reserve(fr, 1); if (rc0 || (!fr->host_tree && (rc0 = uh::kd_build_launch(fr, nullptr, 0, 0, 0)))) return rc0; fr->n_known = 0; }
         return UH_OK;
     }
     UH_REQUIRE(cn == 1 || cn == 3 || cn == 4, "uh_orb_extract_frame: %d channels (1 = gray, 3 = BGR, 4 = BGRA)", cn);
@@ -2032,7 +2034,7 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
     if (fr && !fr->host_tree && (rc = uh::kd_build_launch(fr, o->d_level_counts.as<int>(), o->plan.nlevels, cap_launch, 0))) return rc;
     uh_orb::Pending& pd = o->pending;
     pd.active = true; pd.direct = direct; pd.und_direct = und_direct; pd.word = word; pd.kps = kps; pd.desc = desc; pd.und_xy = und_xy; pd.cap = cap;
-    pd.o_cnt = o_cnt; pd.o_kps = o_kps; pd.o_desc = o_desc; pd.o_und = o_und;
+    pd.o_cnt = o_cnt; pd.o_kps = o_kps; pd.o_desc = o_desc; pd.o_und = o_und; pd.fr = fr;
     if (early) {   // the keypoints' undistorted positions and octaves are enough for the caller to go on with (the kd-tree): the rest is collected by _end
         char* he = o->h_early.host<char>();
         if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(he), ea.word, st, "uh_orb_extract_frame_dev_begin"))) { pd.active = false; return rc; }
@@ -2040,6 +2042,7 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
         *n_out = n;
         *early = reinterpret_cast<const uh_keypoint*>(he + 128);
         if (n > cap) { pd.active = false; (void)hipStreamSynchronize(st); uh::set_error("uh_orb_extract: %d keypoints but capacity %d", n, cap); return UH_ECAPACITY; }
+        fr->n_known = n;
         return UH_OK;
     }
     return extract_finish(o, n_out);
@@ -2049,12 +2052,14 @@ static int extract_finish(uh_orb* o, int* n_out) {
     uh_orb::Pending& pd = o->pending;
     UH_REQUIRE(pd.active, "uh_orb_extract_frame_dev_end: no extraction in flight");
     pd.active = false;
+    if (pd.fr) pd.fr->n_known = -1;
     char* hb = o->h_out.host<char>();
     int rc;
     if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(hb), pd.word, o->ctx->stream, "uh_orb_extract"))) return rc;
     const int n = *reinterpret_cast<const int*>(hb + pd.o_cnt);
     if (n_out) *n_out = n;
     if (n > pd.cap) { uh::set_error("uh_orb_extract: %d keypoints but capacity %d", n, pd.cap); return UH_ECAPACITY; }
+    if (pd.fr) pd.fr->n_known = n;
     if (!pd.direct && n > 0) {
         std::memcpy(pd.kps, hb + pd.o_kps, (size_t)n * sizeof(uh_keypoint));
         std::memcpy(pd.desc, hb + pd.o_desc, (size_t)n * 32);

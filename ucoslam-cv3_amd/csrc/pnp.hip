@@ -773,65 +773,83 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
 struct uh_pnp {
     uh_ctx* ctx = nullptr;
     uh::DevBuf d_work;
-    uh::MappedBuf h_io;      // pinned, device-visible: [inputs | results | completion word]
+    uh::MappedBuf h_io;      // pinned, device-visible: [completion word | results | inputs]
     unsigned long long seq = 0;
-    bool attr_set = false, attr_set_st = false;
+    bool attr_set[2] = {false, false};   // the LDS attribute of pnp_solve_kernel<true, STEREO>, per STEREO
     long long* d_clk = nullptr;   // measurement hook (uh_pnp_debug_clocks)
     ~uh_pnp() { if (d_clk) (void)hipFree(d_clk); }
 };
 
 namespace {
 
+constexpr size_t pnp_rec_bytes(bool stereo) { return stereo ? kPnpRecBytesStereo : sizeof(MatchRec); }
+
+// the fields every entry sets; the callers add the device-side match count, the decision or the completion word
+PnpArgs pnp_args(const float* pose, const float* intr, int n, const float* p3d, const float* kp, const float* inv_sigma, const float* weight, const float* depth,
+                 float bl, void* work, float* pose_out, unsigned char* bad_out, int* result, double* state_out) {
+    PnpArgs A{};
+    A.pose_in = pose; A.intr = intr; A.n = n; A.p3d = p3d; A.kp = kp; A.invsig = inv_sigma; A.weight = weight; A.depth = depth; A.bl = bl;
+    A.work = work; A.pose_out = pose_out; A.bad_out = bad_out; A.result = result; A.state_out = state_out;
+    return A;
+}
+
+// the dynamic-LDS limit of a CACHED instantiation, set once per solver object
+int lds_attr(uh_pnp* p, const void* kernel, bool stereo) {
+    if (!p->attr_set[stereo]) UH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kPnpLdsMatches * pnp_rec_bytes(stereo))));
+    p->attr_set[stereo] = true;
+    return UH_OK;
+}
+
+// the instantiation: matches in LDS up to kPnpLdsMatches (CACHED), the stereo edges with a depth array (STEREO)
 int launch(uh_pnp* p, PnpArgs& A) {
-    const int n = A.n;
     A.clk = p->d_clk;
-    if (A.depth) {   // stereo / RGB-D observations: the three-row edge where depth > 0
-        if (n <= kPnpLdsMatches) {
-            const size_t lds = (size_t)std::max(n, 1) * kPnpRecBytesStereo;
-            if (!p->attr_set_st) {
-                UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_solve_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 kPnpLdsMatches * kPnpRecBytesStereo));
-                p->attr_set_st = true;
-            }
-            UH_LAUNCH(p->ctx, (pnp_solve_kernel<true, true>), dim3(1), dim3(kPnpThreads), lds, A);
-        } else {
-            UH_LAUNCH(p->ctx, (pnp_solve_kernel<false, true>), dim3(1), dim3(kPnpThreads), 0, A);
-        }
-        UH_HIP_CHECK(hipGetLastError());
-        return UH_OK;
-    }
-    if (n <= kPnpLdsMatches) {
-        const size_t lds = (size_t)std::max(n, 1) * 32;
-        if (!p->attr_set) {
-            UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPnpLdsMatches * 32));
-            p->attr_set = true;
-        }
-        UH_LAUNCH(p->ctx, pnp_solve_kernel<true>, dim3(1), dim3(kPnpThreads), lds, A);
+    const bool cached = A.n <= kPnpLdsMatches, stereo = A.depth != nullptr;
+    const size_t lds = cached ? (size_t)std::max(A.n, 1) * pnp_rec_bytes(stereo) : 0;
+    int rc;
+    // (stereo first, LDS form first in each: the order in which the instantiations have always been named, which fixes their order in the device code)
+    if (stereo) {
+        if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true, true>), true))) return rc;
+        if (cached) UH_LAUNCH(p->ctx, (pnp_solve_kernel<true, true>), dim3(1), dim3(kPnpThreads), lds, A);
+        else UH_LAUNCH(p->ctx, (pnp_solve_kernel<false, true>), dim3(1), dim3(kPnpThreads), 0, A);
     } else {
-        UH_LAUNCH(p->ctx, pnp_solve_kernel<false>, dim3(1), dim3(kPnpThreads), 0, A);
+        if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true>), false))) return rc;
+        if (cached) UH_LAUNCH(p->ctx, pnp_solve_kernel<true>, dim3(1), dim3(kPnpThreads), lds, A);
+        else UH_LAUNCH(p->ctx, pnp_solve_kernel<false>, dim3(1), dim3(kPnpThreads), 0, A);
     }
     UH_HIP_CHECK(hipGetLastError());
     return UH_OK;
+}
+
+// uh_pnp_solve_dev (d_depth == NULL) and uh_pnp_solve_stereo_dev
+int solve_dev(const char* fn, uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
+              const float* d_weight, const float* d_depth, float bl, void* d_work, float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
+    UH_REQUIRE(p && d_pose_f2g && d_intr4 && d_pose_out && d_result5, "%s: NULL argument", fn);
+    UH_REQUIRE(n >= 0, "%s: negative match count", fn);
+    if (d_depth) UH_REQUIRE(bl > 0.f, "%s: a depth array needs a baseline > 0 (bl = %g)", fn, (double)bl);
+    if (n > 0) UH_REQUIRE(d_p3d && d_kp && d_inv_sigma && d_weight && d_work && d_bad_out, "%s: NULL match arrays", fn);
+    UH_HIP_CHECK(hipSetDevice(p->ctx->device));
+    PnpArgs A = pnp_args(d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    return launch(p, A);
 }
 
 }  // namespace
 
 namespace uh {
 uh_ctx* pnp_ctx(uh_pnp* p) { return p->ctx; }
+// the scratch a solve over n_cap matches needs beyond the LDS (uh_track_pose reserves it before its first launch)
+int pnp_reserve(uh_pnp* p, int n_cap, bool stereo) {
+    return n_cap > kPnpLdsMatches ? p->d_work.reserve((size_t)n_cap * pnp_rec_bytes(stereo)) : UH_OK;
+}
 // the solve behind uh_track_pose: everything resident, the match count decided by an earlier launch of the same stream
 // d_depth != NULL: the stereo form (per-match depth, baseline bl)
 int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
                     const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl) {
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     int rc;
-    if (n_cap > kPnpLdsMatches && (rc = p->d_work.reserve((size_t)n_cap * (d_depth ? kPnpRecBytesStereo : 32)))) return rc;
-    PnpArgs A{};
-    A.pose_in = d_pose; A.intr = d_intr4; A.n = n_cap; A.n_dev = d_n; A.p3d = d_p3d; A.kp = d_kp; A.invsig = d_inv_sigma; A.weight = d_weight;
-    A.work = p->d_work.p;
-    A.pose_out = d_pose_out; A.bad_out = d_bad_out; A.result = d_result5; A.state_out = nullptr;
-    A.host_done = nullptr; A.done_word = 0;
+    if ((rc = pnp_reserve(p, n_cap, d_depth != nullptr))) return rc;
+    PnpArgs A = pnp_args(d_pose, d_intr4, n_cap, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, p->d_work.p, d_pose_out, d_bad_out, d_result5, nullptr);
+    A.n_dev = d_n;
     if (dec) A.dec = *dec;
-    A.depth = d_depth; A.bl = bl;
     return launch(p, A);
 }
 }  // namespace uh
@@ -852,16 +870,7 @@ void uh_pnp_destroy(uh_pnp* p) { delete p; }
 int uh_pnp_solve_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                      const float* d_inv_sigma, const float* d_weight, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
                      int32_t* d_result5, double* d_state7) {
-    UH_REQUIRE(p && d_pose_f2g && d_intr4 && d_pose_out && d_result5, "uh_pnp_solve_dev: NULL argument");
-    UH_REQUIRE(n >= 0, "uh_pnp_solve_dev: negative match count");
-    if (n > 0) UH_REQUIRE(d_p3d && d_kp && d_inv_sigma && d_weight && d_work && d_bad_out, "uh_pnp_solve_dev: NULL match arrays");
-    UH_HIP_CHECK(hipSetDevice(p->ctx->device));
-    PnpArgs A{};
-    A.pose_in = d_pose_f2g; A.intr = d_intr4; A.n = n; A.p3d = d_p3d; A.kp = d_kp; A.invsig = d_inv_sigma; A.weight = d_weight;
-    A.work = d_work;
-    A.pose_out = d_pose_out; A.bad_out = d_bad_out; A.result = d_result5; A.state_out = d_state7;
-    A.host_done = nullptr; A.done_word = 0;
-    return launch(p, A);
+    return solve_dev("uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, nullptr, 0.f, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
 // Stereo / RGB-D form of uh_pnp_solve_dev: d_depth (n floats, device) as in uh_pnp_solve_stereo; d_work = n * 36 bytes when d_depth is given.
@@ -869,20 +878,8 @@ int uh_pnp_solve_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, i
 int uh_pnp_solve_stereo_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                             const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, void* d_work, float* d_pose_out,
                             uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
-    if (!d_depth)
-        return uh_pnp_solve_dev(p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
-    UH_REQUIRE(p && d_pose_f2g && d_intr4 && d_pose_out && d_result5, "uh_pnp_solve_stereo_dev: NULL argument");
-    UH_REQUIRE(n >= 0, "uh_pnp_solve_stereo_dev: negative match count");
-    UH_REQUIRE(bl > 0.f, "uh_pnp_solve_stereo_dev: a depth array needs a baseline > 0 (bl = %g)", (double)bl);
-    if (n > 0) UH_REQUIRE(d_p3d && d_kp && d_inv_sigma && d_weight && d_work && d_bad_out, "uh_pnp_solve_stereo_dev: NULL match arrays");
-    UH_HIP_CHECK(hipSetDevice(p->ctx->device));
-    PnpArgs A{};
-    A.pose_in = d_pose_f2g; A.intr = d_intr4; A.n = n; A.p3d = d_p3d; A.kp = d_kp; A.invsig = d_inv_sigma; A.weight = d_weight;
-    A.work = d_work;
-    A.pose_out = d_pose_out; A.bad_out = d_bad_out; A.result = d_result5; A.state_out = d_state7;
-    A.host_done = nullptr; A.done_word = 0;
-    A.depth = d_depth; A.bl = bl;
-    return launch(p, A);
+    return solve_dev(d_depth ? "uh_pnp_solve_stereo_dev" : "uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth,
+                     d_depth ? bl : 0.f, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
 // Host-pointer form: PnPSolver::solvePnp(frame, map, matches, pose): returns the inlier count (>= 0) or a negative error.
@@ -902,19 +899,17 @@ int uh_pnp_solve_stereo(uh_pnp* p, const float* pose_f2g, const float* intr4, in
     UH_REQUIRE(n >= 0, "%s: negative match count", fn);
     if (n == 0) { memcpy(pose_out, pose_f2g, 64); if (iters_out4) memset(iters_out4, 0, 16); return 0; }   // pnpsolver.cpp:149-150
     UH_REQUIRE(p3d && kp && inv_sigma && weight && bad_out, "%s: NULL match arrays", fn);
-    if (depth) {
-        bool any = false;
-        for (int i = 0; i < n && !any; i++) any = !(depth[i] <= 0.f);
-        UH_REQUIRE(!any || bl > 0.f, "uh_pnp_solve_stereo: stereo matches need a baseline > 0 (bl = %g)", (double)bl);
-    }
+    const bool any_depth = depth && std::any_of(depth, depth + n, [](float d) { return !(d <= 0.f); });
+    UH_REQUIRE(!any_depth || bl > 0.f, "uh_pnp_solve_stereo: stereo matches need a baseline > 0 (bl = %g)", (double)bl);
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     const size_t nf = (size_t)n;
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t o_done = 0, o_pout = 64, o_res = 128, o_state = 192, o_pose = 256, o_intr = 320, o_p3d = 384, o_kp = al(o_p3d + nf * 12), o_is = al(o_kp + nf * 8),
-                 o_w = al(o_is + nf * 4), o_bad = al(o_w + nf * 4), o_dep = al(o_bad + nf), total = al(o_dep + (depth ? nf * 4 : 0));
+    uh::Layout L{64};   // the pinned block, 64-byte regions: [0, 64) the completion word, the results, the inputs
+    const size_t o_pout = L.take<float>(16, 64), o_res = L.take<int>(5, 64), o_state = L.take<double>(7, 64), o_pose = L.take<float>(16, 64), o_intr = L.take<float>(4, 64);
+    const size_t o_p3d = L.take<float>(3 * nf, 64), o_kp = L.take<float>(2 * nf, 64), o_is = L.take<float>(nf, 64), o_w = L.take<float>(nf, 64), o_bad = L.take<unsigned char>(nf, 64),
+                 o_dep = L.take<float>(depth ? nf : 0, 64), total = L.take<char>(0, 64);
     int rc;
     if ((rc = p->h_io.reserve(total))) return rc;
-    if (n > kPnpLdsMatches && (rc = p->d_work.reserve(nf * (depth ? kPnpRecBytesStereo : 32)))) return rc;
+    if ((rc = uh::pnp_reserve(p, n, depth != nullptr))) return rc;
     char* h = p->h_io.host<char>();
     char* d = p->h_io.dev<char>();
     memcpy(h + o_pose, pose_f2g, 64);
@@ -924,17 +919,14 @@ int uh_pnp_solve_stereo(uh_pnp* p, const float* pose_f2g, const float* intr4, in
     memcpy(h + o_is, inv_sigma, nf * 4);
     memcpy(h + o_w, weight, nf * 4);
     if (depth) memcpy(h + o_dep, depth, nf * 4);
-    PnpArgs A{};
-    A.depth = depth ? (const float*)(d + o_dep) : nullptr; A.bl = bl;
-    A.pose_in = (const float*)(d + o_pose); A.intr = (const float*)(d + o_intr); A.n = n;
-    A.p3d = (const float*)(d + o_p3d); A.kp = (const float*)(d + o_kp); A.invsig = (const float*)(d + o_is); A.weight = (const float*)(d + o_w);
-    A.work = p->d_work.p;
-    A.pose_out = (float*)(d + o_pout); A.bad_out = (unsigned char*)(d + o_bad); A.result = (int*)(d + o_res); A.state_out = (double*)(d + o_state);
-    A.host_done = (unsigned long long*)(d + o_done);
+    PnpArgs A = pnp_args((const float*)(d + o_pose), (const float*)(d + o_intr), n, (const float*)(d + o_p3d), (const float*)(d + o_kp), (const float*)(d + o_is),
+                         (const float*)(d + o_w), depth ? (const float*)(d + o_dep) : nullptr, bl, p->d_work.p, (float*)(d + o_pout), (unsigned char*)(d + o_bad),
+                         (int*)(d + o_res), (double*)(d + o_state));
+    A.host_done = (unsigned long long*)d;
     A.done_word = ++p->seq;
     std::atomic_thread_fence(std::memory_order_release);
     if ((rc = launch(p, A))) return rc;
-    if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(h + o_done), A.done_word, p->ctx->stream, fn))) return rc;
+    if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(h), A.done_word, p->ctx->stream, fn))) return rc;
     int32_t res[5];
     memcpy(res, h + o_res, 20);
     memcpy(pose_out, h + o_pout, 64);

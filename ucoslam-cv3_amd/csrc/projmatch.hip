@@ -786,6 +786,48 @@ struct uh_projmatch {
     ~uh_projmatch();
 };
 
+// The tree over the frame's undistorted keypoints, built by this core (uh_projmatch_set_frame; uh_projmatch_set_frame_dev with a host-built tree).
+// t0: uh_projmatch_set_frame's UH_PM_TIMING clock, started in front of the build (NULL: no timing)
+static int pm_build_tree(uh_projmatch* h, const uh_proj_frame* f, const char* what, std::chrono::steady_clock::time_point* t0) {
+    const int n = f->n_kpts;
+    h->xy.resize(2 * (size_t)std::max(n, 1));
+    h->oct.resize(std::max(n, 1));
+    for (int i = 0; i < n; i++) {
+        // the kernel packs a candidate's octave into 4 bits and an int8: anything outside [0,16) would silently corrupt bestLevel / bestLevel2
+        UH_REQUIRE(f->und_kpts[i].octave >= 0 && f->und_kpts[i].octave < 16, "%s: octave %d of keypoint %d outside [0,16)", what, f->und_kpts[i].octave, i);
+        h->xy[2 * i] = f->und_kpts[i].x; h->xy[2 * i + 1] = f->und_kpts[i].y; h->oct[i] = f->und_kpts[i].octave;
+    }
+    if (t0) *t0 = std::chrono::steady_clock::now();
+    h->kd.build(h->xy.data(), n);
+    if (t0) fprintf(stderr, "kd build: %.1f us (n=%d, depth %d, nodes %zu)\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - *t0).count(), n, h->kd.max_depth, h->kd.nodes.size());
+    UH_REQUIRE(h->kd.max_depth <= kMaxDepth, "%s: kd-tree depth %d exceeds the walk stack (%d levels)", what, h->kd.max_depth, kMaxDepth);
+    return UH_OK;
+}
+
+// the leaf records of the host-built tree, in leaf order: {x, y, bits(keypoint << 4 | octave), 0}
+static void pm_leaf_records(const uh_projmatch* h, float* lr, int n) {
+    for (int i = 0; i < n; i++) {
+        const uint32_t id = h->kd.leaf_idx[i], io = (id << 4) | (uint32_t)h->oct[id];
+        lr[4 * i] = h->xy[2 * (size_t)id]; lr[4 * i + 1] = h->xy[2 * (size_t)id + 1];
+        std::memcpy(lr + 4 * i + 2, &io, 4); lr[4 * i + 3] = 0.f;
+    }
+}
+
+// the matcher's frame from now on: its arrays and tree, and the camera / scale / image-bounds fields of f
+static void pm_adopt(uh_projmatch* h, const uh_proj_frame* f, const void* desc, const void* nodes, const float4* leaf, const float* scale, const double* box, int n, int n_nodes,
+                     int max_depth, uh_dev_frame* dev) {
+    PmFrame& d = h->fr;
+    d.kp_desc = reinterpret_cast<const uint64_t*>(desc); d.nodes = reinterpret_cast<const KdNodeDev*>(nodes); d.leaf_rec = leaf; d.scale = scale;
+    for (int i = 0; i < 4; i++) d.box[i] = box[i];
+    d.n_levels = f->n_levels; d.n_kpts = n;
+    d.fx = f->fx; d.fy = f->fy; d.cx = f->cx; d.cy = f->cy;
+    d.min_x = (float)f->min_x; d.min_y = (float)f->min_y; d.max_x = (float)f->max_x; d.max_y = (float)f->max_y;
+    d.log_scale = f->n_levels > 1 ? std::log(f->scale_factors[1]) : 1.f;   // float overload = libm logf, as Frame::predictScale
+    h->n_kpts = n; h->n_levels = f->n_levels;
+    h->n_nodes = n_nodes; h->max_depth = max_depth; h->dev = dev;
+    h->have_frame = true;
+}
+
 extern "C" {
 
 int uh_projmatch_create(uh_ctx* ctx, uh_projmatch** out) {
@@ -814,27 +856,15 @@ int uh_projmatch_set_frame(uh_projmatch* h, const uh_proj_frame* f) {
     UH_REQUIRE(f->n_kpts >= 0 && (f->n_kpts == 0 || (f->und_kpts && f->desc)), "uh_projmatch_set_frame: keypoints / descriptors missing");
     UH_REQUIRE(f->n_levels >= 1 && f->scale_factors, "uh_projmatch_set_frame: scale factors missing");
     UH_HIP_CHECK(hipSetDevice(h->ctx->device));
-    hipStream_t st = h->ctx->stream;
     const int n = f->n_kpts;
-    std::vector<float>& xy = h->xy;
-    std::vector<int>& oct = h->oct;
-    xy.resize(2 * (size_t)std::max(n, 1));
-    oct.resize(std::max(n, 1));
-    for (int i = 0; i < n; i++) {
-        // the kernel packs a candidate's octave into 4 bits and an int8: anything outside [0,16) would silently corrupt bestLevel / bestLevel2
-        UH_REQUIRE(f->und_kpts[i].octave >= 0 && f->und_kpts[i].octave < 16, "uh_projmatch_set_frame: octave %d of keypoint %d outside [0,16)", f->und_kpts[i].octave, i);
-        xy[2 * i] = f->und_kpts[i].x; xy[2 * i + 1] = f->und_kpts[i].y; oct[i] = f->und_kpts[i].octave;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    h->kd.build(xy.data(), n);
-    if (getenv("UH_PM_TIMING")) fprintf(stderr, "kd build: %.1f us (n=%d, depth %d, nodes %zu)\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), n, h->kd.max_depth, h->kd.nodes.size());
-    UH_REQUIRE(h->kd.max_depth <= kMaxDepth, "uh_projmatch_set_frame: kd-tree depth %d exceeds the walk stack (%d levels)", h->kd.max_depth, kMaxDepth);
+    const bool timing = getenv("UH_PM_TIMING") != nullptr;   // (measurement: the build's and the call's time)
+    std::chrono::steady_clock::time_point t0;
+    int rc;
+    if ((rc = pm_build_tree(h, f, "uh_projmatch_set_frame", timing ? &t0 : nullptr))) return rc;
     const size_t nn = h->kd.nodes.size();
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_desc = 0, o_nodes = al(o_desc + 32 * (size_t)n);
-    const size_t o_leaf = al(o_nodes + sizeof(KdNodeDev) * nn), o_scale = al(o_leaf + 16 * (size_t)n), total = al(o_scale + 4 * (size_t)f->n_levels);
-    int rc = h->d_frame.reserve(total + 256);
-    if (rc) return rc;
+    uh::Layout L;
+    const size_t o_desc = L.take<uint8_t>(32 * (size_t)n), o_nodes = L.take<KdNodeDev>(nn), o_leaf = L.take<float4>(n), o_scale = L.take<float>(f->n_levels), total = L.take<char>(0);
+    if ((rc = h->d_frame.reserve(total + 256))) return rc;
     char* base = h->d_frame.as<char>();
     {   // one pinned staging block, one 16-byte-wide copy launch, no synchronisation: the block is only reused by the NEXT set_frame,
         // which first makes sure this upload has landed (its completion word — long since posted unless two set_frame calls follow
@@ -845,36 +875,22 @@ int uh_projmatch_set_frame(uh_projmatch* h, const uh_proj_frame* f) {
         if (n) {
             std::memcpy(hi + o_desc, f->desc, 32 * (size_t)n);
             std::memcpy(hi + o_nodes, h->kd.nodes.data(), sizeof(KdNodeDev) * nn);
-            float* lr = reinterpret_cast<float*>(hi + o_leaf);   // the leaf records, in leaf order
-            for (int i = 0; i < n; i++) {
-                const uint32_t id = h->kd.leaf_idx[i], io = (id << 4) | (uint32_t)oct[id];
-                lr[4 * i] = xy[2 * (size_t)id]; lr[4 * i + 1] = xy[2 * (size_t)id + 1];
-                std::memcpy(lr + 4 * i + 2, &io, 4); lr[4 * i + 3] = 0.f;
-            }
+            pm_leaf_records(h, reinterpret_cast<float*>(hi + o_leaf), n);
         }
         std::memcpy(hi + o_scale, f->scale_factors, 4 * (size_t)f->n_levels);
         std::atomic_thread_fence(std::memory_order_release);
         if ((rc = uh::copy16(h->ctx, base, h->h_frame.dev<char>() + 64, total))) return rc;
         h->upload_pending = true;
     }
-    if (getenv("UH_PM_TIMING")) fprintf(stderr, "set_frame total: %.1f us (bytes %zu)\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), total);
-    PmFrame& d = h->fr;
-    d.kp_desc = (const uint64_t*)(base + o_desc);
-    d.nodes = (const KdNodeDev*)(base + o_nodes); d.leaf_rec = (const float4*)(base + o_leaf); d.scale = (const float*)(base + o_scale);
-    for (int i = 0; i < 4; i++) d.box[i] = h->kd.root_box[i];
-    d.n_levels = f->n_levels; d.n_kpts = n;
-    d.fx = f->fx; d.fy = f->fy; d.cx = f->cx; d.cy = f->cy;
-    d.min_x = (float)f->min_x; d.min_y = (float)f->min_y; d.max_x = (float)f->max_x; d.max_y = (float)f->max_y;
-    d.log_scale = f->n_levels > 1 ? std::log(f->scale_factors[1]) : 1.f;   // float overload = libm logf, as Frame::predictScale
-    h->n_kpts = n; h->n_levels = f->n_levels;
-    h->n_nodes = (int)nn; h->max_depth = h->kd.max_depth; h->dev = nullptr;
-    h->have_frame = true;
+    if (timing) fprintf(stderr, "set_frame total: %.1f us (bytes %zu)\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), total);
+    pm_adopt(h, f, base + o_desc, base + o_nodes, reinterpret_cast<const float4*>(base + o_leaf), reinterpret_cast<const float*>(base + o_scale), h->kd.root_box, n, (int)nn,
+             h->kd.max_depth, nullptr);
     return UH_OK;
 }
 
 // The frame the extractor left on the device (uh_orb_extract_frame_dev: descriptors, undistorted keypoints in leaf order, kd-tree built by
 // kdbuild.hip) becomes the matcher's frame: no keypoints or descriptors cross the host link, no tree is built on the host.  `f` carries the
-// camera / scale / image-bounds fields only (und_kpts, n_kpts, desc are ignored).
+// camera / scale / image-bounds fields (desc is ignored; und_kpts / n_kpts too, but for a frame whose tree the host core builds).
 int uh_projmatch_set_frame_dev(uh_projmatch* h, uh_dev_frame* fr, const uh_proj_frame* f) {
     UH_REQUIRE(h && fr && f, "uh_projmatch_set_frame_dev: NULL argument");
     UH_REQUIRE(fr->ctx == h->ctx, "uh_projmatch_set_frame_dev: the device frame belongs to another context");
@@ -888,65 +904,32 @@ int uh_projmatch_set_frame_dev(uh_projmatch* h, uh_dev_frame* fr, const uh_proj_
     }
     if (fr->host_tree) {
         // the tree by this core (KdBuilder, as uh_projmatch_set_frame), nodes and leaf records uploaded into the frame object; the descriptors
-        // and everything else stay where the extractor left them
+        // and everything else stay where the extractor left them.  The keypoints must be the frame's own: as many as the host last learned
+        // it has (a stale or foreign array would pair leaf ids with other keypoints' descriptors).
         const int n = f->n_kpts;
-        UH_REQUIRE(n >= 0 && n <= fr->n_cap && (n == 0 || f->und_kpts), "uh_projmatch_set_frame_dev: %d keypoints for a device frame of capacity %d (host-built tree)", n, fr->n_cap);
-        std::vector<float>& xy = h->xy;
-        std::vector<int>& oct = h->oct;
-        xy.resize(2 * (size_t)std::max(n, 1));
-        oct.resize(std::max(n, 1));
-        for (int i = 0; i < n; i++) {
-            UH_REQUIRE(f->und_kpts[i].octave >= 0 && f->und_kpts[i].octave < 16, "uh_projmatch_set_frame_dev: octave %d of keypoint %d outside [0,16)", f->und_kpts[i].octave, i);
-            xy[2 * i] = f->und_kpts[i].x; xy[2 * i + 1] = f->und_kpts[i].y; oct[i] = f->und_kpts[i].octave;
-        }
-        h->kd.build(xy.data(), n);
-        UH_REQUIRE(h->kd.max_depth <= kMaxDepth, "uh_projmatch_set_frame_dev: kd-tree depth %d exceeds the walk stack (%d levels)", h->kd.max_depth, kMaxDepth);
+        UH_REQUIRE(n >= 0 && n == fr->n_known && n <= fr->n_cap && (n == 0 || f->und_kpts), "uh_projmatch_set_frame_dev: %d keypoints for a device frame of %d (host-built tree)",
+                   n, fr->n_known);   // (n >= 0: an unknown count, n_known = -1, matches no request)
+        if ((rc = pm_build_tree(h, f, "uh_projmatch_set_frame_dev", nullptr))) return rc;
         const size_t nn = h->kd.nodes.size(), gap = fr->o_leaf - fr->o_nodes, span = gap + 16 * (size_t)n;
         UH_REQUIRE(sizeof(KdNodeDev) * nn <= gap, "uh_projmatch_set_frame_dev: %zu nodes exceed the device frame's node block", nn);
-        hipStream_t st = h->ctx->stream;
         if ((rc = pm_staging_free(h, "uh_projmatch_set_frame_dev"))) return rc;
         if ((rc = h->h_frame.reserve(span + 64))) return rc;
         char* hi = h->h_frame.host<char>() + 64;   // (the first 64 bytes hold the completion word)
         if (n) {
             std::memcpy(hi, h->kd.nodes.data(), sizeof(KdNodeDev) * nn);
-            float* lr = reinterpret_cast<float*>(hi + gap);   // the leaf records, in leaf order
-            for (int i = 0; i < n; i++) {
-                const uint32_t id = h->kd.leaf_idx[i], io = (id << 4) | (uint32_t)oct[id];
-                lr[4 * i] = xy[2 * (size_t)id]; lr[4 * i + 1] = xy[2 * (size_t)id + 1];
-                std::memcpy(lr + 4 * i + 2, &io, 4); lr[4 * i + 3] = 0.f;
-            }
+            pm_leaf_records(h, reinterpret_cast<float*>(hi + gap), n);
             std::atomic_thread_fence(std::memory_order_release);
             // (one launch over the node block and the leaf records: the unused tail of the node block travels with them — a few KB against a second launch)
             if ((rc = uh::copy16(h->ctx, reinterpret_cast<char*>(fr->nodes()), h->h_frame.dev<char>() + 64, span))) return rc;
             h->upload_pending = true;
         }
-        PmFrame& d = h->fr;
-        d.kp_desc = reinterpret_cast<const uint64_t*>(fr->desc());
-        d.nodes = reinterpret_cast<const KdNodeDev*>(fr->nodes()); d.leaf_rec = fr->leaf(); d.scale = h->d_scale.as<float>();
-        for (int i = 0; i < 4; i++) d.box[i] = h->kd.root_box[i];
-        d.n_levels = f->n_levels; d.n_kpts = n;
-        d.fx = f->fx; d.fy = f->fy; d.cx = f->cx; d.cy = f->cy;
-        d.min_x = (float)f->min_x; d.min_y = (float)f->min_y; d.max_x = (float)f->max_x; d.max_y = (float)f->max_y;
-        d.log_scale = f->n_levels > 1 ? std::log(f->scale_factors[1]) : 1.f;
-        h->n_kpts = n; h->n_levels = f->n_levels;
-        h->n_nodes = (int)nn; h->max_depth = h->kd.max_depth; h->dev = fr;
-        h->have_frame = true;
+        pm_adopt(h, f, fr->desc(), fr->nodes(), fr->leaf(), h->d_scale.as<float>(), h->kd.root_box, n, (int)nn, h->kd.max_depth, fr);
         return UH_OK;
     }
     const uh_kd::Meta* m = nullptr;
     if ((rc = uh::dev_frame_wait(fr, &m, "uh_projmatch_set_frame_dev"))) return rc;   // (the build runs behind the extractor's completion word: normally done)
     UH_REQUIRE(m->max_depth <= kMaxDepth, "uh_projmatch_set_frame_dev: kd-tree depth %d exceeds the walk stack (%d levels)", m->max_depth, kMaxDepth);
-    PmFrame& d = h->fr;
-    d.kp_desc = reinterpret_cast<const uint64_t*>(fr->desc());
-    d.nodes = reinterpret_cast<const KdNodeDev*>(fr->nodes()); d.leaf_rec = fr->leaf(); d.scale = h->d_scale.as<float>();
-    for (int i = 0; i < 4; i++) d.box[i] = m->box[i];
-    d.n_levels = f->n_levels; d.n_kpts = m->n;
-    d.fx = f->fx; d.fy = f->fy; d.cx = f->cx; d.cy = f->cy;
-    d.min_x = (float)f->min_x; d.min_y = (float)f->min_y; d.max_x = (float)f->max_x; d.max_y = (float)f->max_y;
-    d.log_scale = f->n_levels > 1 ? std::log(f->scale_factors[1]) : 1.f;
-    h->n_kpts = m->n; h->n_levels = f->n_levels;
-    h->n_nodes = m->n_nodes; h->max_depth = m->max_depth; h->dev = fr;
-    h->have_frame = true;
+    pm_adopt(h, f, fr->desc(), fr->nodes(), fr->leaf(), h->d_scale.as<float>(), m->box, m->n, m->n_nodes, m->max_depth, fr);
     return UH_OK;
 }
 
@@ -979,34 +962,58 @@ int uh_projmatch_debug_tree(uh_projmatch* h, int32_t* n_nodes, const void** node
 
 namespace {
 
-// What a search leaves behind until its results are collected: where they lie (HBM, pinned twin) and the call's completion word.
+// What a search leaves behind until its results are collected: where they lie (HBM) and the call's completion word.
 struct PmPending {
-    int n = 0, slot = 0;
-    bool prev = false;
+    int n = 0, slot = 0; bool prev = false;
     unsigned long long word = 0;
     const int* d_best_kp = nullptr; const float* d_best_dist = nullptr;   // HBM (for launches behind this one on the same stream)
-    const float* d_rec = nullptr;                                        // the candidates' 64-byte records (pinned, device address)
-    size_t o_bk = 0, o_bd = 0, o_vis = 0;
 };
 
-// Stage the candidates and enqueue the search (no waiting).  octave == nullptr: Map::matchFrameToMapPoints; normal / min / max == nullptr: the
-// previous-frame search.  dyn != nullptr: pose and radius are read from device memory at launch time (written by an earlier launch of this stream).
-int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn* dyn, int n, const float* pos3d, const float* normal,
-                  const float* mn_dist, const float* mx_dist, const uint8_t* desc, const int32_t* octave, float min_desc_dist, float max_repj_dist, PmPending* pend,
-                  float4* pos_out = nullptr, const uint32_t* ids = nullptr, const int32_t* rows = nullptr, const float* weights = nullptr, const float* weights_by_row = nullptr,
-                  uint4* aux_out = nullptr, const float* prev_weights = nullptr) {
-    const bool prev = octave != nullptr;
+// A slot's blocks for n candidates: byte offsets.  d_points: [0, 256) the walk status word (overflow flag, UH_PM_CLK stamps, the publish
+// ticket at +128), then best_kp | best_dist | visible, which the kernel's last workgroup copies to +64 of h_out (behind the completion word).
+// h_in: the candidates' 64-byte records, then uh_track_pose's 16-byte {id, map row, weight} records.
+struct PmSlotLayout { size_t bk, bd, vis, end, rec, aux, in_bytes; };
+PmSlotLayout pm_slot_layout(int n) {
+    PmSlotLayout L;
+    uh::Layout d{256};
+    L.bk = d.take<int>(n); L.bd = d.take<float>(n, 4); L.vis = d.take<unsigned char>(n, 4); L.end = d.take<char>(0);
+    uh::Layout in;
+    L.rec = in.take<uint4>(4 * (size_t)n); L.aux = in.take<uint4>(n, 16); L.in_bytes = in.off + 64;
+    return L;
+}
+
+// The slot's buffers for n candidates (uh_track_pose reserves both slots before its first launch: a buffer that grows is freed, which
+// synchronises the device)
+int match_reserve(uh_projmatch* h, int slot, int n) {
+    uh_projmatch::Slot& S = h->slot[slot];
+    const PmSlotLayout L = pm_slot_layout(n);
+    int rc = S.d_points.reserve(L.end + 256);
+    if (!rc) rc = S.h_out.reserve(L.end - L.bk + 64);
+    return rc ? rc : S.h_in.reserve(L.in_bytes);
+}
+
+// uh_track_pose's part of a search: each candidate's position and {id, map row, solver weight} record, left in HBM for the look-ups
+struct PmTrack {
+    const int32_t* rows;       // previous-frame items: row of the same point in the local map or -1 (NULL: all -1); a map candidate's row is its own
+    const float* map_weight;   // per map row (NULL: all 1)
+    const float* prev_weight;  // previous-frame items outside the local map (uh_track_pose_stereo; NULL: all 1)
+    float4* pos_out; uint4* aux_out;
+};
+
+// Stage the candidates — the local map's points (mp: Map::matchFrameToMapPoints) or the previous frame's items (pp) — and enqueue the search
+// (no waiting).  dyn != nullptr: pose and radius are read from device memory at launch time (written by an earlier launch of this stream).
+int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn* dyn, const uh_map_points* mp, const uh_prev_points* pp,
+                  float min_desc_dist, float max_repj_dist, PmPending* pend, const PmTrack* trk = nullptr) {
+    const bool prev = pp != nullptr;
+    const int n = prev ? pp->n : mp->n;
+    const float* pos3d = prev ? pp->pos3d : mp->pos3d;
+    const uint8_t* desc = prev ? pp->desc : mp->desc;
     uh_projmatch::Slot& S = h->slot[slot];
     UH_HIP_CHECK(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_pos = 256 /* [0, 256): the walk-overflow status word, at a fixed place */;
-    const size_t o_bk = 256, o_bd = o_bk + 4 * (size_t)n, o_vis = o_bd + 4 * (size_t)n;
-    const size_t o_ovf = 0, o_end = al(o_vis + (size_t)n), total = o_end + 256;
-    int rc = S.d_points.reserve(total);
+    int rc = match_reserve(h, slot, n);
     if (rc) return rc;
-    const size_t out_bytes = o_end - o_bk;
-    if ((rc = S.h_out.reserve(out_bytes + 64))) return rc;
+    const PmSlotLayout L = pm_slot_layout(n);
     char* base = S.d_points.as<char>();
     if (!S.ovf_zeroed || S.ovf_gen != S.d_points.gen) {   // the walk-overflow word: zero once per allocation, the kernel's last workgroup clears it after every call
         UH_HIP_CHECK(hipMemsetAsync(base, 0, 256, st));
@@ -1017,22 +1024,21 @@ int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn*
     static const bool pm_timing = getenv("UH_PM_TIMING") != nullptr;
     const auto t_pack0 = std::chrono::steady_clock::now();
     {   // one pinned staging block (the previous call's launches are complete: its results were awaited): the candidates as 64-byte records
-        if ((rc = S.h_in.reserve(o_pos + 80 * (size_t)n + 64))) return rc;   // (64-byte records, then uh_track_pose's 16-byte ones)
         char* hi = S.h_in.host<char>();
-        if (pos_out) {   // uh_track_pose: {id, row of the same point in the local map (a map candidate: its own), the solver weight of that row}
-            uint32_t* ax = reinterpret_cast<uint32_t*>(hi + o_pos + 64 * (size_t)n);
+        if (trk) {   // {id, row of the same point in the local map, the solver weight of that row — or, outside the local map, the item's own}
+            const uint32_t* ids = prev ? pp->ids : mp->ids;
+            uint32_t* ax = reinterpret_cast<uint32_t*>(hi + L.aux);
             for (int i = 0; i < n; i++, ax += 4) {
-                const int row = prev ? (rows ? rows[i] : -1) : i;
-                // (prev_weights: uh_track_pose_stereo's weight of a previous-frame item outside the local map)
-                const float w = prev ? (row >= 0 ? (weights_by_row ? weights_by_row[row] : 1.f) : (prev_weights ? prev_weights[i] : 1.f)) : (weights ? weights[i] : 1.f);
+                const int row = !prev ? i : trk->rows ? trk->rows[i] : -1;
+                const float w = row >= 0 ? (trk->map_weight ? trk->map_weight[row] : 1.f) : (trk->prev_weight ? trk->prev_weight[i] : 1.f);
                 ax[0] = ids[i]; std::memcpy(ax + 1, &row, 4); std::memcpy(ax + 2, &w, 4); ax[3] = 0;
             }
         }
-        float* rec = reinterpret_cast<float*>(hi + o_pos);
+        float* rec = reinterpret_cast<float*>(hi + L.rec);
         for (int i = 0; i < n; i++, rec += 16) {
             rec[0] = pos3d[3 * i]; rec[1] = pos3d[3 * i + 1]; rec[2] = pos3d[3 * i + 2];
-            if (prev) { std::memcpy(rec + 3, octave + i, 4); rec[4] = rec[5] = rec[6] = rec[7] = 0.f; }
-            else { rec[3] = normal[3 * i]; rec[4] = normal[3 * i + 1]; rec[5] = normal[3 * i + 2]; rec[6] = mn_dist[i]; rec[7] = mx_dist[i]; }
+            if (prev) { std::memcpy(rec + 3, pp->octave + i, 4); rec[4] = rec[5] = rec[6] = rec[7] = 0.f; }
+            else { rec[3] = mp->normal[3 * i]; rec[4] = mp->normal[3 * i + 1]; rec[5] = mp->normal[3 * i + 2]; rec[6] = mp->min_dist[i]; rec[7] = mp->max_dist[i]; }
             std::memcpy(rec + 8, desc + 32 * (size_t)i, 32);
         }
         std::atomic_thread_fence(std::memory_order_release);
@@ -1040,10 +1046,10 @@ int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn*
     if (pm_timing) fprintf(stderr, "projmatch%s: packing %d records %.1f us\n", prev ? "_prev" : "", n, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_pack0).count());
     PmPoints P;
     P.n = n;
-    P.rec = reinterpret_cast<const uint4*>(S.h_in.dev<char>() + o_pos);   // (read by the kernel where they lie: every wave fetches its own candidate once)
-    P.best_kp = (int*)(base + o_bk); P.best_dist = (float*)(base + o_bd); P.visible = (unsigned char*)(base + o_vis);
-    P.pos_out = pos_out;
-    P.aux_in = reinterpret_cast<const uint4*>(S.h_in.dev<char>() + o_pos + 64 * (size_t)n); P.aux_out = aux_out;
+    P.rec = reinterpret_cast<const uint4*>(S.h_in.dev<char>() + L.rec);   // (read by the kernel where they lie: every wave fetches its own candidate once)
+    P.best_kp = (int*)(base + L.bk); P.best_dist = (float*)(base + L.bd); P.visible = (unsigned char*)(base + L.vis);
+    P.pos_out = trk ? trk->pos_out : nullptr;
+    P.aux_in = reinterpret_cast<const uint4*>(S.h_in.dev<char>() + L.aux); P.aux_out = trk ? trk->aux_out : nullptr;
     PmPose ps{};
     if (pose_f2g) {
         const float* T = pose_f2g;
@@ -1064,7 +1070,7 @@ int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn*
         const int gpw = std::min(kGroupsMax, std::max(4, uh_div_up(n, ncu)));
         const size_t stack_bytes = (size_t)levels * gpw * 24 + (size_t)kCandCap * gpw * 8 + 64;
         const size_t tree_bytes = (((size_t)n_nodes * sizeof(KdNodeDev) + 15) & ~(size_t)15) + 16 * (size_t)h->n_kpts;
-        static const bool no_lds = getenv("UH_PROJMATCH_NO_LDS") != nullptr;   // env: test knob for the big-frame path
+        const bool no_lds = getenv("UH_PROJMATCH_NO_LDS") != nullptr;   // env: test knob for the big-frame path (read per call: tests set it within a process)
         const bool in_lds = tree_bytes + stack_bytes <= kLdsBudget && !no_lds;
         const size_t lds = stack_bytes + (in_lds ? tree_bytes : 0);
         if (!h->attr_set) {
@@ -1075,10 +1081,10 @@ int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn*
             h->attr_set = true;
         }
         const dim3 grid(std::min(uh_div_up(n, gpw), kPmMaxBlocks));
-        int* d_ovf = (int*)(base + o_ovf);
+        int* d_ovf = (int*)base;
         const unsigned long long word = ++h->seq;
-        const PmPublish pub{reinterpret_cast<unsigned*>(base + 128), reinterpret_cast<const unsigned long long*>(base + o_bk), reinterpret_cast<unsigned long long*>(S.h_out.dev<char>() + 64),
-                            (unsigned)(out_bytes / 8), S.h_out.dev<unsigned long long>(), word};
+        const PmPublish pub{reinterpret_cast<unsigned*>(base + 128), reinterpret_cast<const unsigned long long*>(base + L.bk), reinterpret_cast<unsigned long long*>(S.h_out.dev<char>() + 64),
+                            (unsigned)((L.end - L.bk) / 8), S.h_out.dev<unsigned long long>(), word};
         const bool lane_stack = levels <= kGroup;
 #define UH_PM_LAUNCH(A, B, C) UH_LAUNCH(h->ctx, (projmatch_kernel<A, B, C>), grid, dim3(gpw * kGroup), lds, h->fr, P, ps, min_desc_dist, max_repj_dist, n_nodes, levels, d_ovf, pub, dyn)
         if (lane_stack) {
@@ -1093,8 +1099,7 @@ int match_enqueue(uh_projmatch* h, int slot, const float* pose_f2g, const PmDyn*
     }
     UH_HIP_CHECK(hipGetLastError());
     pend->n = n; pend->slot = slot; pend->prev = prev;
-    pend->d_best_kp = P.best_kp; pend->d_best_dist = P.best_dist; pend->d_rec = reinterpret_cast<const float*>(P.rec);
-    pend->o_bk = o_bk; pend->o_bd = o_bd; pend->o_vis = o_vis;
+    pend->d_best_kp = P.best_kp; pend->d_best_dist = P.best_dist;
     return UH_OK;
 }
 
@@ -1115,30 +1120,40 @@ int match_collect(uh_projmatch* h, const PmPending& pd, const char* what, const 
         fprintf(stderr, "projmatch%s workgroup 0 cycles: stage %lld  visibility+walk %lld (group 0: %lld loop iterations, %lld leaves)  final drain (%lld hits) %lld  tail %lld  total %lld\n",
                 pd.prev ? "_prev" : "", c[1] - c[0], c[2] - c[1], c[6], c[7], c[5], c[3] - c[2], c[4] - c[3], c[4] - c[0]);
     }
+    const PmSlotLayout L = pm_slot_layout(pd.n);
     const char* ho = S.h_out.host<char>() + 64;
-    const int n = pd.n;
     const int* bk = (const int*)ho;
-    const float* bd = (const float*)(ho + (pd.o_bd - pd.o_bk));
-    const unsigned char* vis = (const unsigned char*)(ho + (pd.o_vis - pd.o_bk));
+    const float* bd = (const float*)(ho + (L.bd - L.bk));
+    const unsigned char* vis = (const unsigned char*)(ho + (L.vis - L.bk));
     const int ovf = *reinterpret_cast<const int*>(S.h_out.host<char>() + 8);
     UH_REQUIRE(!ovf, "%s: kd-tree walk stack overflow", what);
-    if (best_kp_out) std::memcpy(best_kp_out, bk, 4 * (size_t)n);
-    if (best_dist_out) std::memcpy(best_dist_out, bd, 4 * (size_t)n);
-    if (visible_out) std::memcpy(visible_out, vis, (size_t)n);
+    if (best_kp_out) std::memcpy(best_kp_out, bk, 4 * (size_t)pd.n);
+    if (best_dist_out) std::memcpy(best_dist_out, bd, 4 * (size_t)pd.n);
+    if (visible_out) std::memcpy(visible_out, vis, (size_t)pd.n);
     if (bk_out) *bk_out = bk;
     if (bd_out) *bd_out = bd;
     return UH_OK;
 }
 
-// one implementation behind uh_projmatch_match (octave == nullptr) and uh_projmatch_match_prev (normal/min/max == nullptr)
-int match_common(uh_projmatch* h, const float* pose_f2g, int n, const uint32_t* ids, const float* pos3d, const float* normal,
-                 const float* mn_dist, const float* mx_dist, const uint8_t* desc, const int32_t* octave, float min_desc_dist,
+// one implementation behind uh_projmatch_match (mp) and uh_projmatch_match_prev (pp), their checks included (`what`: the entry's name)
+int match_common(const char* what, uh_projmatch* h, const float* pose_f2g, const uh_map_points* mp, const uh_prev_points* pp, float min_desc_dist,
                  float max_repj_dist, uh_dmatch* matches_out, int32_t cap, int32_t* best_kp_out, float* best_dist_out, uint8_t* visible_out) {
+    const int n = mp ? mp->n : pp ? pp->n : -1;
+    UH_REQUIRE(h && h->have_frame, "%s: no frame set (call uh_projmatch_set_frame first)", what);
+    UH_REQUIRE(pose_f2g && n >= 0, "%s: NULL / negative argument", what);
+    UH_REQUIRE(max_repj_dist > 0, "%s: maxRepjDist must be > 0 (a non-positive radius turns the reference's search into an unbounded one)", what);
+    if (n == 0) return 0;
+    if (mp) UH_REQUIRE(mp->ids && mp->pos3d && mp->normal && mp->min_dist && mp->max_dist && mp->desc, "%s: map point arrays missing", what);
+    else UH_REQUIRE(pp->ids && pp->pos3d && pp->octave && pp->desc, "%s: point arrays missing", what);
+    UH_REQUIRE(matches_out && cap >= 0, "%s: output buffer missing", what);
+    for (int i = 0; pp && i < n; i++)   // Frame::scaleFactors[octave] (system.cpp:6130): out of range is undefined in the reference
+        UH_REQUIRE(pp->octave[i] >= 0 && pp->octave[i] < h->n_levels, "%s: octave %d of item %d outside [0,%d)", what, pp->octave[i], i, h->n_levels);
     PmPending pd;
-    int rc = match_enqueue(h, 0, pose_f2g, nullptr, n, pos3d, normal, mn_dist, mx_dist, desc, octave, min_desc_dist, max_repj_dist, &pd);
+    int rc = match_enqueue(h, 0, pose_f2g, nullptr, mp, pp, min_desc_dist, max_repj_dist, &pd);
     if (rc) return rc;
     const int* bk = nullptr; const float* bd = nullptr;
     if ((rc = match_collect(h, pd, "uh_projmatch_match", &bk, &bd, best_kp_out, best_dist_out, visible_out))) return rc;
+    const uint32_t* ids = pp ? pp->ids : mp->ids;
     std::vector<uh_dmatch>& mm = h->mm;
     mm.clear();
     mm.reserve(n);
@@ -1157,28 +1172,12 @@ extern "C" {
 
 int uh_projmatch_match(uh_projmatch* h, const float* pose_f2g, const uh_map_points* mp, float min_desc_dist, float max_repj_dist,
                        uh_dmatch* matches_out, int32_t cap, int32_t* best_kp_out, float* best_dist_out, uint8_t* visible_out) {
-    UH_REQUIRE(h && h->have_frame, "uh_projmatch_match: no frame set (call uh_projmatch_set_frame first)");
-    UH_REQUIRE(pose_f2g && mp && mp->n >= 0, "uh_projmatch_match: NULL / negative argument");
-    UH_REQUIRE(max_repj_dist > 0, "uh_projmatch_match: maxRepjDist must be > 0 (a non-positive radius turns the reference's search into an unbounded one)");
-    if (mp->n == 0) return 0;
-    UH_REQUIRE(mp->ids && mp->pos3d && mp->normal && mp->min_dist && mp->max_dist && mp->desc, "uh_projmatch_match: map point arrays missing");
-    UH_REQUIRE(matches_out && cap >= 0, "uh_projmatch_match: output buffer missing");
-    return match_common(h, pose_f2g, mp->n, mp->ids, mp->pos3d, mp->normal, mp->min_dist, mp->max_dist, mp->desc, nullptr, min_desc_dist,
-                        max_repj_dist, matches_out, cap, best_kp_out, best_dist_out, visible_out);
+    return match_common("uh_projmatch_match", h, pose_f2g, mp, nullptr, min_desc_dist, max_repj_dist, matches_out, cap, best_kp_out, best_dist_out, visible_out);
 }
 
 int uh_projmatch_match_prev(uh_projmatch* h, const float* pose_f2g, const uh_prev_points* pp, float min_desc_dist, float max_repj_dist,
                             uh_dmatch* matches_out, int32_t cap, int32_t* best_kp_out, float* best_dist_out) {
-    UH_REQUIRE(h && h->have_frame, "uh_projmatch_match_prev: no frame set (call uh_projmatch_set_frame first)");
-    UH_REQUIRE(pose_f2g && pp && pp->n >= 0, "uh_projmatch_match_prev: NULL / negative argument");
-    UH_REQUIRE(max_repj_dist > 0, "uh_projmatch_match_prev: maxRepjDist must be > 0 (a non-positive radius turns the reference's search into an unbounded one)");
-    if (pp->n == 0) return 0;
-    UH_REQUIRE(pp->ids && pp->pos3d && pp->octave && pp->desc, "uh_projmatch_match_prev: point arrays missing");
-    UH_REQUIRE(matches_out && cap >= 0, "uh_projmatch_match_prev: output buffer missing");
-    for (int i = 0; i < pp->n; i++)   // Frame::scaleFactors[octave] (system.cpp:6130): out of range is undefined in the reference
-        UH_REQUIRE(pp->octave[i] >= 0 && pp->octave[i] < h->n_levels, "uh_projmatch_match_prev: octave %d of item %d outside [0,%d)", pp->octave[i], i, h->n_levels);
-    return match_common(h, pose_f2g, pp->n, pp->ids, pp->pos3d, nullptr, nullptr, nullptr, pp->desc, pp->octave, min_desc_dist,
-                        max_repj_dist, matches_out, cap, best_kp_out, best_dist_out, nullptr);
+    return match_common("uh_projmatch_match_prev", h, pose_f2g, nullptr, pp, min_desc_dist, max_repj_dist, matches_out, cap, best_kp_out, best_dist_out, nullptr);
 }
 
 }  // extern "C"

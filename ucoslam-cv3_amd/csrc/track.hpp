@@ -9,7 +9,7 @@
 //   :6913-6954   the first matches + the new ones, filter_ambiguous_query over the union, per-match look-ups, PnPSolver::solvePnp (uh_pnp_solve)
 // Called one after the other through the C ABI the four operators cost four host round trips (launch latency + completion word + unpacking +
 // the host's look-ups in between: ~55 of the frame's ~430 us were no kernel's).  Here the host stages both candidate sets, enqueues
-// SIX launches on the context stream and waits once; what the host did between the calls runs on the device:
+// SEVEN launches on the context stream and waits once; what the host did between the calls runs on the device:
 //   projmatch_kernel<prev>  ->  track_select_kernel (matches in item order, filter_ambiguous_query, look-ups for the solve)
 //   -> pnp_solve_kernel (match count from device memory; its last thread also takes the decision: pose / radius of the map search)
 //   -> projmatch_kernel<map> (pose and radius read from device memory)  ->  track_select_kernel (the seen points' hits dropped, its own
@@ -26,8 +26,8 @@
 
 namespace uh {
 int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec,
-                    const float* d_depth = nullptr, float bl = 0.f);
+                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl);
+int pnp_reserve(uh_pnp* p, int n_cap, bool stereo);
 uh_ctx* pnp_ctx(uh_pnp* p);
 }
 
@@ -235,8 +235,8 @@ __global__ __launch_bounds__(kTrkThreads) void track_publish_kernel(TrkPublish p
 }  // namespace
 
 struct uh_track_state {
-    uh::DevBuf d;          // header | poses | PmDyn | lists | solver arrays | scratch
-    uh::MappedBuf h_par;   // pinned: [completion word | pose0 | intr | inv sigma per level | candidate ids | prev_map_row | map weights]
+    uh::DevBuf d;          // header | poses | PmDyn | lists | solver arrays | scratch (TrkLayout)
+    uh::MappedBuf h_par;   // pinned, read by the launches in place: [completion word | pose0 | intr | inv sigma per level | depth per keypoint]
     uh::MappedBuf h_out;   // pinned: the results
     unsigned long long seq = 0;
     bool attr_set = false;
@@ -247,8 +247,39 @@ uh_projmatch::~uh_projmatch() { delete track; }
 
 namespace {
 
-// uh_track_pose (sx == NULL) and uh_track_pose_stereo
-int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, uh_track_result* r) {
+// One call's list capacities and the byte offsets of uh_track_state's blocks (uh::Layout, 256-byte regions).  The device block begins with
+// the results, laid out as the pinned result block, which is that prefix; the parameter block has 64-byte regions behind the completion word.
+struct TrkLayout {
+    int cap1, cap2, capa, capn;   // the first search's list, the second's, the union; capn: a filtered list holds one match per keypoint at most
+    size_t hdr, pose1, pose2, m1, bad1, m2, ma, bada, out_bytes;
+    size_t pose_map, dyn, src1, src2, srca, p3d, kp, isg, wgt, sa, sb, pos_prev, pos_map, aux_prev, aux_map, dep_kp, dep, seen, d_bytes;
+    size_t par_pose0, par_intr, par_isl, par_dep, par_bytes;
+};
+
+TrkLayout trk_layout(int np, int nm, int nk, bool stereo) {
+    TrkLayout L;
+    L.cap1 = std::max(np, 1); L.cap2 = std::max(nm, 1); L.capa = std::max(np + nm, 1); L.capn = std::min(L.capa, std::max(nk, 1));
+    const size_t c1 = L.cap1, c2 = L.cap2, ca = L.capa;
+    uh::Layout d;
+    L.hdr = d.take<int>(kTrkHdrInts); L.pose1 = d.take<float>(16); L.pose2 = d.take<float>(16);
+    L.m1 = d.take<uh_dmatch>(c1); L.bad1 = d.take<unsigned char>(c1); L.m2 = d.take<uh_dmatch>(c2); L.ma = d.take<uh_dmatch>(ca); L.bada = d.take<unsigned char>(ca);
+    L.out_bytes = d.off;
+    L.pose_map = d.take<float>(16); L.dyn = d.take<PmDyn>(1); L.src1 = d.take<int>(c1); L.src2 = d.take<int>(c2); L.srca = d.take<int>(ca);
+    L.p3d = d.take<float>(3 * ca); L.kp = d.take<float>(2 * ca); L.isg = d.take<float>(ca); L.wgt = d.take<float>(ca); L.sa = d.take<TrkElem>(ca); L.sb = d.take<TrkElem>(ca);
+    L.pos_prev = d.take<float4>(c1); L.pos_map = d.take<float4>(c2); L.aux_prev = d.take<uint4>(c1); L.aux_map = d.take<uint4>(c2);
+    L.dep_kp = d.take<float>(stereo ? std::max(nk, 1) : 0); L.dep = d.take<float>(stereo ? ca : 0); L.seen = d.take<unsigned char>(c2);
+    L.d_bytes = d.take<char>(0);
+    uh::Layout p{64};
+    L.par_pose0 = p.take<float>(16, 64); L.par_intr = p.take<float>(4, 64); L.par_isl = p.take<float>(16, 64); L.par_dep = p.take<float>(stereo ? nk : 0, 64);
+    L.par_bytes = p.off;
+    return L;
+}
+
+// a block's base + offset, as whatever pointer it is assigned to
+struct TrkAt { char* p; template <typename T> operator T*() const { return reinterpret_cast<T*>(p); } };
+
+// Every check of uh_track_pose (sx == NULL) and uh_track_pose_stereo, before anything is staged
+int track_validate(const uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, const uh_track_result* r) {
     UH_REQUIRE(h && pnp && a && r, "uh_track_pose: NULL argument");
     UH_REQUIRE(h->have_frame && h->dev, "uh_track_pose: needs a device-resident frame (uh_orb_extract_frame_dev + uh_projmatch_set_frame_dev)");
     UH_REQUIRE(a->pose0 && a->intr4 && a->prev && a->map && a->inv_sigma_levels, "uh_track_pose: NULL input");
@@ -261,138 +292,116 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     if (nm) UH_REQUIRE(a->map->ids && a->map->pos3d && a->map->normal && a->map->min_dist && a->map->max_dist && a->map->desc, "uh_track_pose: map point arrays missing");
     for (int i = 0; i < np; i++)
         UH_REQUIRE(a->prev->octave[i] >= 0 && a->prev->octave[i] < h->n_levels, "uh_track_pose: octave %d of item %d outside [0,%d)", a->prev->octave[i], i, h->n_levels);
-    const bool stereo = sx && sx->depth;
-    if (sx) {
-        if (a->prev_map_row)
-            for (int i = 0; i < np; i++)
-                UH_REQUIRE(a->prev_map_row[i] >= -1 && a->prev_map_row[i] < nm, "uh_track_pose_stereo: prev_map_row %d of item %d outside [-1,%d)", a->prev_map_row[i], i, nm);
-        if (stereo) {
-            bool any = false;
-            for (int k = 0; k < nk && !any; k++) any = !(sx->depth[k] <= 0.f);
-            UH_REQUIRE(!any || sx->bl > 0.f, "uh_track_pose_stereo: stereo keypoints need a baseline > 0 (bl = %g)", (double)sx->bl);
-        }
-    }
+    if (a->prev_map_row)   // (a row indexes map_weight on the host and the map search's positions on the device)
+        for (int i = 0; i < np; i++)
+            UH_REQUIRE(a->prev_map_row[i] >= -1 && a->prev_map_row[i] < nm, "%s: prev_map_row %d of item %d outside [-1,%d)", sx ? "uh_track_pose_stereo" : "uh_track_pose",
+                       a->prev_map_row[i], i, nm);
+    const bool any_depth = sx && sx->depth && std::any_of(sx->depth, sx->depth + nk, [](float d) { return !(d <= 0.f); });
+    UH_REQUIRE(!any_depth || sx->bl > 0.f, "uh_track_pose_stereo: stereo keypoints need a baseline > 0 (bl = %g)", (double)sx->bl);
     UH_REQUIRE(r->matches_prev && r->bad_prev && r->matches_map && r->matches_all && r->bad_all, "uh_track_pose: output buffers missing");
     UH_REQUIRE(h->ctx == uh::pnp_ctx(pnp), "uh_track_pose: matcher and solver belong to different contexts");
+    return UH_OK;
+}
+
+// A return between the first launch and the completion wait: the launches in flight still read the pinned blocks and slots the next call
+// rewrites — wait for them, and have both slots' status words cleared again.  A failed wait does not synchronise (a hung launch would
+// block the host for good): it only clears the words.
+struct TrkInFlight {
+    uh_projmatch* h;
+    bool sync = true, done = false;
+    ~TrkInFlight() { if (!done) { if (sync) (void)hipStreamSynchronize(h->ctx->stream); h->slot[0].ovf_zeroed = h->slot[1].ovf_zeroed = false; } }
+};
+
+// the select launch: its working lists in LDS while two lists of capa elements fit beside the per-keypoint table
+int select_launch(uh_projmatch* h, const TrkSelect& s, int capa) {
+    const size_t lds = 2 * sizeof(TrkElem) * (size_t)capa;
+    const bool in_lds = lds <= 120 * 1024;
+    if (in_lds && !h->track->attr_set) {
+        UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(track_select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
+        h->track->attr_set = true;
+    }
+    if (in_lds) UH_LAUNCH(h->ctx, track_select_kernel<true>, dim3(1), dim3(kTrkThreads), lds, s, capa);
+    else UH_LAUNCH(h->ctx, track_select_kernel<false>, dim3(1), dim3(kTrkThreads), 0, s, capa);
+    return UH_OK;
+}
+
+// uh_track_pose (sx == NULL) and uh_track_pose_stereo
+int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, uh_track_result* r) {
+    int rc;
+    if ((rc = track_validate(h, pnp, a, sx, r))) return rc;
     UH_HIP_CHECK(hipSetDevice(h->ctx->device));
     if (!h->track) h->track = new uh_track_state();
     uh_track_state& T = *h->track;
-    int rc;
-    const int cap1 = std::max(np, 1), cap2 = std::max(nm, 1), capa = std::max(np + nm, 1), capn = std::min(capa, std::max(nk, 1));   // (a filtered list holds one match per keypoint at most)
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // ---- device block
-    size_t o = 0;
-    const size_t o_hdr = o; o = al(o + 4 * kTrkHdrInts);
-    const size_t o_pose1 = o; o += 64; const size_t o_posem = o; o += 64; const size_t o_pose2 = o; o += 64;
-    const size_t o_dyn = o; o = al(o + sizeof(PmDyn));
-    const size_t o_m1 = o; o = al(o + 16 * (size_t)cap1); const size_t o_src1 = o; o = al(o + 4 * (size_t)cap1); const size_t o_bad1 = o; o = al(o + (size_t)cap1);
-    const size_t o_m2 = o; o = al(o + 16 * (size_t)cap2); const size_t o_src2 = o; o = al(o + 4 * (size_t)cap2);
-    const size_t o_ma = o; o = al(o + 16 * (size_t)capa); const size_t o_srca = o; o = al(o + 4 * (size_t)capa); const size_t o_bada = o; o = al(o + (size_t)capa);
-    const size_t o_p3d = o; o = al(o + 12 * (size_t)capa); const size_t o_kp = o; o = al(o + 8 * (size_t)capa); const size_t o_isg = o; o = al(o + 4 * (size_t)capa);
-    const size_t o_wgt = o; o = al(o + 4 * (size_t)capa);
-    const size_t o_sa = o; o = al(o + sizeof(TrkElem) * (size_t)capa); const size_t o_sb = o; o = al(o + sizeof(TrkElem) * (size_t)capa);
-    const size_t o_posp = o; o = al(o + 16 * (size_t)cap1); const size_t o_posm = o; o = al(o + 16 * (size_t)cap2);
-    const size_t o_auxp = o; o = al(o + 16 * (size_t)cap1); const size_t o_auxm = o; o = al(o + 16 * (size_t)cap2);
-    const size_t o_depk = o; o = al(o + (stereo ? 4 * (size_t)std::max(nk, 1) : 0)); const size_t o_dep = o; o = al(o + (stereo ? 4 * (size_t)capa : 0));
-    const size_t o_seen = o; o = al(o + (size_t)cap2);
-    if ((rc = T.d.reserve(o))) return rc;
-    char* D = T.d.as<char>();
-    // ---- pinned parameter block (read by the launches in place)
-    size_t q = 64;
-    const size_t q_pose0 = q; q += 64; const size_t q_intr = q; q += 64; const size_t q_isl = q; q += 64;
-    const size_t q_dep = q; q += stereo ? 4 * (size_t)nk : 0;
-    if ((rc = T.h_par.reserve(q))) return rc;   // (the previous call's launches are complete: its results were awaited)
+    const int np = a->prev->n, nm = a->map->n, nk = h->n_kpts;
+    const bool stereo = sx && sx->depth;
+    const TrkLayout L = trk_layout(np, nm, nk, stereo);
+    static const bool trk_clk = getenv("UH_TRK_CLK") != nullptr;
+    // ---- every buffer of the call before its first launch (a buffer that grows is freed, which synchronises the device)
+    if ((rc = T.d.reserve(L.d_bytes)) || (rc = T.h_par.reserve(L.par_bytes)) || (rc = T.h_out.reserve(L.out_bytes))) return rc;
+    if ((np && (rc = match_reserve(h, 0, np))) || (nm && (rc = match_reserve(h, 1, nm)))) return rc;
+    if ((rc = uh::pnp_reserve(pnp, L.capn, stereo)) || (trk_clk && (rc = T.d_clk.reserve(16 * 8)))) return rc;
+    auto at = [D = T.d.as<char>()](size_t o) { return TrkAt{D + o}; };
+    auto par = [dp = T.h_par.dev<char>()](size_t o) { return TrkAt{dp + o}; };
+    auto out = [dout = T.h_out.dev<char>()](size_t o) { return TrkAt{dout + o}; };
+    // ---- the pinned parameters (the previous call's launches are complete: its results were awaited, or its failure drained the stream)
     char* hp = T.h_par.host<char>();
-    char* dp = T.h_par.dev<char>();
-    std::memcpy(hp + q_pose0, a->pose0, 64);
-    std::memcpy(hp + q_intr, a->intr4, 16);
-    std::memcpy(hp + q_isl, a->inv_sigma_levels, 4 * (size_t)a->n_levels);
-    if (stereo && nk) std::memcpy(hp + q_dep, sx->depth, 4 * (size_t)nk);
-    // ---- pinned result block
-    size_t w = 0;
-    const size_t w_hdr = w; w = al(w + 4 * kTrkHdrInts); const size_t w_pose1 = w; w += 64; const size_t w_pose2 = w; w = al(w + 64);
-    const size_t w_m1 = w; w = al(w + 16 * (size_t)cap1); const size_t w_bad1 = w; w = al(w + (size_t)cap1);
-    const size_t w_m2 = w; w = al(w + 16 * (size_t)cap2);
-    const size_t w_ma = w; w = al(w + 16 * (size_t)capa); const size_t w_bada = w; w = al(w + (size_t)capa);
-    if ((rc = T.h_out.reserve(w))) return rc;
-    hipStream_t st = h->ctx->stream;
+    std::memcpy(hp + L.par_pose0, a->pose0, 64);
+    std::memcpy(hp + L.par_intr, a->intr4, 16);
+    std::memcpy(hp + L.par_isl, a->inv_sigma_levels, 4 * (size_t)a->n_levels);
+    if (stereo && nk) std::memcpy(hp + L.par_dep, sx->depth, 4 * (size_t)nk);
     std::atomic_thread_fence(std::memory_order_release);   // (every header field the publish reads is written by one of the launches below)
-
-    const float4* kp_xyo = h->dev->kd_in();
-    int* hdr = reinterpret_cast<int*>(D + o_hdr);
+    int* hdr = at(L.hdr);
+    // the select launch behind search k (0: the previous frame's items, 1: the local map's points; the second also forms the union)
+    auto select_args = [&](int k, const PmPending& pd) {
+        TrkSelect s{};
+        s.nB = k ? nm : np; s.bk = pd.d_best_kp; s.bd = pd.d_best_dist; s.aux = at(k ? L.aux_map : L.aux_prev); s.map_kind = k;
+        if (k) { s.carry = at(L.m1); s.carry_src = at(L.src1); s.carry_cap = L.cap1; }
+        s.seen = at(L.seen); s.n_map_rows = nm;
+        s.hdr = hdr; s.fresh_n_slot = k ? kTrkN2 : kTrkN1; s.final_n_slot = k ? kTrkNA : kTrkN1;
+        s.fresh_out = at(k ? L.m2 : L.m1); s.fresh_src = at(k ? L.src2 : L.src1);
+        if (k) { s.final_out = at(L.ma); s.final_src = at(L.srca); }
+        s.pos_prev = at(L.pos_prev); s.pos_map = at(L.pos_map); s.aux_prev = at(L.aux_prev); s.aux_map = at(L.aux_map);
+        s.prefer_map_row = k;   // (first solve: the candidate's own position)
+        s.kp_xyo = h->dev->kd_in(); s.inv_sigma_lv = par(L.par_isl); s.n_levels = a->n_levels;
+        s.p3d = at(L.p3d); s.kp = at(L.kp); s.isg = at(L.isg); s.wgt = at(L.wgt);
+        s.n_kpts = nk; s.scratch_a = at(L.sa); s.scratch_b = at(L.sb);
+        if (trk_clk) s.clk = T.d_clk.as<long long>() + 8 * k;
+        if (stereo) { s.dep_kp = at(L.dep_kp); s.dep = at(L.dep); }
+        if (stereo && !k) s.dep_src = par(L.par_dep);   // (the first select launch leaves the frame's depths in dep_kp)
+        return s;
+    };
+    const float bl = stereo ? sx->bl : 0.f;
+    TrkInFlight in_flight{h};
     // ---- 1: the search against the previous frame (slot 0), its list and look-ups, the first solve
     PmPending pd1, pd2;
     if (np) {
-        if ((rc = match_enqueue(h, 0, a->pose0, nullptr, np, a->prev->pos3d, nullptr, nullptr, nullptr, a->prev->desc, a->prev->octave, a->prev_min_desc_dist, a->prev_max_repj_dist, &pd1,
-                                reinterpret_cast<float4*>(D + o_posp), a->prev->ids, a->prev_map_row, nullptr, a->map_weight, reinterpret_cast<uint4*>(D + o_auxp),
-                                sx ? sx->prev_weight : nullptr))) return rc;
+        const PmTrack t{a->prev_map_row, a->map_weight, sx ? sx->prev_weight : nullptr, at(L.pos_prev), at(L.aux_prev)};
+        if ((rc = match_enqueue(h, 0, a->pose0, nullptr, nullptr, a->prev, a->prev_min_desc_dist, a->prev_max_repj_dist, &pd1, &t))) return rc;
     }
     // (the map candidates are staged now, while the device works on the first search: slot 1 has its own pinned block)
-    TrkSelect s1{};
-    s1.nB = np; s1.bk = pd1.d_best_kp; s1.bd = pd1.d_best_dist; s1.aux = reinterpret_cast<const uint4*>(D + o_auxp); s1.map_kind = 0;
-    s1.carry = nullptr; s1.hdr = hdr; s1.fresh_n_slot = kTrkN1; s1.final_n_slot = kTrkN1;
-    s1.fresh_out = reinterpret_cast<uh_dmatch*>(D + o_m1); s1.fresh_src = reinterpret_cast<int*>(D + o_src1); s1.final_out = nullptr; s1.final_src = nullptr;
-    s1.pos_prev = reinterpret_cast<const float4*>(D + o_posp); s1.pos_map = reinterpret_cast<const float4*>(D + o_posm);
-    s1.aux_prev = reinterpret_cast<const uint4*>(D + o_auxp); s1.aux_map = reinterpret_cast<const uint4*>(D + o_auxm); s1.prefer_map_row = 0;
-    s1.kp_xyo = kp_xyo; s1.inv_sigma_lv = reinterpret_cast<const float*>(dp + q_isl); s1.n_levels = a->n_levels;
-    s1.p3d = reinterpret_cast<float*>(D + o_p3d); s1.kp = reinterpret_cast<float*>(D + o_kp); s1.isg = reinterpret_cast<float*>(D + o_isg); s1.wgt = reinterpret_cast<float*>(D + o_wgt);
-    s1.n_kpts = nk; s1.scratch_a = reinterpret_cast<TrkElem*>(D + o_sa); s1.scratch_b = reinterpret_cast<TrkElem*>(D + o_sb);
-    static const bool trk_clk = getenv("UH_TRK_CLK") != nullptr;
-    if (trk_clk && !T.d_clk.p) { if ((rc = T.d_clk.reserve(16 * 8))) return rc; }
-    s1.clk = trk_clk ? T.d_clk.as<long long>() : nullptr;
-    s1.dep_src = stereo ? reinterpret_cast<const float*>(dp + q_dep) : nullptr; s1.dep_kp = stereo ? reinterpret_cast<float*>(D + o_depk) : nullptr;
-    s1.dep = stereo ? reinterpret_cast<float*>(D + o_dep) : nullptr;
-    s1.seen = reinterpret_cast<unsigned char*>(D + o_seen); s1.n_map_rows = nm;
-    const float bl = stereo ? sx->bl : 0.f;
-    // the select launches' working lists: in LDS while two lists of capa elements fit beside the per-keypoint table
-    const size_t sel_lds = 2 * sizeof(TrkElem) * (size_t)capa;
-    const bool sel_in_lds = sel_lds <= 120 * 1024;
-    if (sel_in_lds && !T.attr_set) {
-        UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(track_select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-        T.attr_set = true;
-    }
-    if (sel_in_lds) UH_LAUNCH(h->ctx, track_select_kernel<true>, dim3(1), dim3(kTrkThreads), sel_lds, s1, capa);
-    else UH_LAUNCH(h->ctx, track_select_kernel<false>, dim3(1), dim3(kTrkThreads), 0, s1, capa);
+    const TrkSelect s1 = select_args(0, pd1);
+    if ((rc = select_launch(h, s1, L.capa))) return rc;
     // (the decision — refined pose + small disc or predicted pose + wide radius — rides on the solve's last thread)
     static_assert(sizeof(PmDyn) == 17 * 4, "PmDyn is what pnp_decide writes");
-    PmDyn* dyn = reinterpret_cast<PmDyn*>(D + o_dyn);
-    const uh::PnpDecide dec{a->min_inliers, a->map_radius_tracked, a->map_radius_lost, reinterpret_cast<float*>(dyn), reinterpret_cast<float*>(D + o_posem), hdr + kTrkTracked};
-    if ((rc = uh::pnp_enqueue_dev(pnp, reinterpret_cast<const float*>(dp + q_pose0), reinterpret_cast<const float*>(dp + q_intr), std::min(cap1, capn), hdr + kTrkN1, s1.p3d, s1.kp, s1.isg, s1.wgt,
-                                  reinterpret_cast<float*>(D + o_pose1), reinterpret_cast<unsigned char*>(D + o_bad1), hdr + kTrkRes1, &dec, s1.dep, bl))) return rc;
+    const uh::PnpDecide dec{a->min_inliers, a->map_radius_tracked, a->map_radius_lost, at(L.dyn), at(L.pose_map), hdr + kTrkTracked};
+    if ((rc = uh::pnp_enqueue_dev(pnp, par(L.par_pose0), par(L.par_intr), std::min(L.cap1, L.capn), hdr + kTrkN1, s1.p3d, s1.kp, s1.isg, s1.wgt, at(L.pose1), at(L.bad1),
+                                  hdr + kTrkRes1, &dec, s1.dep, bl))) return rc;
     // ---- 2: the search of the local map at the decided pose / radius (slot 1), the union, the second solve
     if (nm) {
-        if ((rc = match_enqueue(h, 1, nullptr, dyn, nm, a->map->pos3d, a->map->normal, a->map->min_dist, a->map->max_dist, a->map->desc, nullptr, a->map_min_desc_dist, a->map_radius_tracked, &pd2,
-                                reinterpret_cast<float4*>(D + o_posm), a->map->ids, nullptr, a->map_weight, nullptr, reinterpret_cast<uint4*>(D + o_auxm)))) return rc;
+        const PmTrack t{nullptr, a->map_weight, nullptr, at(L.pos_map), at(L.aux_map)};
+        if ((rc = match_enqueue(h, 1, nullptr, at(L.dyn), a->map, nullptr, a->map_min_desc_dist, a->map_radius_tracked, &pd2, &t))) return rc;
     }
-    TrkSelect s2 = s1;
-    s2.nB = nm; s2.bk = pd2.d_best_kp; s2.bd = pd2.d_best_dist; s2.aux = reinterpret_cast<const uint4*>(D + o_auxm); s2.map_kind = 1;
-    s2.carry = reinterpret_cast<const uh_dmatch*>(D + o_m1); s2.carry_src = reinterpret_cast<const int*>(D + o_src1); s2.carry_cap = cap1;
-    s2.fresh_n_slot = kTrkN2; s2.final_n_slot = kTrkNA;
-    if (trk_clk) s2.clk = T.d_clk.as<long long>() + 8;
-    s2.fresh_out = reinterpret_cast<uh_dmatch*>(D + o_m2); s2.fresh_src = reinterpret_cast<int*>(D + o_src2); s2.final_out = reinterpret_cast<uh_dmatch*>(D + o_ma); s2.final_src = reinterpret_cast<int*>(D + o_srca);
-    s2.prefer_map_row = 1;
-    s2.dep_src = nullptr;   // (the first select launch left the frame's depths in dep_kp)
-    if (sel_in_lds) UH_LAUNCH(h->ctx, track_select_kernel<true>, dim3(1), dim3(kTrkThreads), sel_lds, s2, capa);
-    else UH_LAUNCH(h->ctx, track_select_kernel<false>, dim3(1), dim3(kTrkThreads), 0, s2, capa);
-    if ((rc = uh::pnp_enqueue_dev(pnp, reinterpret_cast<const float*>(D + o_posem), reinterpret_cast<const float*>(dp + q_intr), capn, hdr + kTrkNA, s2.p3d, s2.kp, s2.isg, s2.wgt,
-                                  reinterpret_cast<float*>(D + o_pose2), reinterpret_cast<unsigned char*>(D + o_bada), hdr + kTrkRes2, nullptr, s2.dep, bl))) return rc;
+    const TrkSelect s2 = select_args(1, pd2);
+    if ((rc = select_launch(h, s2, L.capa))) return rc;
+    if ((rc = uh::pnp_enqueue_dev(pnp, at(L.pose_map), par(L.par_intr), L.capn, hdr + kTrkNA, s2.p3d, s2.kp, s2.isg, s2.wgt, at(L.pose2), at(L.bada), hdr + kTrkRes2, nullptr,
+                                  s2.dep, bl))) return rc;
     // ---- 3: everything back in one block
-    char* ho = T.h_out.host<char>();
-    char* dout = T.h_out.dev<char>();
-    TrkPublish pb{};
-    pb.hdr = hdr; pb.pose1 = reinterpret_cast<const float*>(D + o_pose1); pb.pose2 = reinterpret_cast<const float*>(D + o_pose2);
-    pb.m1 = s1.fresh_out; pb.bad1 = reinterpret_cast<const unsigned char*>(D + o_bad1); pb.m2 = s2.fresh_out; pb.ma = s2.final_out; pb.bad2 = reinterpret_cast<const unsigned char*>(D + o_bada);
-    pb.cap1 = cap1; pb.cap2 = cap2; pb.capa = capa;
-    pb.h_hdr = reinterpret_cast<int*>(dout + w_hdr); pb.h_pose1 = reinterpret_cast<float*>(dout + w_pose1); pb.h_pose2 = reinterpret_cast<float*>(dout + w_pose2);
-    pb.h_m1 = reinterpret_cast<uh_dmatch*>(dout + w_m1); pb.h_bad1 = reinterpret_cast<unsigned char*>(dout + w_bad1); pb.h_m2 = reinterpret_cast<uh_dmatch*>(dout + w_m2);
-    pb.h_ma = reinterpret_cast<uh_dmatch*>(dout + w_ma); pb.h_bad2 = reinterpret_cast<unsigned char*>(dout + w_bada);
-    pb.host_done = T.h_par.dev<unsigned long long>(); pb.word = ++T.seq;
+    const TrkPublish pb{hdr, at(L.pose1), at(L.pose2), at(L.m1), at(L.bad1), at(L.m2), at(L.ma), at(L.bada), L.cap1, L.cap2, L.capa,   // (the pinned twins at the same offsets)
+                        out(L.hdr), out(L.pose1), out(L.pose2), out(L.m1), out(L.bad1), out(L.m2), out(L.ma), out(L.bada), T.h_par.dev<unsigned long long>(), ++T.seq};
     UH_LAUNCH(h->ctx, track_publish_kernel, dim3(1), dim3(kTrkThreads), 0, pb);
     UH_HIP_CHECK(hipGetLastError());
-    if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(hp), pb.word, st, "uh_track_pose"))) {
-        h->slot[0].ovf_zeroed = h->slot[1].ovf_zeroed = false;
-        return rc;
-    }
+    if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(hp), pb.word, h->ctx->stream, "uh_track_pose"))) { in_flight.sync = false; return rc; }
+    in_flight.done = true;
     h->upload_pending = false;
     if (trk_clk) {
         long long c[16];
@@ -404,21 +413,19 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
         }
     }
     // (both searches posted their own words and walk-overflow flags on the way: the stream is in order, they are long since visible)
-    for (int sl = 0; sl < 2; sl++) {
-        if ((sl == 0 && !np) || (sl == 1 && !nm)) continue;
-        const int ovf = *reinterpret_cast<const int*>(h->slot[sl].h_out.host<char>() + 8);
-        UH_REQUIRE(!ovf, "uh_track_pose: kd-tree walk stack overflow");
-    }
-    const int* hh = reinterpret_cast<const int*>(ho + w_hdr);
+    for (int sl = 0; sl < 2; sl++)
+        UH_REQUIRE(!(sl ? nm : np) || !*reinterpret_cast<const int*>(h->slot[sl].h_out.host<char>() + 8), "uh_track_pose: kd-tree walk stack overflow");
+    const char* ho = T.h_out.host<char>();
+    const int* hh = reinterpret_cast<const int*>(ho + L.hdr);
     const int n1 = hh[kTrkN1], n2 = hh[kTrkN2], na = hh[kTrkNA];
     UH_REQUIRE(n1 <= r->cap_prev && n2 <= r->cap_map && na <= r->cap_all, "uh_track_pose: %d / %d / %d matches do not fit the output buffers (%d / %d / %d)", n1, n2, na, r->cap_prev, r->cap_map, r->cap_all);
     r->n_prev = n1; r->n_map = n2; r->n_all = na; r->tracked = hh[kTrkTracked];
     r->inliers1 = hh[kTrkRes1]; r->inliers2 = hh[kTrkRes2];
     for (int i = 0; i < 4; i++) { r->iters1[i] = hh[kTrkRes1 + 1 + i]; r->iters2[i] = hh[kTrkRes2 + 1 + i]; }
-    std::memcpy(r->pose1, ho + w_pose1, 64); std::memcpy(r->pose2, ho + w_pose2, 64);
-    if (n1) { std::memcpy(r->matches_prev, ho + w_m1, 16 * (size_t)n1); std::memcpy(r->bad_prev, ho + w_bad1, (size_t)n1); }
-    if (n2) std::memcpy(r->matches_map, ho + w_m2, 16 * (size_t)n2);
-    if (na) { std::memcpy(r->matches_all, ho + w_ma, 16 * (size_t)na); std::memcpy(r->bad_all, ho + w_bada, (size_t)na); }
+    std::memcpy(r->pose1, ho + L.pose1, 64); std::memcpy(r->pose2, ho + L.pose2, 64);
+    if (n1) { std::memcpy(r->matches_prev, ho + L.m1, 16 * (size_t)n1); std::memcpy(r->bad_prev, ho + L.bad1, (size_t)n1); }
+    if (n2) std::memcpy(r->matches_map, ho + L.m2, 16 * (size_t)n2);
+    if (na) { std::memcpy(r->matches_all, ho + L.ma, 16 * (size_t)na); std::memcpy(r->bad_all, ho + L.bada, (size_t)na); }
     return UH_OK;
 }
 
