@@ -355,8 +355,10 @@ int uh_orb_debug_level(uh_orb* orb, int frame, int level, int which, uint8_t* ou
  *   obs     : one monocular EdgeSE3ProjectXYZ per (point, frame): undistorted keypoint (float x,y) and
  *             information scalar 1/scaleFactor[octave] (globaloptimizer_g2o.cpp:96-97,244)
  * Arithmetic is fp64 like g2o; poses agree with the reference within 1e-6 (se3 state), see DESIGN.md.
- * Monocular edges only.  Up to 64 non-fixed frames run the local-BA form (two launches per LM trial, reduced system in one
+ * Up to 64 non-fixed frames run the local-BA form (two launches per LM trial, reduced system in one
  * workgroup's LDS); more (global BA, up to 4096) run the wide form: sparse camera-pair lists, blocked dense LDL^T in HBM.
+ * Stereo / RGB-D observations (EdgeStereoSE3ProjectXYZ, typesg2o.h:327-409: three residual rows u, v, u_right) enter through the
+ * *_stereo entries below; such a problem runs the launch chain or the wide form (the persistent one-launch form is monocular).
  * ------------------------------------------------------------------------ */
 typedef struct uh_ba uh_ba;
 
@@ -452,6 +454,38 @@ int  uh_ba_form(uh_ba* ba, int* lanes_per_landmark_out);
 /* the per-observation chi2 is an extra of this ABI (GlobalOptimizer::getResults does not return it) and three quarters of the bytes the
  * optimisation kernel hands over: uh_ba_want_chi2(ba, 0) leaves it out from the next set_problem on (chi2_out must then be NULL) */
 int  uh_ba_want_chi2(uh_ba* ba, int on);
+
+/* ---- stereo / RGB-D observations (globaloptimizer_g2o.cpp:229-272).  Per observation the depth Frame::getDepth(kp): depth <= 0 is
+ * the monocular edge above; depth > 0 is a three-row edge with mbf = bl * fx and kp_ur = u - mbf / depth formed in float as the
+ * reference forms them, information I3 * inv_sigma, Huber width thHuber3D and outlier limit Chi3D (globaloptimizer_g2o.h:112-117).
+ * A problem in which no observation has depth > 0 takes exactly the monocular route of uh_ba_set_problem / _staged (same form, same
+ * kernels, same results).  With at least one, uh_ba_form reports 0 or 2; optimize / optimize_async / wait / get_results /
+ * get_pose_state / stop flag / want_chi2 work unchanged, uh_ba_results_view_get refuses as for every chain / wide problem.  A landmark
+ * with a single (three-row) observation is accepted (:142).  Refused with UH_EINVAL, nothing launched: stereo == NULL or a NULL
+ * array while n_obs > 0, a non-finite depth, depth > 0 on a frame whose baseline is not finite and positive, more than 4096 free
+ * keyframes.  uh_ba_solve_async has no stereo form. */
+typedef struct uh_ba_stereo {
+    const float* obs_depth;         /* n_obs: Frame::getDepth(kp); <= 0 -> monocular edge */
+    const float* frame_bl;          /* n_frames: Frame::imageParams.bl of that frame */
+    double huber_delta_3d;          /* <= 0 -> (double)(float)sqrt(7.815f) */
+    double chi2_threshold_3d;       /* <= 0 -> (double)7.815f */
+} uh_ba_stereo;
+
+typedef struct uh_ba_staging_stereo {   /* uh_ba_staging + the two stereo arrays (host memory owned by the optimiser) */
+    float*     poses_f2g;           /* cap_frames x 16 */
+    uint8_t*   fixed;               /* cap_frames */
+    float*     intr;                /* cap_frames x 4 */
+    float*     points;              /* cap_points x 3 */
+    uh_ba_obs* obs;                 /* cap_obs (24-byte records) */
+    float*     obs_depth;           /* cap_obs */
+    float*     frame_bl;            /* cap_frames */
+    int32_t    cap_frames, cap_points, cap_obs;
+} uh_ba_staging_stereo;
+
+int  uh_ba_set_problem_stereo(uh_ba* ba, const uh_ba_problem* problem, const uh_ba_stereo* stereo, const uh_ba_params* params);
+int  uh_ba_map_staging_stereo(uh_ba* ba, int n_frames, int n_points, int max_obs, uh_ba_staging_stereo* out);
+int  uh_ba_set_problem_staged_stereo(uh_ba* ba, int n_frames, int n_points, int n_obs, const uh_ba_params* params,
+                                     double huber_delta_3d, double chi2_threshold_3d);
 
 /* ------------------------------------------------------------------------
  * Bag of words — replaces fbow::Vocabulary::transform / fBow::score:

@@ -211,16 +211,28 @@ class GlobalOptimizer {
         staged_ = true;
         obs_keep_.assign(sink.st.obs, sink.st.obs + index_.n_obs);   // (getResults names the bad associations by these)
     }
+    // setParams on a map with stereo / RGB-D observations (Frame::getDepth > 0, :250-272): flatten_for_ba_stereo + the stereo staging block.
+    // The MapView also needs frame_baseline(f).  A map without any depth ends on the monocular route.
+    template <class MapView>
+    void setParamsStereo(const MapView& map, const ParamSet& p) {
+        StereoStagingSink sink(b_);
+        index_ = flatten_for_ba_stereo(map, p, sink);
+        uh_ba_params bp{p.nIters, 0.0, 0.0, 1.0f};
+        check(uh_ba_set_problem_staged_stereo(b_, (int)index_.frame_of.size(), (int)index_.point_of.size(), index_.n_obs, &bp, 0.0, 0.0));
+        staged_ = true;
+        obs_keep_.assign(sink.st.obs, sink.st.obs + index_.n_obs);
+    }
+    // ... and on flattened arrays with the stereo block beside them
+    void setParams(const uh_ba_problem& problem, const uh_ba_stereo& stereo, const ParamSet& p) {
+        uh_ba_params bp{p.nIters, 0.0, 0.0, 1.0f};
+        check(uh_ba_set_problem_stereo(b_, &problem, &stereo, &bp));
+        keep_flat(problem);
+    }
     // setParams on a map the caller has flattened already
     void setParams(const uh_ba_problem& problem, const ParamSet& p) {
         uh_ba_params bp{p.nIters, 0.0, 0.0, 1.0f};
         check(uh_ba_set_problem(b_, &problem, &bp));
-        staged_ = false;
-        obs_keep_.resize(problem.n_obs);
-        for (int e = 0; e < problem.n_obs; e++) obs_keep_[e] = uh_ba_obs{problem.obs_point[e], problem.obs_frame[e], 0.f, 0.f, 0.0};
-        index_ = FlatBAIndex{};
-        index_.n_obs = problem.n_obs;
-        K_ = problem.n_frames; P_ = problem.n_points;
+        keep_flat(problem);
     }
     void optimize(bool* stopASAP = nullptr) { check(uh_ba_optimize(b_, reinterpret_cast<const volatile uint8_t*>(stopASAP))); }
     // getResults(map) (:466-537): poses of the free frames, point coordinates, updatePointNormalAndDistances; fills getBadAssociations()
@@ -251,6 +263,14 @@ class GlobalOptimizer {
     const FlatBAIndex& index() const { return index_; }
     uh_ba* handle() const { return b_; }
    private:
+    void keep_flat(const uh_ba_problem& problem) {   // what getResults needs of a problem given as arrays
+        staged_ = false;
+        obs_keep_.resize(problem.n_obs);
+        for (int e = 0; e < problem.n_obs; e++) obs_keep_[e] = uh_ba_obs{problem.obs_point[e], problem.obs_frame[e], 0.f, 0.f, 0.0};
+        index_ = FlatBAIndex{};
+        index_.n_obs = problem.n_obs;
+        K_ = problem.n_frames; P_ = problem.n_points;
+    }
     std::shared_ptr<Context> ctx_;
     uh_ba* b_ = nullptr;
     int K_ = 0, P_ = 0;

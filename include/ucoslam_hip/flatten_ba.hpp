@@ -18,7 +18,9 @@
 //   :224-249  one monocular edge per (taken point, observer that is used) in the point's observer order (ascending frame index:
 //             MapPoint::frames is a std::map): measurement = undistorted keypoint, intrinsics of THAT frame, information =
 //             I * _InvScaleFactors[octave] with _InvScaleFactors a vector<float> filled with 1./scaleFactor (:96-97) — i.e. the
-//             optimiser sees (double)(float)(1. / f).  depth > 0 (stereo / RGB-D observation, :250-) is refused: monocular path.
+//             optimiser sees (double)(float)(1. / f).  depth > 0 (stereo / RGB-D observation, :250-) is refused by flatten_for_ba
+//             (the monocular entry) and taken by flatten_for_ba_stereo, which writes the depth per observation and the baseline
+//             (Frame::imageParams.bl) per frame beside the records: the optimiser forms mbf and kp_ur from them (:253-254).
 //   markers (:158-171, :300-398) are refused: marker-less maps only.
 // getResults (:466-537) is apply_results below: poses of the non-fixed used frames, coordinates of the taken points, and the bad
 // associations as (map point id, frame id) pairs.
@@ -54,6 +56,7 @@ struct BAParamSet {
  *   size_t   frame_n_ids(f); uint32_t frame_id(f,i) Frame::ids (0xFFFFFFFF = no map point)
  *   void     frame_keypoint(f, kp, float& x, float& y, int& octave)   Frame::und_kpts[kp]
  *   float    frame_depth(f, kp)                     Frame::getDepth(kp): <= 0 for a monocular observation
+ *   float    frame_baseline(f)                      Frame::imageParams.bl — needed by flatten_for_ba_stereo only
  *   bool     frame_has_valid_markers(f)             any marker of the frame with a valid pose in the map (:158-171)
  *   const std::vector<float>& scale_factors()       map->keyframes.front().scaleFactors
  *   uint32_t point_capacity()
@@ -74,10 +77,15 @@ struct FlatBAIndex {                       // what getResults needs to write bac
 
 constexpr uint32_t kInvalidIdx = 0xFFFFFFFFu;
 
-// Sink = something with `uh_ba_staging begin(int n_frames, int n_points, int n_obs)`: StagingSink(uh_ba*) below maps the optimiser's
-// pinned block; tests pass a vector-backed one and run without a GPU.
-template <class MapView, class Sink>
-FlatBAIndex flatten_for_ba(const MapView& map, const BAParamSet& ps, Sink& sink) {
+namespace detail {
+inline float* stereo_depth(uh_ba_staging&) { return nullptr; }
+inline float* stereo_depth(uh_ba_staging_stereo& st) { return st.obs_depth; }
+inline float* stereo_bl(uh_ba_staging&) { return nullptr; }
+inline float* stereo_bl(uh_ba_staging_stereo& st) { return st.frame_bl; }
+
+// the walk of both entries; STEREO: the sink's block has obs_depth / frame_bl and observations with depth are taken
+template <bool STEREO, class MapView, class Sink>
+FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
     enum : uint8_t { UNFIXED = 0, FIXED_WITHPOINTS = 1, FIXED_WITHOUTPOINTS = 2 };
     const uint32_t FC = map.frame_capacity(), PC = map.point_capacity();
     std::vector<uint8_t> used(FC, 0), fixed(FC, UNFIXED);
@@ -120,13 +128,14 @@ FlatBAIndex flatten_for_ba(const MapView& map, const BAParamSet& ps, Sink& sink)
 
     const int K = (int)ix.frame_of.size(), P = (int)ix.point_of.size();
     if (K == 0) throw std::runtime_error("flatten_for_ba: no frame selected");
-    uh_ba_staging st = sink.begin(K, P, E);
+    auto st = sink.begin(K, P, E);
     for (int k = 0; k < K; k++) {
         const uint32_t f = ix.frame_of[k];
         const float* M = map.frame_pose_f2g(f);
         for (int j = 0; j < 16; j++) st.poses_f2g[16 * k + j] = M[j];
         st.fixed[k] = ix.frame_fixed[k] ? 1 : 0;
         map.frame_intrinsics(f, st.intr + 4 * k);
+        if constexpr (STEREO) stereo_bl(st)[k] = map.frame_baseline(f);
     }
     // _InvScaleFactors (:96-97): a vector<float> of 1./f, read back into a double information matrix
     const std::vector<float>& sf = map.scale_factors();
@@ -138,7 +147,9 @@ FlatBAIndex flatten_for_ba(const MapView& map, const BAParamSet& ps, Sink& sink)
         map.point_coordinates(p, st.points + 3 * pi);
         map.for_each_observer(p, [&](uint32_t of, uint32_t kp) {
             if (!used[of]) return;
-            if (map.frame_depth(of, kp) > 0)
+            const float depth = map.frame_depth(of, kp);
+            if constexpr (STEREO) stereo_depth(st)[e] = depth;
+            else if (depth > 0)
                 throw std::runtime_error("flatten_for_ba: stereo / RGB-D observation (map point " + std::to_string(p) + ", frame " + std::to_string(of) + "); monocular edges only");
             float x, y;
             int octave;
@@ -149,6 +160,21 @@ FlatBAIndex flatten_for_ba(const MapView& map, const BAParamSet& ps, Sink& sink)
         });
     }
     return ix;
+}
+}  // namespace detail
+
+// Sink = something with `uh_ba_staging begin(int n_frames, int n_points, int n_obs)`: StagingSink(uh_ba*) below maps the optimiser's
+// pinned block; tests pass a vector-backed one and run without a GPU.
+template <class MapView, class Sink>
+FlatBAIndex flatten_for_ba(const MapView& map, const BAParamSet& ps, Sink& sink) {
+    return detail::flatten_walk<false>(map, ps, sink);
+}
+
+// The same selection for maps with stereo / RGB-D observations: Sink::begin returns a uh_ba_staging_stereo (StereoStagingSink /
+// StereoVectorSink below); then uh_ba_set_problem_staged_stereo, or uh_ba_set_problem_stereo on the vectors.
+template <class MapView, class Sink>
+FlatBAIndex flatten_for_ba_stereo(const MapView& map, const BAParamSet& ps, Sink& sink) {
+    return detail::flatten_walk<true>(map, ps, sink);
 }
 
 // getResults (:466-537) onto the map: poses of the free used frames, coordinates of every taken point, then
@@ -185,6 +211,28 @@ struct VectorSink {
     uh_ba_staging begin(int K, int P, int E) {
         poses.assign(16 * (size_t)K, 0.f); intr.assign(4 * (size_t)K, 0.f); points.assign(3 * (size_t)P, 0.f); fixed.assign(K, 0); obs.assign(E, uh_ba_obs{});
         return uh_ba_staging{poses.data(), fixed.data(), intr.data(), points.data(), obs.data(), K, P, E};
+    }
+};
+
+// the stereo forms of the two sinks
+struct StereoStagingSink {
+    uh_ba* ba;
+    uh_ba_staging_stereo st{};
+    explicit StereoStagingSink(uh_ba* b) : ba(b) {}
+    uh_ba_staging_stereo begin(int K, int P, int E) {
+        if (uh_ba_map_staging_stereo(ba, K, P, E, &st) < 0) throw std::runtime_error(uh_last_error());
+        return st;
+    }
+};
+
+struct StereoVectorSink {
+    std::vector<float> poses, intr, points, depth, bl;
+    std::vector<uint8_t> fixed;
+    std::vector<uh_ba_obs> obs;
+    uh_ba_staging_stereo begin(int K, int P, int E) {
+        poses.assign(16 * (size_t)K, 0.f); intr.assign(4 * (size_t)K, 0.f); points.assign(3 * (size_t)P, 0.f); fixed.assign(K, 0); obs.assign(E, uh_ba_obs{});
+        depth.assign(E, 0.f); bl.assign(K, 0.f);
+        return uh_ba_staging_stereo{poses.data(), fixed.data(), intr.data(), points.data(), obs.data(), depth.data(), bl.data(), K, P, E};
     }
 };
 

@@ -33,6 +33,15 @@ class _Staging(C.Structure):
                 ("cap_frames", C.c_int32), ("cap_points", C.c_int32), ("cap_obs", C.c_int32)]
 
 
+class _Stereo(C.Structure):   # uh_ba_stereo
+    _fields_ = [("obs_depth", VP), ("frame_bl", VP), ("huber_delta_3d", C.c_double), ("chi2_threshold_3d", C.c_double)]
+
+
+class _StagingStereo(C.Structure):   # uh_ba_staging_stereo
+    _fields_ = [("poses_f2g", VP), ("fixed", VP), ("intr", VP), ("points", VP), ("obs", VP), ("obs_depth", VP), ("frame_bl", VP),
+                ("cap_frames", C.c_int32), ("cap_points", C.c_int32), ("cap_obs", C.c_int32)]
+
+
 class _ResultsView(C.Structure):
     _fields_ = [("poses", VP), ("points", VP), ("chi2", VP), ("bad", VP), ("pose_state", VP), ("iters", C.c_int32 * 2),
                 ("n_frames", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32)]
@@ -57,6 +66,9 @@ def _declare(L, sig):
     sig("uh_ba_solve_async", I, VP, C.POINTER(_Problem), I, I, I, C.POINTER(ParamSet), VP)
     sig("uh_ba_form", I, VP, C.POINTER(C.c_int))
     sig("uh_ba_want_chi2", I, VP, I)
+    sig("uh_ba_set_problem_stereo", I, VP, C.POINTER(_Problem), C.POINTER(_Stereo), C.POINTER(ParamSet))
+    sig("uh_ba_map_staging_stereo", I, VP, I, I, I, C.POINTER(_StagingStereo))
+    sig("uh_ba_set_problem_staged_stereo", I, VP, I, I, I, C.POINTER(ParamSet), C.c_double, C.c_double)
 
 
 _lib._EXTRA_DECLS.append(_declare)
@@ -89,9 +101,20 @@ class GlobalOptimizer:
                       np_ptr(a["obs_kf"]), np_ptr(a["obs_uv"]), np_ptr(a["obs_w"]))
         return pr, a, (K, P, E)
 
-    def setParams(self, problem, params: ParamSet | None = None):
+    def setParams(self, problem, params: ParamSet | None = None, stereo=None):
+        """stereo: None (monocular edges only, uh_ba_set_problem), True (the problem dict's "obs_depth" [E] f32 and "frame_bl" [K] f32:
+        an observation with depth > 0 is a three-row stereo / RGB-D edge) or a dict(huber_delta_3d=, chi2_threshold_3d=) with that meaning."""
         pr, a, dims = problem if isinstance(problem, tuple) else self._problem_struct(problem)
-        check(lib().uh_ba_set_problem(self._h, C.byref(pr), C.byref(params) if params is not None else None))
+        pp = C.byref(params) if params is not None else None
+        if stereo is None or stereo is False:
+            check(lib().uh_ba_set_problem(self._h, C.byref(pr), pp))
+        else:
+            opts = stereo if isinstance(stereo, dict) else {}
+            depth = np.ascontiguousarray(problem["obs_depth"], np.float32)
+            bl = np.ascontiguousarray(problem["frame_bl"], np.float32)
+            assert len(depth) == dims[2] and len(bl) == dims[0]
+            sx = _Stereo(np_ptr(depth), np_ptr(bl), float(opts.get("huber_delta_3d", 0.0)), float(opts.get("chi2_threshold_3d", 0.0)))
+            check(lib().uh_ba_set_problem_stereo(self._h, C.byref(pr), C.byref(sx), pp))
         self._dims = dims
         self._obs = (a["obs_pt"], a["obs_kf"])
         self._bad = None
@@ -121,6 +144,34 @@ class GlobalOptimizer:
         o["inv_sigma"] = problem["obs_w"]
         self._obs = (np.array(problem["obs_pt"], np.int32), np.array(problem["obs_kf"], np.int32))
         return K, P, E
+
+    def fillStagingStereo(self, problem: dict) -> tuple:
+        """fillStaging through uh_ba_map_staging_stereo: also the per-observation depth and the per-frame baseline."""
+        K, P, E = len(problem["fixed"]), len(problem["points"]), len(problem["obs_pt"])
+        st = _StagingStereo()
+        check(lib().uh_ba_map_staging_stereo(self._h, K, P, E, C.byref(st)))
+
+        def view(ptr, dtype, shape):
+            n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            return np.frombuffer((C.c_char * max(n, 1)).from_address(ptr), dtype=dtype, count=int(np.prod(shape))).reshape(shape)
+
+        view(st.poses_f2g, np.float32, (K, 16))[:] = problem["poses"].reshape(K, 16)
+        view(st.fixed, np.uint8, (K,))[:] = problem["fixed"]
+        view(st.intr, np.float32, (K, 4))[:] = problem["intr"]
+        view(st.points, np.float32, (P, 3))[:] = problem["points"]
+        o = view(st.obs, OBS_DTYPE, (E,))
+        o["point"] = problem["obs_pt"]; o["frame"] = problem["obs_kf"]; o["u"] = problem["obs_uv"][:, 0]; o["v"] = problem["obs_uv"][:, 1]
+        o["inv_sigma"] = problem["obs_w"]
+        view(st.obs_depth, np.float32, (E,))[:] = problem["obs_depth"]
+        view(st.frame_bl, np.float32, (K,))[:] = problem["frame_bl"]
+        self._obs = (np.array(problem["obs_pt"], np.int32), np.array(problem["obs_kf"], np.int32))
+        return K, P, E
+
+    def setParamsStagedStereo(self, K: int, P: int, E: int, params: ParamSet | None = None, huber_delta_3d=0.0, chi2_threshold_3d=0.0):
+        check(lib().uh_ba_set_problem_staged_stereo(self._h, K, P, E, C.byref(params) if params is not None else None,
+                                                    float(huber_delta_3d), float(chi2_threshold_3d)))
+        self._dims = (K, P, E)
+        self._bad = None
 
     def setParamsStaged(self, K: int, P: int, E: int, params: ParamSet | None = None):
         check(lib().uh_ba_set_problem_staged(self._h, K, P, E, C.byref(params) if params is not None else None))

@@ -244,6 +244,97 @@ __device__ __forceinline__ void edge_eval(const BAPtrs& p, const BADims& d, int 
                      d.delta, d.dsqr, Rt, X, robust, o);
 }
 
+// ------------------------------------------------------------------------------------------------ stereo / RGB-D edges
+// EdgeStereoSE3ProjectXYZ (typesg2o.h:327-409): an observation with depth has three residual rows (u, v, u_right).  Only the STEREO
+// instantiations of the linearising kernels receive this block, as a trailing kernel argument of their own: BAPtrs / BADims / BAState
+// and every monocular instantiation keep their layout and their code.  An edge without depth inside a stereo problem (e_st == 0)
+// evaluates the monocular expressions above and contributes zeros in the third row.
+struct BAStereo {
+    const double* e_ur;           // E: right-image column kp_ur (a float, widened); unused where e_st == 0
+    const double* e_bf;           // E: baseline * fx of the observing frame (a float product, widened)
+    const unsigned char* e_st;    // E: 1 = three-row edge
+    double delta3, dsqr3, chi2_th3;   // thHuber3D (and its square), Chi3D
+};
+__device__ __forceinline__ BAStereo stereo_arg() { return BAStereo{}; }
+__device__ __forceinline__ BAStereo stereo_arg(const BAStereo& s) { return s; }
+
+struct EdgeLin3 {         // EdgeLin with a third row
+    double ex, ey, ez, chi2, rho1, ww, r0, r1, r2;
+    double A[9], B[18];
+    double robchi;
+};
+
+template <bool JAC>
+__device__ __forceinline__ void edge_eval_s(const BAPtrs& p, const BADims& d, const BAStereo& sx, int e, int k, const double* Rt, const double* X,
+                                            bool robust, EdgeLin3& o) {
+    const double u = p.e_uv[2 * e], v = p.e_uv[2 * e + 1], w = p.e_w[e];
+    const double fx = p.intr[4 * k], fy = p.intr[4 * k + 1], cx = p.intr[4 * k + 2], cy = p.intr[4 * k + 3];
+    const bool st = sx.e_st[e] != 0;
+    const double x = Rt[0] * X[0] + Rt[1] * X[1] + Rt[2] * X[2] + Rt[9];
+    const double y = Rt[3] * X[0] + Rt[4] * X[1] + Rt[5] * X[2] + Rt[10];
+    const double z = Rt[6] * X[0] + Rt[7] * X[1] + Rt[8] * X[2] + Rt[11];
+    double bf = 0;
+    o.rho1 = 1.0;
+    if (st) {   // cam_project (:399-406): invz is a double quotient rounded to float, bf * invz a float product
+        bf = sx.e_bf[e];
+        const float invzf = (float)(1.0 / z);
+        const double invz = invzf;
+        const double pu = x * invz * fx + cx;
+        const double pv = y * invz * fy + cy;
+        const double pr = pu - (double)((float)bf * invzf);
+        o.ex = u - pu; o.ey = v - pv; o.ez = sx.e_ur[e] - pr;
+        o.chi2 = w * (o.ex * o.ex + o.ey * o.ey + o.ez * o.ez);
+        o.robchi = o.chi2;
+        if (robust && o.chi2 > sx.dsqr3) {   // (the Huber step once per branch: each reads its own width straight from its argument block)
+            const double sq = sqrt(o.chi2);
+            o.rho1 = sx.delta3 / sq;
+            o.robchi = 2 * sq * sx.delta3 - sx.dsqr3;
+        }
+    } else {
+        o.ex = u - ((x / z) * fx + cx);
+        o.ey = v - ((y / z) * fy + cy);
+        o.ez = 0;
+        o.chi2 = w * (o.ex * o.ex + o.ey * o.ey);
+        o.robchi = o.chi2;
+        if (robust && o.chi2 > d.dsqr) {
+            const double sq = sqrt(o.chi2);
+            o.rho1 = d.delta / sq;
+            o.robchi = 2 * sq * d.delta - d.dsqr;
+        }
+    }
+    if (JAC) {
+        o.ww = o.rho1 * w;
+        o.r0 = -w * o.ex * o.rho1;
+        o.r1 = -w * o.ey * o.rho1;
+        o.r2 = -w * o.ez * o.rho1;
+        const double z2 = z * z;
+        if (st) {   // linearizeOplus (:352-397)
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                o.A[c] = -fx * Rt[c] / z + fx * x * Rt[6 + c] / z2;
+                o.A[3 + c] = -fy * Rt[3 + c] / z + fy * y * Rt[6 + c] / z2;
+                o.A[6 + c] = o.A[c] - bf * Rt[6 + c] / z2;
+            }
+        } else {
+            const double t02 = -x / z * fx, t12 = -y / z * fy, iz = -1. / z;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                o.A[c] = iz * (fx * Rt[c] + t02 * Rt[6 + c]);
+                o.A[3 + c] = iz * (fy * Rt[3 + c] + t12 * Rt[6 + c]);
+                o.A[6 + c] = 0;
+            }
+        }
+        o.B[0] = x * y / z2 * fx; o.B[1] = -(1 + (x * x / z2)) * fx; o.B[2] = y / z * fx; o.B[3] = -1. / z * fx; o.B[4] = 0; o.B[5] = x / z2 * fx;
+        o.B[6] = (1 + y * y / z2) * fy; o.B[7] = -x * y / z2 * fy; o.B[8] = -x / z * fy; o.B[9] = 0; o.B[10] = -1. / z * fy; o.B[11] = y / z2 * fy;
+        if (st) {
+            o.B[12] = o.B[0] - bf * y / z2; o.B[13] = o.B[1] + bf * x / z2; o.B[14] = o.B[2]; o.B[15] = o.B[3]; o.B[16] = 0; o.B[17] = o.B[5] - bf / z2;
+        } else {
+#pragma unroll
+            for (int a = 0; a < 6; a++) o.B[12 + a] = 0;
+        }
+    }
+}
+
 // Linearisation of one landmark by its 8 lanes (one observation each per round; 32 landmarks per workgroup): errors, Huber
 // weights, Hll, bl and the per-edge Hpl blocks at pose set poseR / point X, written to linearisation buffer `buf`.  The 8 partial sums are added with a fixed xor
 // butterfly, so the result is deterministic and identical in all 8 lanes.  Lane gl==0 returns the landmark's robust chi2
@@ -275,6 +366,56 @@ __device__ __forceinline__ void linearize_point(const BAPtrs& p, const BADims& d
                 for (int a = 0; a < 6; a++)
 #pragma unroll
                     for (int c = 0; c < 3; c++) Hx[a * 3 + c] = L.ww * (L.B[a] * L.A[c] + L.B[6 + a] * L.A[3 + c]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+#pragma unroll
+        for (int o = kLanesPerPoint / 2; o > 0; o >>= 1) acc[i] += __shfl_xor(acc[i], o);
+    }
+    const unsigned long long anym = __ballot(any);
+    const bool any_pt = ((anym >> ((threadIdx.x & 63) & ~(kLanesPerPoint - 1))) & 0xFFull) != 0;
+    chi_part = 0; maxd = 0;
+    if (live && gl == 0) {
+        double* Hl = p.Hll[buf] + 9 * (size_t)pt;
+        Hl[0] = acc[0]; Hl[1] = acc[1]; Hl[2] = acc[2]; Hl[3] = acc[1]; Hl[4] = acc[3]; Hl[5] = acc[4]; Hl[6] = acc[2]; Hl[7] = acc[4]; Hl[8] = acc[5];
+        double* bo = p.bl[buf] + 3 * (size_t)pt;
+        bo[0] = acc[6]; bo[1] = acc[7]; bo[2] = acc[8];
+        chi_part = acc[9];
+        if (any_pt) maxd = fmax(fabs(acc[0]), fmax(fabs(acc[3]), fabs(acc[5])));
+    }
+}
+
+// linearize_point with three-row edges: same lanes, same butterfly, same outputs (Hll, bl, 6 x 3 Hpl blocks)
+__device__ __forceinline__ void linearize_point_s(const BAPtrs& p, const BADims& d, const BAStereo& sx, int buf, int pt, int gl, bool live,
+                                                  const double* poseR, const double* X, double& chi_part, double& maxd) {
+    double acc[10];   // Hll upper (6), bl (3), robust chi2 (1)
+#pragma unroll
+    for (int i = 0; i < 10; i++) acc[i] = 0;
+    bool any = false;
+    if (live) {
+        for (int i = p.pt_ptr[pt] + gl; i < p.pt_ptr[pt + 1]; i += kLanesPerPoint) {
+            const int e = p.pt_edges[i];
+            if (!p.e_active[e]) continue;
+            any = true;
+            const int k = p.e_kf[e];
+            EdgeLin3 L;
+            edge_eval_s<true>(p, d, sx, e, k, poseR + 12 * k, X, p.e_robust[e] != 0, L);
+            p.e_err[2 * e] = L.ex; p.e_err[2 * e + 1] = L.ey;
+            p.e_chi2[e] = L.chi2;
+            acc[9] += L.robchi;
+            acc[0] += L.ww * (L.A[0] * L.A[0] + L.A[3] * L.A[3] + L.A[6] * L.A[6]); acc[1] += L.ww * (L.A[0] * L.A[1] + L.A[3] * L.A[4] + L.A[6] * L.A[7]);
+            acc[2] += L.ww * (L.A[0] * L.A[2] + L.A[3] * L.A[5] + L.A[6] * L.A[8]); acc[3] += L.ww * (L.A[1] * L.A[1] + L.A[4] * L.A[4] + L.A[7] * L.A[7]);
+            acc[4] += L.ww * (L.A[1] * L.A[2] + L.A[4] * L.A[5] + L.A[7] * L.A[8]); acc[5] += L.ww * (L.A[2] * L.A[2] + L.A[5] * L.A[5] + L.A[8] * L.A[8]);
+            acc[6] += L.A[0] * L.r0 + L.A[3] * L.r1 + L.A[6] * L.r2; acc[7] += L.A[1] * L.r0 + L.A[4] * L.r1 + L.A[7] * L.r2;
+            acc[8] += L.A[2] * L.r0 + L.A[5] * L.r1 + L.A[8] * L.r2;
+            if (p.slot[k] >= 0) {
+                double* Hx = p.Hpl[buf] + 18 * (size_t)e;
+#pragma unroll
+                for (int a = 0; a < 6; a++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) Hx[a * 3 + c] = L.ww * (L.B[a] * L.A[c] + L.B[6 + a] * L.A[3 + c] + L.B[12 + a] * L.A[6 + c]);
             }
         }
     }
@@ -329,9 +470,43 @@ __device__ __forceinline__ void camera_block(const BAPtrs& p, const BADims& d, i
     if (threadIdx.x < 27) p.HppPart[(size_t)cb * 27 + threadIdx.x] = s_out27[threadIdx.x];
 }
 
+// camera_block with three-row edges
+__device__ __forceinline__ void camera_block_s(const BAPtrs& p, const BADims& d, const BAStereo& sx, int cb, const double* poseR, const double* pts) {
+    const int s = cb / kCamChunks, chunk = cb - s * kCamChunks;
+    const int k = p.free_kf[s];
+    double Rt[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) Rt[i] = poseR[12 * k + i];
+    // 28 slots, 27 used: a block reduction instantiation of its own.  Sharing block_sum_vec<28> with camera_block changed the address
+    // arithmetic the compiler emits for it inside the monocular kernels (same values, other operand order); their code is to stay as it is.
+    double acc[28];
+#pragma unroll
+    for (int i = 0; i < 28; i++) acc[i] = 0;
+    for (int i = p.cam_ptr[s] + chunk * kThreads + threadIdx.x; i < p.cam_ptr[s + 1]; i += kCamChunks * kThreads) {
+        const int e = p.cam_edges[i];
+        if (!p.e_active[e]) continue;
+        const int pt = p.e_pt[e];
+        const double X[3] = {pts[3 * pt], pts[3 * pt + 1], pts[3 * pt + 2]};
+        EdgeLin3 L;
+        edge_eval_s<true>(p, d, sx, e, k, Rt, X, p.e_robust[e] != 0, L);
+        int q = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int c = a; c < 6; c++) acc[q++] += L.ww * (L.B[a] * L.B[c] + L.B[6 + a] * L.B[6 + c] + L.B[12 + a] * L.B[12 + c]);
+#pragma unroll
+        for (int a = 0; a < 6; a++) acc[21 + a] += L.B[a] * L.r0 + L.B[6 + a] * L.r1 + L.B[12 + a] * L.r2;
+    }
+    __shared__ double s_part[4 * 28];
+    __shared__ double s_out27[28];
+    block_sum_vec<28>(acc, s_part, s_out27);
+    if (threadIdx.x < 27) p.HppPart[(size_t)cb * 27 + threadIdx.x] = s_out27[threadIdx.x];
+}
+
 // ------------------------------------------------------------------------------------------------ lin
 // grid = nPointBlocks + nfree*kCamChunks.  Launched once per pass (first trial); later linearisations come from backsub.
-__global__ __launch_bounds__(kThreads) void ba_lin_kernel(BAPtrs p, BADims d, int slot) {
+template <bool STEREO, typename... SX>
+__global__ __launch_bounds__(kThreads) void ba_lin_kernel(BAPtrs p, BADims d, int slot, SX... sx) {
     uh_latency_critical();
     __shared__ double s_red[kThreads];
     const BAState st = p.st[slot];
@@ -347,15 +522,18 @@ __global__ __launch_bounds__(kThreads) void ba_lin_kernel(BAPtrs p, BADims d, in
         const int ptc = live ? pt : 0;
         const double X[3] = {pts[3 * ptc], pts[3 * ptc + 1], pts[3 * ptc + 2]};
         double chi_part, maxd;
-        linearize_point(p, d, cur, pt, gl, live, poseR, X, chi_part, maxd);
+        if constexpr (STEREO) linearize_point_s(p, d, stereo_arg(sx...), cur, pt, gl, live, poseR, X, chi_part, maxd);
+        else linearize_point(p, d, cur, pt, gl, live, poseR, X, chi_part, maxd);
         const double cs = block_sum(chi_part, s_red);
         const double mx = block_max(maxd, s_red);
         if (threadIdx.x == 0) { p.part_lin_chi[blockIdx.x] = cs; p.part_maxdiag[blockIdx.x] = mx; }
         UH_BA_CLK(1);
     } else {
-        camera_block(p, d, blockIdx.x - d.nPointBlocks, poseR, pts);
+        if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x - d.nPointBlocks, poseR, pts);
+        else camera_block(p, d, blockIdx.x - d.nPointBlocks, poseR, pts);
     }
 }
+template __global__ void ba_lin_kernel<false>(BAPtrs, BADims, int);   // (instantiated here: the monocular kernel keeps its place in the module)
 
 // ------------------------------------------------------------------------------------------------ decide
 // One wave: the tail of OptimizationAlgorithmLevenberg::solve's do-while body plus SparseOptimizer::optimize's loop header.
@@ -453,7 +631,8 @@ __device__ __forceinline__ BAState apply_decision(const BAState& st0, const Deci
 // grid = npairs * nsplit.  Block (pair, chunk) accumulates the landmarks pt = chunk*256 + tid (+ nsplit*256 ...) of the
 // (i1 <= i2) block and writes a PARTIAL 6x6 (and, on diagonal pairs, a partial 6-vector); the solve kernel adds the
 // partials in chunk order.  The first block also publishes lambda at iteration 0 (computeLambdaInit).
-__global__ __launch_bounds__(kThreads) void ba_schur_kernel(BAPtrs p, BADims d, int nsplit, int slot) {
+template <bool STEREO, typename... SX>
+__global__ __launch_bounds__(kThreads) void ba_schur_kernel(BAPtrs p, BADims d, int nsplit, int slot, SX... sx) {
     uh_latency_critical();
     __shared__ double s_part[4 * 42];
     __shared__ double s_out[42];
@@ -511,7 +690,10 @@ __global__ __launch_bounds__(kThreads) void ba_schur_kernel(BAPtrs p, BADims d, 
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
     if (cam_role) {   // camera workgroups: Hpp / bp partials (the lin kernel has them at the first trial)
-        if (!st.first_trial) camera_block(p, d, blockIdx.x - npairblocks, p.poseR[st.cur], p.pts[st.cur]);
+        if (!st.first_trial) {
+            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x - npairblocks, p.poseR[st.cur], p.pts[st.cur]);
+            else camera_block(p, d, blockIdx.x - npairblocks, p.poseR[st.cur], p.pts[st.cur]);
+        }
         return;
     }
     double acc[42];
@@ -553,6 +735,7 @@ __global__ __launch_bounds__(kThreads) void ba_schur_kernel(BAPtrs p, BADims d, 
     if (have_pair && threadIdx.x < 42) p.Spart[((size_t)chunk * npairs + pair) * 42 + threadIdx.x] = s_out[threadIdx.x];
     UH_BA_CLK(5);
 }
+template __global__ void ba_schur_kernel<false>(BAPtrs, BADims, int, int);
 
 // ------------------------------------------------------------------------------------------------ schur, dense form (17-32 free cameras)
 // The pair form above recomputes a landmark's D^-1 for every camera pair and re-reads both Hpl blocks per pair: 528 pairs x 3000
@@ -675,7 +858,8 @@ __device__ __forceinline__ void schur_dense_wave(const BAPtrs& p, const BADims& 
     if (tid < n) p.dbpart[(size_t)g * 16 * sd.ntt + tid] = bacc;
 }
 
-__global__ __launch_bounds__(kThreads) void ba_schur_dense_kernel(BAPtrs p, BADims d, SchurDense sd, int slot) {
+template <bool STEREO, typename... SX>
+__global__ __launch_bounds__(kThreads) void ba_schur_dense_kernel(BAPtrs p, BADims d, SchurDense sd, int slot, SX... sx) {
     uh_latency_critical();
     extern __shared__ __attribute__((aligned(16))) double s_dense[];   // Yt[48][ys], z[48]
     __shared__ BAState s_state;
@@ -721,7 +905,10 @@ __global__ __launch_bounds__(kThreads) void ba_schur_dense_kernel(BAPtrs p, BADi
     }
     if (blockIdx.x == 0 && tid == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
     if (cam_role) {
-        if (!st.first_trial) camera_block(p, d, blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+        if (!st.first_trial) {
+            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+            else camera_block(p, d, blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+        }
         UH_DENSE_END(17);
         return;
     }
@@ -737,14 +924,15 @@ __global__ __launch_bounds__(kThreads) void ba_schur_dense_kernel(BAPtrs p, BADi
     if ((int)blockIdx.x == ncam && tid == 0) p.clk[5] = wall_clock64();
     UH_DENSE_END(16);
 }
+template __global__ void ba_schur_dense_kernel<false>(BAPtrs, BADims, SchurDense, int);
 
 // The dense form for 33-64 free cameras (13-24 tile rows, up to 300 lower tiles: their accumulators do not fit one workgroup).  SP
 // workgroups share a landmark group; each builds the group's panels itself (8 landmarks = 24 rows at a time: the panel of 24 tile
 // columns is 77 KB) and owns a contiguous range of the tile list, NOWN tiles per wave.  A wave's tile list is computed at run time
 // (the operands' column offsets are wave-uniform scalars), every k-step reads its 2 NOWN operands from LDS and issues NOWN MFMAs —
 // no predicate: a slot past the end of the list works on tile 0 and is not stored.
-template <int NOWN>
-__global__ __launch_bounds__(kThreads) void ba_schur_dense_wide_kernel(BAPtrs p, BADims d, SchurDense sd, int slot) {
+template <int NOWN, bool STEREO, typename... SX>
+__global__ __launch_bounds__(kThreads) void ba_schur_dense_wide_kernel(BAPtrs p, BADims d, SchurDense sd, int slot, SX... sx) {
     uh_latency_critical();
     extern __shared__ __attribute__((aligned(16))) double s_dense[];   // Yt[24][ys], z[24]
     __shared__ BAState s_state;
@@ -785,7 +973,10 @@ __global__ __launch_bounds__(kThreads) void ba_schur_dense_wide_kernel(BAPtrs p,
     }
     if (blockIdx.x == 0 && tid == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
     if (cam_role) {
-        if (!st.first_trial) camera_block(p, d, blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+        if (!st.first_trial) {
+            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+            else camera_block(p, d, blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+        }
         return;
     }
     const int wg = blockIdx.x - ncam, g = wg / sd.SP, sp = wg - g * sd.SP;
@@ -1734,13 +1925,17 @@ __global__ __launch_bounds__(64) void ba_advance_kernel(BAPtrs p, BADims d, int 
 }
 
 // grid = n_items + nfree * kCamChunks; `slot` = the state ba_advance_kernel published
-__global__ __launch_bounds__(kThreads) void ba_schurw_kernel(BAPtrs p, BADims d, BAWide w, int slot) {
+template <bool STEREO, typename... SX>
+__global__ __launch_bounds__(kThreads) void ba_schurw_kernel(BAPtrs p, BADims d, BAWide w, int slot, SX... sx) {
     __shared__ double s_part[4 * 42];
     __shared__ double s_out[42];
     const BAState st = p.st[slot];
     if (st.phase == 2) return;
     if ((int)blockIdx.x >= w.n_items) {
-        if (!st.first_trial) camera_block(p, d, blockIdx.x - w.n_items, p.poseR[st.cur], p.pts[st.cur]);
+        if (!st.first_trial) {
+            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x - w.n_items, p.poseR[st.cur], p.pts[st.cur]);
+            else camera_block(p, d, blockIdx.x - w.n_items, p.poseR[st.cur], p.pts[st.cur]);
+        }
         return;
     }
     const int item = blockIdx.x, pair = w.item_pair[item];
@@ -1779,6 +1974,7 @@ __global__ __launch_bounds__(kThreads) void ba_schurw_kernel(BAPtrs p, BADims d,
     block_sum_vec<42>(acc, s_part, s_out);
     if (threadIdx.x < 42) w.Wpart[(size_t)item * 42 + threadIdx.x] = s_out[threadIdx.x];
 }
+template __global__ void ba_schurw_kernel<false>(BAPtrs, BADims, BAWide, int);
 
 // grid = n_pairs, 64 threads (42 used): S block of the pair = [Hpp + lambda I on diagonal pairs] - sum of the pair's items (in
 // order), mirrored into the lower triangle; diagonal pairs also write b_p (for the decision) and the border row b_p - B D^-1 b_l
@@ -1961,8 +2157,8 @@ __global__ __launch_bounds__(256) void ba_posew_kernel(BAPtrs p, BADims d, BAWid
 // factorisation and substitution in all of them, ~22 us that would otherwise be a one-workgroup launch of its own — keeps dx_p
 // in LDS and goes on with its landmarks.  All workgroups write identical trial poses / xp / solve_ok.  Saves one kernel
 // boundary and the dependent reloads behind it per LM trial.
-template <bool FUSED>
-__global__ __launch_bounds__(FUSED ? kFusedThreads : kThreads) void ba_backsub_kernel(BAPtrs p, BADims d, int nsplit, int slot) {
+template <bool FUSED, bool STEREO, typename... SX>
+__global__ __launch_bounds__(FUSED ? kFusedThreads : kThreads) void ba_backsub_kernel(BAPtrs p, BADims d, int nsplit, int slot, SX... sx) {
     uh_latency_critical();
     __shared__ double s_red[kThreads];
     __shared__ double s_xp[6 * kMaxFree];
@@ -2039,7 +2235,8 @@ __global__ __launch_bounds__(FUSED ? kFusedThreads : kThreads) void ba_backsub_k
         // double-buffered Hll/bl/Hpl: an accepted trial flips both and goes straight to the schur kernel, a rejected one keeps
         // the current estimate with its linearisation intact.  The lin kernel is needed only once per pass.
         double maxd_unused;
-        linearize_point(p, d, trial, pt, gl, live, p.poseR[trial], X, chi_part, maxd_unused);
+        if constexpr (STEREO) linearize_point_s(p, d, stereo_arg(sx...), trial, pt, gl, live, p.poseR[trial], X, chi_part, maxd_unused);
+        else linearize_point(p, d, trial, pt, gl, live, p.poseR[trial], X, chi_part, maxd_unused);
     }
     const double cs = block_sum(chi_part, s_red);
     const double ss = block_sum(scale_part, s_red);
@@ -2058,7 +2255,8 @@ __global__ void ba_gate_kernel(BAPtrs p, int slot) {
     if (st.gate) st.iters_pass1 = st.iters_done;
 }
 
-__global__ void ba_relabel_kernel(BAPtrs p, BADims d, int slot, int gated) {
+template <bool STEREO, typename... SX>
+__global__ void ba_relabel_kernel(BAPtrs p, BADims d, int slot, int gated, SX... sx) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= d.E) return;
     if (gated && !p.st[slot].gate) return;
@@ -2067,7 +2265,9 @@ __global__ void ba_relabel_kernel(BAPtrs p, BADims d, int slot, int gated) {
     const double* Rt = p.poseR[cur] + 12 * k;
     const double* X = p.pts[cur] + 3 * pt;
     const double z = Rt[6] * X[0] + Rt[7] * X[1] + Rt[8] * X[2] + Rt[11];
-    if (p.e_chi2[e] > d.chi2_th || !(z > 0.0)) p.e_active[e] = 0;
+    double th = d.chi2_th;
+    if constexpr (STEREO) { const BAStereo s3 = stereo_arg(sx...); if (s3.e_st[e]) th = s3.chi2_th3; }   // (:438: Chi3D for a three-row edge)
+    if (p.e_chi2[e] > th || !(z > 0.0)) p.e_active[e] = 0;
     p.e_robust[e] = 0;
 }
 
@@ -2091,8 +2291,9 @@ __global__ void ba_begin_pass_kernel(BAPtrs p, int max_iters, float minChi2, int
 }
 
 // getResults (:466-537): float poses (free frames), float points, bad associations
+template <bool STEREO, typename... SX>
 __global__ void ba_results_kernel(BAPtrs p, BADims d, const float* __restrict__ poses_in, float* __restrict__ poses_out,
-                                  float* __restrict__ points_out, unsigned char* __restrict__ bad_out, int stage, int slot) {
+                                  float* __restrict__ points_out, unsigned char* __restrict__ bad_out, int stage, int slot, SX... sx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int cur = p.st[slot].cur;
     if (stage == 0) {
@@ -2108,6 +2309,15 @@ __global__ void ba_results_kernel(BAPtrs p, BADims d, const float* __restrict__ 
         if (i < 3 * d.P) points_out[i] = (float)p.pts[cur][i];
     } else if (i < d.E) {
         bool bad = p.e_chi2[i] > d.chi2_th;
+        if constexpr (STEREO) {   // (:509) a three-row edge: Chi3D, and isDepthPositive() on the double state
+            const BAStereo s3 = stereo_arg(sx...);
+            if (s3.e_st[i]) {
+                const double* Rt = p.poseR[cur] + 12 * p.e_kf[i];
+                const double* Xd = p.pts[cur] + 3 * p.e_pt[i];
+                const double zd = Rt[6] * Xd[0] + Rt[7] * Xd[1] + Rt[8] * Xd[2] + Rt[11];
+                bad = p.e_chi2[i] > s3.chi2_th3 || !(zd > 0.0);
+            }
+        }
         if (!bad) {
             const float* M = poses_out + 16 * p.e_kf[i];
             const float* X = points_out + 3 * p.e_pt[i];
@@ -2210,6 +2420,8 @@ struct uh_ba {
     int nsplit = 1;
     bool dense = false; SchurDense sd{};   // 17-32 free keyframes of the launch chain: ba_schur_dense_kernel + ba_schur_reduce_kernel (Spart then holds ONE chunk)
     bool wide = false;                    // more than kMaxFree free keyframes: sparse pair lists + blocked dense LDL^T in HBM
+    bool stereo = false; BAStereo sx{};   // the problem has three-row (stereo / RGB-D) edges: launch chain or wide form, STEREO instantiations
+    std::vector<float> stage_depth, stage_bl;   // uh_ba_map_staging_stereo: per-observation depth / per-frame baseline beside the staging block
     bool persist = false;                 // 1..8 free keyframes: the whole optimisation is ONE persistent launch (ba_persist.hpp)
     int persist_blocked = 0;              // > 0: the persistent form's workgroups did not all become resident lately (another spinning kernel shares the GPU): so many of the next problems take the launch chain
     BAPersist pq{};
@@ -2292,6 +2504,19 @@ void quat_from_R_host(const double* R, double* q) {
     for (int a = 0; a < 4; a++) q[a] /= n;
 }
 
+// Launch of a kernel that linearises: the monocular instantiation (same arguments as ever) or, on a problem with three-row edges, the
+// STEREO one with the BAStereo block behind them.  T0: a leading template argument of the kernel's own.
+#define UH_LAUNCH_BA(b, K, grid, block, shmem, ...)                                                            \
+    do {                                                                                                       \
+        if ((b)->stereo) UH_LAUNCH((b)->ctx, (K<true, BAStereo>), grid, block, shmem, __VA_ARGS__, (b)->sx);   \
+        else UH_LAUNCH((b)->ctx, (K<false>), grid, block, shmem, __VA_ARGS__);                                 \
+    } while (0)
+#define UH_LAUNCH_BA1(b, K, T0, grid, block, shmem, ...)                                                           \
+    do {                                                                                                           \
+        if ((b)->stereo) UH_LAUNCH((b)->ctx, (K<T0, true, BAStereo>), grid, block, shmem, __VA_ARGS__, (b)->sx);   \
+        else UH_LAUNCH((b)->ctx, (K<T0, false>), grid, block, shmem, __VA_ARGS__);                                 \
+    } while (0)
+
 int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
     hipStream_t st = b->ctx->stream;
     const BADims& d = b->dims;
@@ -2301,14 +2526,14 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
     const size_t lds = use_lds ? (size_t)(d.n + 1) * (d.n + 1) * sizeof(double) : 0;   // n rows of S + the right-hand-side row
     for (int s = 0; s < nsteps; s++) {
         const int slot = b->step & 1;   // state left by the previous step (or by begin_pass / the closing decide kernel)
-        if (pass_start && s == 0) UH_LAUNCH(b->ctx,ba_lin_kernel, dim3(d.nPointBlocks + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, slot);
+        if (pass_start && s == 0) UH_LAUNCH_BA(b, ba_lin_kernel, dim3(d.nPointBlocks + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, slot);
         if (b->wide) {
             const BAWide& W = b->wd;
             const int run = slot ^ 1;   // the state this step runs with (published by the advance kernel)
             UH_LAUNCH(b->ctx, ba_advance_kernel, dim3(1), dim3(64), 0, b->ptrs, d, slot);
             UH_HIP_CHECK(hipMemsetAsync(W.S, 0, sizeof(double) * (size_t)W.ld * W.ld, st));
             UH_HIP_CHECK(hipMemsetAsync(W.fail, 0, sizeof(int), st));
-            UH_LAUNCH(b->ctx, ba_schurw_kernel, dim3(W.n_items + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, W, run);
+            UH_LAUNCH_BA(b, ba_schurw_kernel, dim3(W.n_items + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, W, run);
             UH_LAUNCH(b->ctx, ba_assemblew_kernel, dim3(W.n_pairs), dim3(64), 0, b->ptrs, d, W, run);
             for (int k0 = 0; k0 < d.n; k0 += kWNB) {
                 const int nb = std::min(kWNB, d.n - k0), rows = d.n + 1 - (k0 + nb);   // rows behind the panel, border row included
@@ -2322,7 +2547,7 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
                 UH_LAUNCH(b->ctx, ba_ldlw_back_kernel, dim3(std::max(uh_div_up(k0, 256), 1)), dim3(256), 0, b->ptrs, W, run, k0, nb);
             }
             UH_LAUNCH(b->ctx, ba_posew_kernel, dim3(uh_div_up(d.nfree, 256)), dim3(256), 0, b->ptrs, d, W, run);
-            UH_LAUNCH(b->ctx, ba_backsub_kernel<false>, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, b->nsplit, run);
+            UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, b->nsplit, run);
             b->step++;
             continue;
         }
@@ -2346,25 +2571,25 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
             if (sd.SP > 0) {
                 const dim3 gridw(d.nfree * kCamChunks + sd.G * sd.SP);
                 const size_t ldsw = (size_t)(24 * sd.ys + 24) * sizeof(double);
-                if (sd.nown == 12) UH_LAUNCH(b->ctx, ba_schur_dense_wide_kernel<12>, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
-                else if (sd.nown == 16) UH_LAUNCH(b->ctx, ba_schur_dense_wide_kernel<16>, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
-                else UH_LAUNCH(b->ctx, ba_schur_dense_wide_kernel<20>, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
+                if (sd.nown == 12) UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, 12, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
+                else if (sd.nown == 16) UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, 16, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
+                else UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, 20, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
             } else
-                UH_LAUNCH(b->ctx, ba_schur_dense_kernel, dim3(d.nfree * kCamChunks + sd.G), dim3(kThreads), (size_t)(48 * sd.ys + 48) * sizeof(double), b->ptrs, d, sd, slot);
+                UH_LAUNCH_BA(b, ba_schur_dense_kernel, dim3(d.nfree * kCamChunks + sd.G), dim3(kThreads), (size_t)(48 * sd.ys + 48) * sizeof(double), b->ptrs, d, sd, slot);
             UH_LAUNCH(b->ctx, ba_schur_reduce_kernel, dim3(sd.T + uh_div_up(d.n, kThreads)), dim3(kThreads * kReduceGroups), 0, b->ptrs, d, sd, slot ^ 1, pre_mode);
         } else
-        UH_LAUNCH(b->ctx,ba_schur_kernel, dim3(std::max(npairs, 1) * b->nsplit + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, b->nsplit, slot);
+        UH_LAUNCH_BA(b, ba_schur_kernel, dim3(std::max(npairs, 1) * b->nsplit + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, b->nsplit, slot);
         // the solve in HBM takes the finished system from a launch of its own (every pair's words in parallel) instead of assembling alone
         const bool pre_hbm = !b->dense && !use_lds && !use_packed && npairs > 0 && !pre_off;
         if (pre_hbm) UH_LAUNCH(b->ctx, ba_assemble_pairs_kernel, dim3(uh_div_up(npairs * 42, kThreads)), dim3(kThreads), 0, b->ptrs, d, b->nsplit, slot ^ 1);
         if (use_lds) {
-            UH_LAUNCH(b->ctx,ba_backsub_kernel<true>, dim3(d.nPointBlocks), dim3(kFusedThreads), lds, b->ptrs, d, ns, slot ^ 1);
+            UH_LAUNCH_BA1(b, ba_backsub_kernel, true, dim3(d.nPointBlocks), dim3(kFusedThreads), lds, b->ptrs, d, ns, slot ^ 1);
         } else {
             if (use_packed)
                 UH_LAUNCH(b->ctx, (ba_solve_kernel<false, true>), dim3(1), dim3(kPackedThreads), packed, b->ptrs, d, ns, slot ^ 1);
             else
                 UH_LAUNCH(b->ctx,ba_solve_kernel<false>, dim3(1), dim3(kHbmThreads), 0, b->ptrs, d, pre_hbm ? 0 : ns, slot ^ 1);
-            UH_LAUNCH(b->ctx,ba_backsub_kernel<false>, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, ns, slot ^ 1);
+            UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, ns, slot ^ 1);
         }
         b->step++;
     }
@@ -2548,8 +2773,12 @@ void uh_ba_destroy(uh_ba* b) { delete b; }
 
 // setParams for the forms that keep host-built tables: the launch chain (more free keyframes than the persistent kernel is
 // instantiated for, or a window whose fixed frames do not fit its LDS) and the wide form (global BA).  Arrays anywhere in host memory.
-static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr) {
+// (sin: the three-row edges of a stereo / RGB-D problem — NULL on the monocular route, whose tables and arena layout it leaves as they are)
+struct StereoIn { std::vector<double> ur, bf; std::vector<unsigned char> st; double delta3 = 0, chi2_th3 = 0; };
+
+static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const StereoIn* sin = nullptr) {
     b->fast = false;
+    b->stereo = false;
     const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
     std::vector<int> slot(K, -1), free_kf;
     for (int k = 0; k < K; k++) if (!pr->fixed[k]) { slot[k] = (int)free_kf.size(); free_kf.push_back(k); }
@@ -2647,6 +2876,7 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr) {
     const size_t o_pt_ptr = A.take<int>(P + 1), o_pt_edges = A.take<int>(E), o_cam_ptr = A.take<int>(nfree + 1), o_cam_edges = A.take<int>(cam_edges.size());
     const size_t o_e_pt = A.take<int>(E), o_e_kf = A.take<int>(E), o_uv = A.take<double>(2 * (size_t)E), o_w = A.take<double>(E);
     const size_t o_slot = A.take<int>(K), o_free = A.take<int>(std::max(nfree, 1)), o_intr = A.take<double>(4 * (size_t)K), o_edge_of = A.take<int>(edge_of.size());
+    const size_t o_ur = sin ? A.take<double>(E) : 0, o_bf = sin ? A.take<double>(E) : 0, o_est = sin ? A.take<unsigned char>(E) : 0;   // (inside the pinned prefix)
     const size_t o_pose0 = A.take<double>(7 * (size_t)K), o_pts0 = A.take<double>(3 * (size_t)P);
     size_t o_pose[2], o_poseR[2], o_pts[2];
     for (int i = 0; i < 2; i++) { o_pose[i] = A.take<double>(7 * (size_t)K); o_poseR[i] = A.take<double>(12 * (size_t)K); o_pts[i] = A.take<double>(3 * (size_t)P); }
@@ -2735,6 +2965,11 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr) {
         if ((rc = up(o_wt1, w_tri_e1.data(), wn_tri * 4))) return rc;
         if ((rc = up(o_wt2, w_tri_e2.data(), wn_tri * 4))) return rc;
     }
+    if (sin) {
+        if ((rc = up(o_ur, sin->ur.data(), (size_t)E * 8))) return rc;
+        if ((rc = up(o_bf, sin->bf.data(), (size_t)E * 8))) return rc;
+        if ((rc = up(o_est, sin->st.data(), (size_t)E))) return rc;
+    }
     if ((rc = up(o_pose0, pose0.data(), pose0.size() * 8))) return rc;
     if ((rc = up(o_pts0, pts0.data(), pts0.size() * 8))) return rc;
     if ((rc = b->d_poses_in.reserve(16 * (size_t)K * 4))) return rc;
@@ -2775,6 +3010,12 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr) {
     }
     b->d_pose0 = (double*)(base + o_pose0);
     b->d_pts0 = (double*)(base + o_pts0);
+    if (sin) {
+        b->stereo = true;
+        BAStereo& sx = b->sx;
+        sx.e_ur = (const double*)(base + o_ur); sx.e_bf = (const double*)(base + o_bf); sx.e_st = (const unsigned char*)(base + o_est);
+        sx.delta3 = sin->delta3; sx.dsqr3 = sin->delta3 * sin->delta3; sx.chi2_th3 = sin->chi2_th3;
+    }
     b->have_problem = true;
     return UH_OK;
 }
@@ -3090,8 +3331,38 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
     return UH_OK;
 }
 
+// The three-row edges of a problem, for both stereo routes (host arrays and staging block): globaloptimizer_g2o.cpp:253-254 forms
+// mbf = bl * fx and kp_ur = u - mbf / depth in FLOAT; the kernels take them widened.  depth <= 0: a monocular edge.  Indices are
+// checked here (frame_bl is indexed by them).  Returns the number of three-row edges in *n_st when asked.
+static int stereo_edges(const uh_ba_problem* pr, const float* obs_depth, const float* frame_bl, double huber_delta_3d, double chi2_threshold_3d,
+                        const char* who, StereoIn& out, int* n_st = nullptr) {
+    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
+    out.ur.assign(E, 0.0); out.bf.assign(E, 0.0); out.st.assign(E, 0);
+    int n = 0;
+    for (int e = 0; e < E; e++) {
+        const int k = pr->obs_frame[e];
+        UH_REQUIRE(pr->obs_point[e] >= 0 && pr->obs_point[e] < P && k >= 0 && k < K,
+                   "%s: observation %d references point %d / frame %d out of range", who, e, pr->obs_point[e], k);
+        const float depth = obs_depth[e];
+        UH_REQUIRE(std::isfinite(depth), "%s: observation %d has a non-finite depth", who, e);
+        if (!(depth > 0)) continue;
+        const float bl = frame_bl[k];
+        UH_REQUIRE(std::isfinite(bl) && bl > 0, "%s: observation %d has depth %g but frame %d has no finite positive baseline (%g)", who, e, (double)depth, k, (double)bl);
+        const float mbf = bl * pr->intr[4 * k];
+        const float kp_ur = pr->obs_uv[2 * e] - mbf / depth;
+        out.ur[e] = kp_ur; out.bf[e] = mbf; out.st[e] = 1;
+        ++n;
+    }
+    // globaloptimizer_g2o.h:112-117: Chi3D and thHuber3D are floats
+    out.delta3 = huber_delta_3d > 0 ? huber_delta_3d : (double)(float)std::sqrt(7.815f);
+    out.chi2_th3 = chi2_threshold_3d > 0 ? chi2_threshold_3d : (double)7.815f;
+    if (n_st) *n_st = n;
+    return UH_OK;
+}
+
 // The problem that sits in the staging block (either record format), handed to the launch chain / wide form as the arrays it wants.
-static int staged_problem_to_tables(uh_ba* b, int K, int P, int E, bool obs16) {
+static int staged_problem_to_tables(uh_ba* b, int K, int P, int E, bool obs16, const float* obs_depth = nullptr, const float* frame_bl = nullptr,
+                                    double huber_delta_3d = 0, double chi2_threshold_3d = 0) {
     const StageLayout& L = b->slay;
     std::vector<int32_t> op(E), of(E);
     std::vector<float> uv(2 * (size_t)E);
@@ -3113,12 +3384,17 @@ static int staged_problem_to_tables(uh_ba* b, int K, int P, int E, bool obs16) {
     pr.poses_f2g = reinterpret_cast<const float*>(b->h_stage + L.poses_in); pr.fixed = b->h_stage + L.fixed; pr.intr = reinterpret_cast<const float*>(b->h_stage + L.intr_f);
     pr.points = reinterpret_cast<const float*>(b->h_stage + L.points);
     pr.obs_point = op.data(); pr.obs_frame = of.data(); pr.obs_uv = uv.data(); pr.obs_inv_sigma = w.data();
-    return set_problem_tables(b, &pr);
+    if (!obs_depth) return set_problem_tables(b, &pr);
+    StereoIn sin;
+    const int rc = stereo_edges(&pr, obs_depth, frame_bl, huber_delta_3d, chi2_threshold_3d, "uh_ba_set_problem_staged_stereo", sin);
+    if (rc) return rc;
+    return set_problem_tables(b, &pr, &sin);
 }
 
 static void set_problem_begin(uh_ba* b, const uh_ba_params* params) {
     b->have_problem = false;
     b->optimized = false;
+    b->stereo = false;
     if (params) b->params = *params;
     if (b->params.huber_delta <= 0) b->params.huber_delta = std::sqrt(5.99);
     if (b->params.chi2_threshold <= 0) b->params.chi2_threshold = 5.99;
@@ -3258,6 +3534,59 @@ int uh_ba_set_problem_staged(uh_ba* b, int K, int P, int E, const uh_ba_params* 
     return staged_problem_to_tables(b, K, P, E, false);
 }
 
+// setParams with stereo / RGB-D observations.  No observation with depth > 0: exactly uh_ba_set_problem.  Otherwise the launch chain or
+// the wide form with the STEREO kernel instantiations (the persistent form is monocular).
+int uh_ba_set_problem_stereo(uh_ba* b, const uh_ba_problem* pr, const uh_ba_stereo* stereo, const uh_ba_params* params) {
+    UH_REQUIRE(b && pr, "uh_ba_set_problem_stereo: NULL argument");
+    UH_REQUIRE(b->job.load() == 0, "uh_ba_set_problem_stereo: an optimisation is in flight (call uh_ba_wait)");
+    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
+    b->have_problem = false; b->optimized = false;
+    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0, "uh_ba_set_problem_stereo: bad sizes K=%d P=%d E=%d", K, P, E);
+    UH_REQUIRE(pr->poses_f2g && pr->fixed && pr->intr, "uh_ba_set_problem_stereo: NULL frame arrays");
+    if (P > 0) UH_REQUIRE(pr->points, "uh_ba_set_problem_stereo: NULL points");
+    if (E > 0) UH_REQUIRE(pr->obs_point && pr->obs_frame && pr->obs_uv && pr->obs_inv_sigma, "uh_ba_set_problem_stereo: NULL observation arrays");
+    if (E > 0) UH_REQUIRE(stereo && stereo->obs_depth && stereo->frame_bl, "uh_ba_set_problem_stereo: NULL stereo block / obs_depth / frame_bl");
+    StereoIn sin;
+    int n_st = 0;
+    if (E > 0) {
+        const int rc = stereo_edges(pr, stereo->obs_depth, stereo->frame_bl, stereo->huber_delta_3d, stereo->chi2_threshold_3d, "uh_ba_set_problem_stereo", sin, &n_st);
+        if (rc) return rc;
+    }
+    if (n_st == 0) return uh_ba_set_problem(b, pr, params);
+    set_problem_begin(b, params);
+    return set_problem_tables(b, pr, &sin);
+}
+
+int uh_ba_map_staging_stereo(uh_ba* b, int n_frames, int n_points, int max_obs, uh_ba_staging_stereo* out) {
+    UH_REQUIRE(b && out, "uh_ba_map_staging_stereo: NULL argument");
+    uh_ba_staging m{};
+    const int rc = uh_ba_map_staging(b, n_frames, n_points, max_obs, &m);
+    if (rc) return rc;
+    if (b->stage_depth.size() < (size_t)b->cap_E) b->stage_depth.resize(b->cap_E);
+    if (b->stage_bl.size() < (size_t)b->cap_K) b->stage_bl.resize(b->cap_K);
+    out->poses_f2g = m.poses_f2g; out->fixed = m.fixed; out->intr = m.intr; out->points = m.points; out->obs = m.obs;
+    out->obs_depth = b->stage_depth.data(); out->frame_bl = b->stage_bl.data();
+    out->cap_frames = m.cap_frames; out->cap_points = m.cap_points; out->cap_obs = m.cap_obs;
+    return UH_OK;
+}
+
+int uh_ba_set_problem_staged_stereo(uh_ba* b, int K, int P, int E, const uh_ba_params* params, double huber_delta_3d, double chi2_threshold_3d) {
+    UH_REQUIRE(b, "uh_ba_set_problem_staged_stereo: NULL argument");
+    UH_REQUIRE(b->h_stage && b->stage_depth.size() >= (size_t)b->cap_E && b->stage_bl.size() >= (size_t)b->cap_K,
+               "uh_ba_set_problem_staged_stereo: no stereo staging block (call uh_ba_map_staging_stereo first)");
+    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0 && K <= b->cap_K && P <= b->cap_P && E <= b->cap_E,
+               "uh_ba_set_problem_staged_stereo: sizes K=%d P=%d E=%d exceed the mapped capacities %d / %d / %d", K, P, E, b->cap_K, b->cap_P, b->cap_E);
+    b->have_problem = false; b->optimized = false;
+    bool any = false;
+    for (int e = 0; e < E; e++) {
+        UH_REQUIRE(std::isfinite(b->stage_depth[e]), "uh_ba_set_problem_staged_stereo: observation %d has a non-finite depth", e);
+        any = any || b->stage_depth[e] > 0;
+    }
+    if (!any) return uh_ba_set_problem_staged(b, K, P, E, params);
+    set_problem_begin(b, params);
+    return staged_problem_to_tables(b, K, P, E, false, b->stage_depth.data(), b->stage_bl.data(), huber_delta_3d, chi2_threshold_3d);
+}
+
 // the per-observation chi2 is an extra of this ABI (the reference's getResults does not return it): a host that never asks for it saves
 // the kernel three quarters of its result hand-over.  Takes effect with the next set_problem.
 int uh_ba_want_chi2(uh_ba* b, int on) {
@@ -3311,7 +3640,7 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
     UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n1, mc, b->step & 1, 0);
     if ((rc = enqueue_steps(b, n1, true))) return rc;
     UH_LAUNCH(b->ctx,ba_gate_kernel, dim3(1), dim3(64), 0, b->ptrs, b->step & 1);
-    if (d.E > 0) UH_LAUNCH(b->ctx,ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, 1);
+    if (d.E > 0) UH_LAUNCH_BA(b, ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, 1);
     UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n2, mc, b->step & 1, 1);
     if ((rc = enqueue_steps(b, n2, true))) return rc;
     BAState hs;
@@ -3327,7 +3656,7 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
         if (stop_asap && *stop_asap) cont = false;
         if (b->h_stop && *b->h_stop) cont = false;
         if (cont) {
-            if (d.E > 0) UH_LAUNCH(b->ctx,ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, 0);
+            if (d.E > 0) UH_LAUNCH_BA(b, ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, 0);
             UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n2, mc, b->step & 1, 0);
             if ((rc = enqueue_steps(b, n2 + 1, true))) return rc;
             if ((rc = wait_state(b, &hs, stop_asap))) return rc;
@@ -3445,10 +3774,10 @@ int uh_ba_get_results(uh_ba* b, float* poses_out, float* points_out, double* chi
     hipStream_t st = b->ctx->stream;
     const BADims& d = b->dims;
     const int n0 = std::max(d.K, 3 * d.P);
-    UH_LAUNCH(b->ctx,ba_results_kernel, dim3(uh_div_up(std::max(n0, 1), 256)), dim3(256), 0, b->ptrs, d, b->d_poses_in.as<float>(),
+    UH_LAUNCH_BA(b, ba_results_kernel, dim3(uh_div_up(std::max(n0, 1), 256)), dim3(256), 0, b->ptrs, d, b->d_poses_in.as<float>(),
                        b->d_poses_out.as<float>(), b->d_points_out.as<float>(), b->d_bad.as<unsigned char>(), 0, b->step & 1);
     if (d.E > 0)
-        UH_LAUNCH(b->ctx,ba_results_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->d_poses_in.as<float>(),
+        UH_LAUNCH_BA(b, ba_results_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->d_poses_in.as<float>(),
                            b->d_poses_out.as<float>(), b->d_points_out.as<float>(), b->d_bad.as<unsigned char>(), 1, b->step & 1);
     // through ONE pinned block: asynchronous DMA + one synchronisation (four pageable copies each staged and synchronised on their own: 0.16 ms)
     const size_t o_po = 0, o_pt = o_po + ((16 * (size_t)d.K * 4 + 255) & ~(size_t)255), o_bad = o_pt + ((3 * (size_t)d.P * 4 + 255) & ~(size_t)255);
