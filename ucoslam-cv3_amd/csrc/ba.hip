@@ -42,6 +42,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
@@ -197,58 +198,18 @@ __device__ __forceinline__ double readlane_f64(double v, int lane_uniform) {   /
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-struct EdgeLin {          // one edge's linearisation at a given state
-    double ex, ey, chi2, rho1, ww, r0, r1;
-    double A[6], B[12];
+template <int ROWS>
+struct EdgeLinT {         // one edge's linearisation at a given state: ROWS residual rows (ez, r2 and the third rows of A, B only where ROWS == 3)
+    double ex, ey, ez, chi2, rho1, ww, r0, r1, r2;
+    double A[3 * ROWS], B[6 * ROWS];
     double robchi;
 };
+using EdgeLin = EdgeLinT<2>;
 
-// error + Huber weight (+ Jacobians) of edge e with camera pose (R,t) and point X
-// value form (observation, information scalar and intrinsics passed in): shared by the legacy kernels and the persistent kernel
-template <bool JAC>
-__device__ __forceinline__ void edge_eval_v(double u, double v, double w, double fx, double fy, double cx, double cy, double delta, double dsqr,
-                                            const double* Rt, const double* X, bool robust, EdgeLin& o) {
-    const double x = Rt[0] * X[0] + Rt[1] * X[1] + Rt[2] * X[2] + Rt[9];
-    const double y = Rt[3] * X[0] + Rt[4] * X[1] + Rt[5] * X[2] + Rt[10];
-    const double z = Rt[6] * X[0] + Rt[7] * X[1] + Rt[8] * X[2] + Rt[11];
-    o.ex = u - ((x / z) * fx + cx);
-    o.ey = v - ((y / z) * fy + cy);
-    o.chi2 = w * (o.ex * o.ex + o.ey * o.ey);
-    o.rho1 = 1.0;
-    o.robchi = o.chi2;
-    if (robust && o.chi2 > dsqr) {
-        const double sq = sqrt(o.chi2);
-        o.rho1 = delta / sq;
-        o.robchi = 2 * sq * delta - dsqr;
-    }
-    if (JAC) {
-        o.ww = o.rho1 * w;
-        o.r0 = -w * o.ex * o.rho1;
-        o.r1 = -w * o.ey * o.rho1;
-        const double z2 = z * z;
-        const double t02 = -x / z * fx, t12 = -y / z * fy, iz = -1. / z;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            o.A[c] = iz * (fx * Rt[c] + t02 * Rt[6 + c]);
-            o.A[3 + c] = iz * (fy * Rt[3 + c] + t12 * Rt[6 + c]);
-        }
-        o.B[0] = x * y / z2 * fx; o.B[1] = -(1 + (x * x / z2)) * fx; o.B[2] = y / z * fx; o.B[3] = -1. / z * fx; o.B[4] = 0; o.B[5] = x / z2 * fx;
-        o.B[6] = (1 + y * y / z2) * fy; o.B[7] = -x * y / z2 * fy; o.B[8] = -x / z * fy; o.B[9] = 0; o.B[10] = -1. / z * fy; o.B[11] = y / z2 * fy;
-    }
-}
-
-template <bool JAC>
-__device__ __forceinline__ void edge_eval(const BAPtrs& p, const BADims& d, int e, int k, const double* Rt, const double* X,
-                                          bool robust, EdgeLin& o) {
-    edge_eval_v<JAC>(p.e_uv[2 * e], p.e_uv[2 * e + 1], p.e_w[e], p.intr[4 * k], p.intr[4 * k + 1], p.intr[4 * k + 2], p.intr[4 * k + 3],
-                     d.delta, d.dsqr, Rt, X, robust, o);
-}
-
-// ------------------------------------------------------------------------------------------------ stereo / RGB-D edges
 // EdgeStereoSE3ProjectXYZ (typesg2o.h:327-409): an observation with depth has three residual rows (u, v, u_right).  Only the STEREO
 // instantiations of the linearising kernels receive this block, as a trailing kernel argument of their own: BAPtrs / BADims / BAState
-// and every monocular instantiation keep their layout and their code.  An edge without depth inside a stereo problem (e_st == 0)
-// evaluates the monocular expressions above and contributes zeros in the third row.
+// keep their layout, and a monocular instantiation is handed an empty block that it never reads.  An edge without depth inside a
+// stereo problem (e_st == 0) evaluates the monocular expressions and contributes zeros in the third row.
 struct BAStereo {
     const double* e_ur;           // E: right-image column kp_ur (a float, widened); unused where e_st == 0
     const double* e_bf;           // E: baseline * fx of the observing frame (a float product, widened)
@@ -257,75 +218,82 @@ struct BAStereo {
 };
 __device__ __forceinline__ BAStereo stereo_arg() { return BAStereo{}; }
 __device__ __forceinline__ BAStereo stereo_arg(const BAStereo& s) { return s; }
+// How linearize_point / camera_block take that block.  The monocular instantiation takes its empty one by value: a reference to the
+// temporary renumbered registers in ba_lin_kernel<false> and ba_schurw_kernel<false> (same instructions, other v_mov order).
+template <bool STEREO>
+using StereoArg = std::conditional_t<STEREO, const BAStereo&, BAStereo>;
 
-struct EdgeLin3 {         // EdgeLin with a third row
-    double ex, ey, ez, chi2, rho1, ww, r0, r1, r2;
-    double A[9], B[18];
-    double robchi;
-};
+// The Huber step.  Called once per branch of the edge evaluation, each with its own width read straight from its argument block: one
+// call behind a `st ? delta3 : delta` select made the compiler build a table in scratch.
+template <int ROWS>
+__device__ __forceinline__ void edge_huber(EdgeLinT<ROWS>& o, bool robust, double delta, double dsqr) {
+    o.rho1 = 1.0;
+    o.robchi = o.chi2;
+    if (robust && o.chi2 > dsqr) {
+        const double sq = sqrt(o.chi2);
+        o.rho1 = delta / sq;
+        o.robchi = 2 * sq * delta - dsqr;
+    }
+}
 
-template <bool JAC>
-__device__ __forceinline__ void edge_eval_s(const BAPtrs& p, const BADims& d, const BAStereo& sx, int e, int k, const double* Rt, const double* X,
-                                            bool robust, EdgeLin3& o) {
-    const double u = p.e_uv[2 * e], v = p.e_uv[2 * e + 1], w = p.e_w[e];
-    const double fx = p.intr[4 * k], fy = p.intr[4 * k + 1], cx = p.intr[4 * k + 2], cy = p.intr[4 * k + 3];
-    const bool st = sx.e_st[e] != 0;
+// error + Huber weight + Jacobians of one edge with camera pose (R,t) and point X, in value form (observation, information scalar,
+// intrinsics and the two-row Huber width passed in).  One body for two- and three-row edges: everything outside `if constexpr (STEREO)`
+// is the two-row edge of the monocular problem; inside it, `st` marks an edge with depth (sx and e are read there only), and an edge
+// without depth in a stereo problem takes the two-row branch plus zeros in row three.
+template <bool STEREO>
+__device__ __forceinline__ void edge_eval_v(double u, double v, double w, double fx, double fy, double cx, double cy, double delta, double dsqr,
+                                            const double* Rt, const double* X, bool robust, EdgeLinT<STEREO ? 3 : 2>& o, const BAStereo& sx, int e) {
+    bool st = false;
+    if constexpr (STEREO) st = sx.e_st[e] != 0;
     const double x = Rt[0] * X[0] + Rt[1] * X[1] + Rt[2] * X[2] + Rt[9];
     const double y = Rt[3] * X[0] + Rt[4] * X[1] + Rt[5] * X[2] + Rt[10];
     const double z = Rt[6] * X[0] + Rt[7] * X[1] + Rt[8] * X[2] + Rt[11];
     double bf = 0;
-    o.rho1 = 1.0;
-    if (st) {   // cam_project (:399-406): invz is a double quotient rounded to float, bf * invz a float product
-        bf = sx.e_bf[e];
-        const float invzf = (float)(1.0 / z);
-        const double invz = invzf;
-        const double pu = x * invz * fx + cx;
-        const double pv = y * invz * fy + cy;
-        const double pr = pu - (double)((float)bf * invzf);
-        o.ex = u - pu; o.ey = v - pv; o.ez = sx.e_ur[e] - pr;
-        o.chi2 = w * (o.ex * o.ex + o.ey * o.ey + o.ez * o.ez);
-        o.robchi = o.chi2;
-        if (robust && o.chi2 > sx.dsqr3) {   // (the Huber step once per branch: each reads its own width straight from its argument block)
-            const double sq = sqrt(o.chi2);
-            o.rho1 = sx.delta3 / sq;
-            o.robchi = 2 * sq * sx.delta3 - sx.dsqr3;
+    if (st) {
+        if constexpr (STEREO) {   // cam_project (:399-406): invz is a double quotient rounded to float, bf * invz a float product
+            bf = sx.e_bf[e];
+            const float invzf = (float)(1.0 / z);
+            const double invz = invzf;
+            const double pu = x * invz * fx + cx;
+            const double pv = y * invz * fy + cy;
+            const double pr = pu - (double)((float)bf * invzf);
+            o.ex = u - pu; o.ey = v - pv; o.ez = sx.e_ur[e] - pr;
+            o.chi2 = w * (o.ex * o.ex + o.ey * o.ey + o.ez * o.ez);
+            edge_huber(o, robust, sx.delta3, sx.dsqr3);
         }
     } else {
         o.ex = u - ((x / z) * fx + cx);
         o.ey = v - ((y / z) * fy + cy);
-        o.ez = 0;
+        if constexpr (STEREO) o.ez = 0;
         o.chi2 = w * (o.ex * o.ex + o.ey * o.ey);
-        o.robchi = o.chi2;
-        if (robust && o.chi2 > d.dsqr) {
-            const double sq = sqrt(o.chi2);
-            o.rho1 = d.delta / sq;
-            o.robchi = 2 * sq * d.delta - d.dsqr;
-        }
+        edge_huber(o, robust, delta, dsqr);
     }
-    if (JAC) {
-        o.ww = o.rho1 * w;
-        o.r0 = -w * o.ex * o.rho1;
-        o.r1 = -w * o.ey * o.rho1;
-        o.r2 = -w * o.ez * o.rho1;
-        const double z2 = z * z;
-        if (st) {   // linearizeOplus (:352-397)
+    o.ww = o.rho1 * w;
+    o.r0 = -w * o.ex * o.rho1;
+    o.r1 = -w * o.ey * o.rho1;
+    if constexpr (STEREO) o.r2 = -w * o.ez * o.rho1;
+    const double z2 = z * z;
+    if (st) {
+        if constexpr (STEREO) {   // linearizeOplus (:352-397)
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 o.A[c] = -fx * Rt[c] / z + fx * x * Rt[6 + c] / z2;
                 o.A[3 + c] = -fy * Rt[3 + c] / z + fy * y * Rt[6 + c] / z2;
                 o.A[6 + c] = o.A[c] - bf * Rt[6 + c] / z2;
             }
-        } else {
-            const double t02 = -x / z * fx, t12 = -y / z * fy, iz = -1. / z;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                o.A[c] = iz * (fx * Rt[c] + t02 * Rt[6 + c]);
-                o.A[3 + c] = iz * (fy * Rt[3 + c] + t12 * Rt[6 + c]);
-                o.A[6 + c] = 0;
-            }
         }
-        o.B[0] = x * y / z2 * fx; o.B[1] = -(1 + (x * x / z2)) * fx; o.B[2] = y / z * fx; o.B[3] = -1. / z * fx; o.B[4] = 0; o.B[5] = x / z2 * fx;
-        o.B[6] = (1 + y * y / z2) * fy; o.B[7] = -x * y / z2 * fy; o.B[8] = -x / z * fy; o.B[9] = 0; o.B[10] = -1. / z * fy; o.B[11] = y / z2 * fy;
+    } else {
+        const double t02 = -x / z * fx, t12 = -y / z * fy, iz = -1. / z;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            o.A[c] = iz * (fx * Rt[c] + t02 * Rt[6 + c]);
+            o.A[3 + c] = iz * (fy * Rt[3 + c] + t12 * Rt[6 + c]);
+            if constexpr (STEREO) o.A[6 + c] = 0;
+        }
+    }
+    o.B[0] = x * y / z2 * fx; o.B[1] = -(1 + (x * x / z2)) * fx; o.B[2] = y / z * fx; o.B[3] = -1. / z * fx; o.B[4] = 0; o.B[5] = x / z2 * fx;
+    o.B[6] = (1 + y * y / z2) * fy; o.B[7] = -x * y / z2 * fy; o.B[8] = -x / z * fy; o.B[9] = 0; o.B[10] = -1. / z * fy; o.B[11] = y / z2 * fy;
+    if constexpr (STEREO) {
         if (st) {
             o.B[12] = o.B[0] - bf * y / z2; o.B[13] = o.B[1] + bf * x / z2; o.B[14] = o.B[2]; o.B[15] = o.B[3]; o.B[16] = 0; o.B[17] = o.B[5] - bf / z2;
         } else {
@@ -335,12 +303,40 @@ __device__ __forceinline__ void edge_eval_s(const BAPtrs& p, const BADims& d, co
     }
 }
 
+// (the loads stay in a function of their own: the compiler orders commutative operands by whether they are arguments or loads)
+template <bool STEREO>
+__device__ __forceinline__ void edge_eval(const BAPtrs& p, const BADims& d, const BAStereo& sx, int e, int k, const double* Rt, const double* X,
+                                          bool robust, EdgeLinT<STEREO ? 3 : 2>& o) {
+    edge_eval_v<STEREO>(p.e_uv[2 * e], p.e_uv[2 * e + 1], p.e_w[e], p.intr[4 * k], p.intr[4 * k + 1], p.intr[4 * k + 2], p.intr[4 * k + 3],
+                        d.delta, d.dsqr, Rt, X, robust, o, sx, e);
+}
+
+// Sums over an edge's residual rows, in row order (row 1, row 2, then row 3 where there is one).  a and b hold ROWS rows each:
+// entry i of a against entry j of b.
+template <int ROWS, int NA, int NB>
+__device__ __forceinline__ double rows_dot(const double (&a)[NA], int i, const double (&b)[NB], int j) {
+    constexpr int sa = NA / ROWS, sb = NB / ROWS;
+    double s = a[i] * b[j] + a[sa + i] * b[sb + j];
+    if constexpr (ROWS == 3) s = s + a[2 * sa + i] * b[2 * sb + j];
+    return s;
+}
+template <int ROWS, int NA>
+__device__ __forceinline__ double rows_res(const double (&a)[NA], int i, const EdgeLinT<ROWS>& L) {   // against the weighted residual
+    constexpr int sa = NA / ROWS;
+    double s = a[i] * L.r0 + a[sa + i] * L.r1;
+    if constexpr (ROWS == 3) s = s + a[2 * sa + i] * L.r2;
+    return s;
+}
+
 // Linearisation of one landmark by its 8 lanes (one observation each per round; 32 landmarks per workgroup): errors, Huber
 // weights, Hll, bl and the per-edge Hpl blocks at pose set poseR / point X, written to linearisation buffer `buf`.  The 8 partial sums are added with a fixed xor
 // butterfly, so the result is deterministic and identical in all 8 lanes.  Lane gl==0 returns the landmark's robust chi2
 // and max |diag Hll| (others 0).  Used by the lin kernel (current estimate) and by the backsub kernel (trial estimate).
-__device__ __forceinline__ void linearize_point(const BAPtrs& p, const BADims& d, int buf, int pt, int gl, bool live,
+// STEREO: three-row edges, read through sx; same lanes, same butterfly, same outputs (Hll, bl, 6 x 3 Hpl blocks).
+template <bool STEREO>
+__device__ __forceinline__ void linearize_point(const BAPtrs& p, const BADims& d, StereoArg<STEREO> sx, int buf, int pt, int gl, bool live,
                                                 const double* poseR, const double* X, double& chi_part, double& maxd) {
+    constexpr int R = STEREO ? 3 : 2;
     double acc[10];   // Hll upper (6), bl (3), robust chi2 (1)
 #pragma unroll
     for (int i = 0; i < 10; i++) acc[i] = 0;
@@ -351,71 +347,22 @@ __device__ __forceinline__ void linearize_point(const BAPtrs& p, const BADims& d
             if (!p.e_active[e]) continue;
             any = true;
             const int k = p.e_kf[e];
-            EdgeLin L;
-            edge_eval<true>(p, d, e, k, poseR + 12 * k, X, p.e_robust[e] != 0, L);
+            EdgeLinT<R> L;
+            edge_eval<STEREO>(p, d, sx, e, k, poseR + 12 * k, X, p.e_robust[e] != 0, L);
             p.e_err[2 * e] = L.ex; p.e_err[2 * e + 1] = L.ey;
             p.e_chi2[e] = L.chi2;
             acc[9] += L.robchi;
-            acc[0] += L.ww * (L.A[0] * L.A[0] + L.A[3] * L.A[3]); acc[1] += L.ww * (L.A[0] * L.A[1] + L.A[3] * L.A[4]);
-            acc[2] += L.ww * (L.A[0] * L.A[2] + L.A[3] * L.A[5]); acc[3] += L.ww * (L.A[1] * L.A[1] + L.A[4] * L.A[4]);
-            acc[4] += L.ww * (L.A[1] * L.A[2] + L.A[4] * L.A[5]); acc[5] += L.ww * (L.A[2] * L.A[2] + L.A[5] * L.A[5]);
-            acc[6] += L.A[0] * L.r0 + L.A[3] * L.r1; acc[7] += L.A[1] * L.r0 + L.A[4] * L.r1; acc[8] += L.A[2] * L.r0 + L.A[5] * L.r1;
+            // (written out: as a loop over the upper triangle the compiler emits other code for it)
+            acc[0] += L.ww * rows_dot<R>(L.A, 0, L.A, 0); acc[1] += L.ww * rows_dot<R>(L.A, 0, L.A, 1);
+            acc[2] += L.ww * rows_dot<R>(L.A, 0, L.A, 2); acc[3] += L.ww * rows_dot<R>(L.A, 1, L.A, 1);
+            acc[4] += L.ww * rows_dot<R>(L.A, 1, L.A, 2); acc[5] += L.ww * rows_dot<R>(L.A, 2, L.A, 2);
+            acc[6] += rows_res(L.A, 0, L); acc[7] += rows_res(L.A, 1, L); acc[8] += rows_res(L.A, 2, L);
             if (p.slot[k] >= 0) {
                 double* Hx = p.Hpl[buf] + 18 * (size_t)e;
 #pragma unroll
                 for (int a = 0; a < 6; a++)
 #pragma unroll
-                    for (int c = 0; c < 3; c++) Hx[a * 3 + c] = L.ww * (L.B[a] * L.A[c] + L.B[6 + a] * L.A[3 + c]);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 10; i++) {
-#pragma unroll
-        for (int o = kLanesPerPoint / 2; o > 0; o >>= 1) acc[i] += __shfl_xor(acc[i], o);
-    }
-    const unsigned long long anym = __ballot(any);
-    const bool any_pt = ((anym >> ((threadIdx.x & 63) & ~(kLanesPerPoint - 1))) & 0xFFull) != 0;
-    chi_part = 0; maxd = 0;
-    if (live && gl == 0) {
-        double* Hl = p.Hll[buf] + 9 * (size_t)pt;
-        Hl[0] = acc[0]; Hl[1] = acc[1]; Hl[2] = acc[2]; Hl[3] = acc[1]; Hl[4] = acc[3]; Hl[5] = acc[4]; Hl[6] = acc[2]; Hl[7] = acc[4]; Hl[8] = acc[5];
-        double* bo = p.bl[buf] + 3 * (size_t)pt;
-        bo[0] = acc[6]; bo[1] = acc[7]; bo[2] = acc[8];
-        chi_part = acc[9];
-        if (any_pt) maxd = fmax(fabs(acc[0]), fmax(fabs(acc[3]), fabs(acc[5])));
-    }
-}
-
-// linearize_point with three-row edges: same lanes, same butterfly, same outputs (Hll, bl, 6 x 3 Hpl blocks)
-__device__ __forceinline__ void linearize_point_s(const BAPtrs& p, const BADims& d, const BAStereo& sx, int buf, int pt, int gl, bool live,
-                                                  const double* poseR, const double* X, double& chi_part, double& maxd) {
-    double acc[10];   // Hll upper (6), bl (3), robust chi2 (1)
-#pragma unroll
-    for (int i = 0; i < 10; i++) acc[i] = 0;
-    bool any = false;
-    if (live) {
-        for (int i = p.pt_ptr[pt] + gl; i < p.pt_ptr[pt + 1]; i += kLanesPerPoint) {
-            const int e = p.pt_edges[i];
-            if (!p.e_active[e]) continue;
-            any = true;
-            const int k = p.e_kf[e];
-            EdgeLin3 L;
-            edge_eval_s<true>(p, d, sx, e, k, poseR + 12 * k, X, p.e_robust[e] != 0, L);
-            p.e_err[2 * e] = L.ex; p.e_err[2 * e + 1] = L.ey;
-            p.e_chi2[e] = L.chi2;
-            acc[9] += L.robchi;
-            acc[0] += L.ww * (L.A[0] * L.A[0] + L.A[3] * L.A[3] + L.A[6] * L.A[6]); acc[1] += L.ww * (L.A[0] * L.A[1] + L.A[3] * L.A[4] + L.A[6] * L.A[7]);
-            acc[2] += L.ww * (L.A[0] * L.A[2] + L.A[3] * L.A[5] + L.A[6] * L.A[8]); acc[3] += L.ww * (L.A[1] * L.A[1] + L.A[4] * L.A[4] + L.A[7] * L.A[7]);
-            acc[4] += L.ww * (L.A[1] * L.A[2] + L.A[4] * L.A[5] + L.A[7] * L.A[8]); acc[5] += L.ww * (L.A[2] * L.A[2] + L.A[5] * L.A[5] + L.A[8] * L.A[8]);
-            acc[6] += L.A[0] * L.r0 + L.A[3] * L.r1 + L.A[6] * L.r2; acc[7] += L.A[1] * L.r0 + L.A[4] * L.r1 + L.A[7] * L.r2;
-            acc[8] += L.A[2] * L.r0 + L.A[5] * L.r1 + L.A[8] * L.r2;
-            if (p.slot[k] >= 0) {
-                double* Hx = p.Hpl[buf] + 18 * (size_t)e;
-#pragma unroll
-                for (int a = 0; a < 6; a++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) Hx[a * 3 + c] = L.ww * (L.B[a] * L.A[c] + L.B[6 + a] * L.A[3 + c] + L.B[12 + a] * L.A[6 + c]);
+                    for (int c = 0; c < 3; c++) Hx[a * 3 + c] = L.ww * rows_dot<R>(L.B, a, L.A, c);
             }
         }
     }
@@ -440,66 +387,38 @@ __device__ __forceinline__ void linearize_point_s(const BAPtrs& p, const BADims&
 // One (free camera, chunk of its observations) workgroup: partial Hpp (21 upper entries) and bp (6) at the CURRENT estimate;
 // the chunks are added in order by the consumers (lambda init in the schur kernel, assembly in the solve kernel).  Runs in
 // the lin launch when that kernel linearises, else as extra workgroups of the schur launch.
-__device__ __forceinline__ void camera_block(const BAPtrs& p, const BADims& d, int cb, const double* poseR, const double* pts) {
+template <bool STEREO>
+__device__ __forceinline__ void camera_block(const BAPtrs& p, const BADims& d, StereoArg<STEREO> sx, int cb, const double* poseR, const double* pts) {
+    constexpr int R = STEREO ? 3 : 2;
+    // STEREO reduces 28 slots, 27 used: a block_sum_vec instantiation of its own.  One block_sum_vec<27> shared by both forms changed
+    // the address arithmetic the compiler emits for it inside the monocular kernels (same values, other operand order).
+    constexpr int N = STEREO ? 28 : 27;
     const int s = cb / kCamChunks, chunk = cb - s * kCamChunks;
     const int k = p.free_kf[s];
     double Rt[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) Rt[i] = poseR[12 * k + i];
-    double acc[27];
+    double acc[N];
 #pragma unroll
-    for (int i = 0; i < 27; i++) acc[i] = 0;
+    for (int i = 0; i < N; i++) acc[i] = 0;
     for (int i = p.cam_ptr[s] + chunk * kThreads + threadIdx.x; i < p.cam_ptr[s + 1]; i += kCamChunks * kThreads) {
         const int e = p.cam_edges[i];
         if (!p.e_active[e]) continue;
         const int pt = p.e_pt[e];
         const double X[3] = {pts[3 * pt], pts[3 * pt + 1], pts[3 * pt + 2]};
-        EdgeLin L;
-        edge_eval<true>(p, d, e, k, Rt, X, p.e_robust[e] != 0, L);
+        EdgeLinT<R> L;
+        edge_eval<STEREO>(p, d, sx, e, k, Rt, X, p.e_robust[e] != 0, L);
         int q = 0;
 #pragma unroll
         for (int a = 0; a < 6; a++)
 #pragma unroll
-            for (int c = a; c < 6; c++) acc[q++] += L.ww * (L.B[a] * L.B[c] + L.B[6 + a] * L.B[6 + c]);
+            for (int c = a; c < 6; c++) acc[q++] += L.ww * rows_dot<R>(L.B, a, L.B, c);
 #pragma unroll
-        for (int a = 0; a < 6; a++) acc[21 + a] += L.B[a] * L.r0 + L.B[6 + a] * L.r1;
+        for (int a = 0; a < 6; a++) acc[21 + a] += rows_res(L.B, a, L);
     }
-    __shared__ double s_part[4 * 27];
-    __shared__ double s_out27[27];
-    block_sum_vec<27>(acc, s_part, s_out27);
-    if (threadIdx.x < 27) p.HppPart[(size_t)cb * 27 + threadIdx.x] = s_out27[threadIdx.x];
-}
-
-// camera_block with three-row edges
-__device__ __forceinline__ void camera_block_s(const BAPtrs& p, const BADims& d, const BAStereo& sx, int cb, const double* poseR, const double* pts) {
-    const int s = cb / kCamChunks, chunk = cb - s * kCamChunks;
-    const int k = p.free_kf[s];
-    double Rt[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) Rt[i] = poseR[12 * k + i];
-    // 28 slots, 27 used: a block reduction instantiation of its own.  Sharing block_sum_vec<28> with camera_block changed the address
-    // arithmetic the compiler emits for it inside the monocular kernels (same values, other operand order); their code is to stay as it is.
-    double acc[28];
-#pragma unroll
-    for (int i = 0; i < 28; i++) acc[i] = 0;
-    for (int i = p.cam_ptr[s] + chunk * kThreads + threadIdx.x; i < p.cam_ptr[s + 1]; i += kCamChunks * kThreads) {
-        const int e = p.cam_edges[i];
-        if (!p.e_active[e]) continue;
-        const int pt = p.e_pt[e];
-        const double X[3] = {pts[3 * pt], pts[3 * pt + 1], pts[3 * pt + 2]};
-        EdgeLin3 L;
-        edge_eval_s<true>(p, d, sx, e, k, Rt, X, p.e_robust[e] != 0, L);
-        int q = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int c = a; c < 6; c++) acc[q++] += L.ww * (L.B[a] * L.B[c] + L.B[6 + a] * L.B[6 + c] + L.B[12 + a] * L.B[12 + c]);
-#pragma unroll
-        for (int a = 0; a < 6; a++) acc[21 + a] += L.B[a] * L.r0 + L.B[6 + a] * L.r1 + L.B[12 + a] * L.r2;
-    }
-    __shared__ double s_part[4 * 28];
-    __shared__ double s_out27[28];
-    block_sum_vec<28>(acc, s_part, s_out27);
+    __shared__ double s_part[4 * N];
+    __shared__ double s_out27[N];
+    block_sum_vec<N>(acc, s_part, s_out27);
     if (threadIdx.x < 27) p.HppPart[(size_t)cb * 27 + threadIdx.x] = s_out27[threadIdx.x];
 }
 
@@ -522,15 +441,13 @@ __global__ __launch_bounds__(kThreads) void ba_lin_kernel(BAPtrs p, BADims d, in
         const int ptc = live ? pt : 0;
         const double X[3] = {pts[3 * ptc], pts[3 * ptc + 1], pts[3 * ptc + 2]};
         double chi_part, maxd;
-        if constexpr (STEREO) linearize_point_s(p, d, stereo_arg(sx...), cur, pt, gl, live, poseR, X, chi_part, maxd);
-        else linearize_point(p, d, cur, pt, gl, live, poseR, X, chi_part, maxd);
+        linearize_point<STEREO>(p, d, stereo_arg(sx...), cur, pt, gl, live, poseR, X, chi_part, maxd);
         const double cs = block_sum(chi_part, s_red);
         const double mx = block_max(maxd, s_red);
         if (threadIdx.x == 0) { p.part_lin_chi[blockIdx.x] = cs; p.part_maxdiag[blockIdx.x] = mx; }
         UH_BA_CLK(1);
     } else {
-        if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x - d.nPointBlocks, poseR, pts);
-        else camera_block(p, d, blockIdx.x - d.nPointBlocks, poseR, pts);
+        camera_block<STEREO>(p, d, stereo_arg(sx...), blockIdx.x - d.nPointBlocks, poseR, pts);
     }
 }
 template __global__ void ba_lin_kernel<false>(BAPtrs, BADims, int);   // (instantiated here: the monocular kernel keeps its place in the module)
@@ -691,8 +608,7 @@ __global__ __launch_bounds__(kThreads) void ba_schur_kernel(BAPtrs p, BADims d, 
     if (blockIdx.x == 0 && threadIdx.x == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
     if (cam_role) {   // camera workgroups: Hpp / bp partials (the lin kernel has them at the first trial)
         if (!st.first_trial) {
-            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x - npairblocks, p.poseR[st.cur], p.pts[st.cur]);
-            else camera_block(p, d, blockIdx.x - npairblocks, p.poseR[st.cur], p.pts[st.cur]);
+            camera_block<STEREO>(p, d, stereo_arg(sx...), blockIdx.x - npairblocks, p.poseR[st.cur], p.pts[st.cur]);
         }
         return;
     }
@@ -906,8 +822,7 @@ __global__ __launch_bounds__(kThreads) void ba_schur_dense_kernel(BAPtrs p, BADi
     if (blockIdx.x == 0 && tid == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
     if (cam_role) {
         if (!st.first_trial) {
-            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
-            else camera_block(p, d, blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+            camera_block<STEREO>(p, d, stereo_arg(sx...), blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
         }
         UH_DENSE_END(17);
         return;
@@ -974,8 +889,7 @@ __global__ __launch_bounds__(kThreads) void ba_schur_dense_wide_kernel(BAPtrs p,
     if (blockIdx.x == 0 && tid == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
     if (cam_role) {
         if (!st.first_trial) {
-            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
-            else camera_block(p, d, blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
+            camera_block<STEREO>(p, d, stereo_arg(sx...), blockIdx.x, p.poseR[st.cur], p.pts[st.cur]);
         }
         return;
     }
@@ -1933,8 +1847,7 @@ __global__ __launch_bounds__(kThreads) void ba_schurw_kernel(BAPtrs p, BADims d,
     if (st.phase == 2) return;
     if ((int)blockIdx.x >= w.n_items) {
         if (!st.first_trial) {
-            if constexpr (STEREO) camera_block_s(p, d, stereo_arg(sx...), blockIdx.x - w.n_items, p.poseR[st.cur], p.pts[st.cur]);
-            else camera_block(p, d, blockIdx.x - w.n_items, p.poseR[st.cur], p.pts[st.cur]);
+            camera_block<STEREO>(p, d, stereo_arg(sx...), blockIdx.x - w.n_items, p.poseR[st.cur], p.pts[st.cur]);
         }
         return;
     }
@@ -2235,8 +2148,7 @@ __global__ __launch_bounds__(FUSED ? kFusedThreads : kThreads) void ba_backsub_k
         // double-buffered Hll/bl/Hpl: an accepted trial flips both and goes straight to the schur kernel, a rejected one keeps
         // the current estimate with its linearisation intact.  The lin kernel is needed only once per pass.
         double maxd_unused;
-        if constexpr (STEREO) linearize_point_s(p, d, stereo_arg(sx...), trial, pt, gl, live, p.poseR[trial], X, chi_part, maxd_unused);
-        else linearize_point(p, d, trial, pt, gl, live, p.poseR[trial], X, chi_part, maxd_unused);
+        linearize_point<STEREO>(p, d, stereo_arg(sx...), trial, pt, gl, live, p.poseR[trial], X, chi_part, maxd_unused);
     }
     const double cs = block_sum(chi_part, s_red);
     const double ss = block_sum(scale_part, s_red);
@@ -3400,6 +3312,22 @@ static void set_problem_begin(uh_ba* b, const uh_ba_params* params) {
     if (b->params.chi2_threshold <= 0) b->params.chi2_threshold = 5.99;
 }
 
+// The argument checks of the four set_problem entries, under the entry's own name `who`: sizes and array pointers of a host-array
+// problem (pr given), or K, P, E against the mapped capacities of the staging block (pr == nullptr).  (An asymmetry, kept as it is:
+// uh_ba_set_problem_stereo first refuses a call while an optimisation is in flight; uh_ba_set_problem does not.)
+static int check_problem_args(const char* who, const uh_ba* b, const uh_ba_problem* pr, int K, int P, int E) {
+    if (!pr) {
+        UH_REQUIRE(K >= 1 && P >= 0 && E >= 0 && K <= b->cap_K && P <= b->cap_P && E <= b->cap_E,
+                   "%s: sizes K=%d P=%d E=%d exceed the mapped capacities %d / %d / %d", who, K, P, E, b->cap_K, b->cap_P, b->cap_E);
+        return UH_OK;
+    }
+    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0, "%s: bad sizes K=%d P=%d E=%d", who, K, P, E);
+    UH_REQUIRE(pr->poses_f2g && pr->fixed && pr->intr, "%s: NULL frame arrays", who);
+    if (P > 0) UH_REQUIRE(pr->points, "%s: NULL points", who);
+    if (E > 0) UH_REQUIRE(pr->obs_point && pr->obs_frame && pr->obs_uv && pr->obs_inv_sigma, "%s: NULL observation arrays", who);
+    return UH_OK;
+}
+
 extern "C" {
 
 // GlobalOptimizer::setParams: snapshot of everything the optimisation needs (the map may change afterwards)
@@ -3407,15 +3335,13 @@ int uh_ba_set_problem(uh_ba* b, const uh_ba_problem* pr, const uh_ba_params* par
     UH_REQUIRE(b && pr, "uh_ba_set_problem: NULL argument");
     set_problem_begin(b, params);
     const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
-    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0, "uh_ba_set_problem: bad sizes K=%d P=%d E=%d", K, P, E);
-    UH_REQUIRE(pr->poses_f2g && pr->fixed && pr->intr, "uh_ba_set_problem: NULL frame arrays");
-    if (P > 0) UH_REQUIRE(pr->points, "uh_ba_set_problem: NULL points");
-    if (E > 0) UH_REQUIRE(pr->obs_point && pr->obs_frame && pr->obs_uv && pr->obs_inv_sigma, "uh_ba_set_problem: NULL observation arrays");
+    int rc = check_problem_args("uh_ba_set_problem", b, pr, K, P, E);
+    if (rc) return rc;
     int nfree = 0;
     for (int k = 0; k < K; k++) nfree += pr->fixed[k] ? 0 : 1;
     const PersistPlan pl = plan_persistent(b, K, P, E, nfree);
     if (!pl.ok) return set_problem_tables(b, pr);
-    int rc = ensure_staging(b, K, P, E);
+    rc = ensure_staging(b, K, P, E);
     if (rc) return rc;
     const StageLayout& L = b->slay;
     std::memcpy(b->h_stage + L.poses_in, pr->poses_f2g, 16 * (size_t)K * sizeof(float));
@@ -3514,8 +3440,8 @@ int uh_ba_map_staging(uh_ba* b, int n_frames, int n_points, int max_obs, uh_ba_s
 int uh_ba_set_problem_staged(uh_ba* b, int K, int P, int E, const uh_ba_params* params) {
     UH_REQUIRE(b, "uh_ba_set_problem_staged: NULL argument");
     UH_REQUIRE(b->h_stage, "uh_ba_set_problem_staged: no staging block (call uh_ba_map_staging first)");
-    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0 && K <= b->cap_K && P <= b->cap_P && E <= b->cap_E,
-               "uh_ba_set_problem_staged: sizes K=%d P=%d E=%d exceed the mapped capacities %d / %d / %d", K, P, E, b->cap_K, b->cap_P, b->cap_E);
+    const int rc = check_problem_args("uh_ba_set_problem_staged", b, nullptr, K, P, E);
+    if (rc) return rc;
     set_problem_begin(b, params);
     const StageLayout& L = b->slay;
     const uh_ba_obs* ob = reinterpret_cast<const uh_ba_obs*>(b->h_stage + L.obs);
@@ -3540,20 +3466,17 @@ int uh_ba_set_problem_stereo(uh_ba* b, const uh_ba_problem* pr, const uh_ba_ster
     UH_REQUIRE(b && pr, "uh_ba_set_problem_stereo: NULL argument");
     UH_REQUIRE(b->job.load() == 0, "uh_ba_set_problem_stereo: an optimisation is in flight (call uh_ba_wait)");
     const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
-    b->have_problem = false; b->optimized = false;
-    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0, "uh_ba_set_problem_stereo: bad sizes K=%d P=%d E=%d", K, P, E);
-    UH_REQUIRE(pr->poses_f2g && pr->fixed && pr->intr, "uh_ba_set_problem_stereo: NULL frame arrays");
-    if (P > 0) UH_REQUIRE(pr->points, "uh_ba_set_problem_stereo: NULL points");
-    if (E > 0) UH_REQUIRE(pr->obs_point && pr->obs_frame && pr->obs_uv && pr->obs_inv_sigma, "uh_ba_set_problem_stereo: NULL observation arrays");
+    set_problem_begin(b, params);   // (ahead of the checks, as in uh_ba_set_problem: a refused problem leaves none set)
+    int rc = check_problem_args("uh_ba_set_problem_stereo", b, pr, K, P, E);
+    if (rc) return rc;
     if (E > 0) UH_REQUIRE(stereo && stereo->obs_depth && stereo->frame_bl, "uh_ba_set_problem_stereo: NULL stereo block / obs_depth / frame_bl");
     StereoIn sin;
     int n_st = 0;
     if (E > 0) {
-        const int rc = stereo_edges(pr, stereo->obs_depth, stereo->frame_bl, stereo->huber_delta_3d, stereo->chi2_threshold_3d, "uh_ba_set_problem_stereo", sin, &n_st);
+        rc = stereo_edges(pr, stereo->obs_depth, stereo->frame_bl, stereo->huber_delta_3d, stereo->chi2_threshold_3d, "uh_ba_set_problem_stereo", sin, &n_st);
         if (rc) return rc;
     }
     if (n_st == 0) return uh_ba_set_problem(b, pr, params);
-    set_problem_begin(b, params);
     return set_problem_tables(b, pr, &sin);
 }
 
@@ -3574,16 +3497,15 @@ int uh_ba_set_problem_staged_stereo(uh_ba* b, int K, int P, int E, const uh_ba_p
     UH_REQUIRE(b, "uh_ba_set_problem_staged_stereo: NULL argument");
     UH_REQUIRE(b->h_stage && b->stage_depth.size() >= (size_t)b->cap_E && b->stage_bl.size() >= (size_t)b->cap_K,
                "uh_ba_set_problem_staged_stereo: no stereo staging block (call uh_ba_map_staging_stereo first)");
-    UH_REQUIRE(K >= 1 && P >= 0 && E >= 0 && K <= b->cap_K && P <= b->cap_P && E <= b->cap_E,
-               "uh_ba_set_problem_staged_stereo: sizes K=%d P=%d E=%d exceed the mapped capacities %d / %d / %d", K, P, E, b->cap_K, b->cap_P, b->cap_E);
-    b->have_problem = false; b->optimized = false;
+    const int rc = check_problem_args("uh_ba_set_problem_staged_stereo", b, nullptr, K, P, E);
+    if (rc) return rc;
+    set_problem_begin(b, params);   // (a refused problem leaves none set)
     bool any = false;
     for (int e = 0; e < E; e++) {
         UH_REQUIRE(std::isfinite(b->stage_depth[e]), "uh_ba_set_problem_staged_stereo: observation %d has a non-finite depth", e);
         any = any || b->stage_depth[e] > 0;
     }
     if (!any) return uh_ba_set_problem_staged(b, K, P, E, params);
-    set_problem_begin(b, params);
     return staged_problem_to_tables(b, K, P, E, false, b->stage_depth.data(), b->stage_bl.data(), huber_delta_3d, chi2_threshold_3d);
 }
 
