@@ -4,7 +4,7 @@ import sys, os, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np, torch
-import synth, oracle_lib
+import synth, oracle_lib, het_ba_synth
 import ucoslam_cv3_amd as u
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 40.0
@@ -389,6 +389,9 @@ def ba_case2(seed):
                               pose_noise=float(r.choice([0.1, 0.3, 0.6, 1.0])), point_noise=float(r.choice([0.5, 2.0, 5.0, 10.0])))
     else:
         pr = synth.ba_problem(K, P, seed % 100000, nfixed=min(nfix, K - 1), outlier_frac=float(r.choice([0.0, 0.02, 0.1])), pose_noise=float(r.choice([0.005, 0.01, 0.03])))
+    het = r.random() < 0.5   # half of the cases: a camera of its own per keyframe (fx != fy), the fixed keyframes anywhere in the window
+    if het:
+        pr = het_ba_synth.unequal_cameras(pr, r)
     if r.random() < 0.25: os.environ["UH_BA_NF"] = "16"   # the 16-lane instantiation also on windows of up to 8 free keyframes
     else: os.environ.pop("UH_BA_NF", None)
     opt = _ba_stream if r.random() < 0.5 else GlobalOptimizer.create(ctx)
@@ -421,7 +424,7 @@ def ba_case2(seed):
             ok = near_o or near_r
             if ok and not near_o:
                 _waived.append(seed)
-    return ok, (K, P, nfix, nit, form, staged, "hard" if hard else "", g["iters"].tolist(), o["iters"].tolist(), err)
+    return ok, (K, P, nfix, nit, form, staged, "hard" if hard else "", "het" if het else "", g["iters"].tolist(), o["iters"].tolist(), err)
 
 _g2o = oracle_lib.load_ref("g2o")
 _chaotic = []
@@ -438,6 +441,9 @@ def ba_wide_case(seed):   # more than 64 free keyframes: the wide form (sparse p
     K, P, nfix = int(r.integers(67, 120)), int(r.integers(200, 1200)), int(r.integers(1, 3))
     nit = int(r.choice([5, 10]))
     pr = synth.ba_problem(K, P, seed % 100000, nfixed=nfix, outlier_frac=float(r.choice([0.0, 0.02, 0.1])), pose_noise=float(r.choice([0.005, 0.01, 0.03])))
+    het = r.random() < 0.5
+    if het:
+        pr = het_ba_synth.unequal_cameras(pr, r)
     opt = GlobalOptimizer.create(ctx)
     opt.setParams(pr, ParamSet(nIters=nit))
     opt.optimize()
@@ -445,7 +451,7 @@ def ba_wide_case(seed):   # more than 64 free keyframes: the wide form (sparse p
     o = oracle_lib.ba_optimize(L, pr, nit)
     err = float(np.abs(g["state"] - o["state"]).max())
     ok = g["iters"].tolist() == o["iters"].tolist() and err < 1e-6 and (g["bad"] == o["bad"]).mean() > 0.999
-    return ok, (K, P, nfix, nit, g["iters"].tolist(), o["iters"].tolist(), err)
+    return ok, (K, P, nfix, nit, "het" if het else "", g["iters"].tolist(), o["iters"].tolist(), err)
 
 run("ba_wide", ba_wide_case)
 pnp = PnPSolver(ctx)

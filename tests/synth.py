@@ -194,12 +194,12 @@ def vocabulary(k=10, depth=3, seed=0, aligment=8):
     return params, blob.tobytes(), dict(nblocks=nblocks, nwords=word, block_size=block_size)
 
 
-def pnp_problem(n=600, seed=0, outlier_frac=0.15, pose_noise=0.03, pix_noise=0.7, w=1241, h=376):
+def pnp_problem(n=600, seed=0, outlier_frac=0.15, pose_noise=0.03, pix_noise=0.7, w=1241, h=376, intr=None):
     """Synthetic per-frame pose estimation (PnPSolver::solvePnp inputs): n map points seen by one frame, a perturbed initial
-    pose, pixel noise, gross outliers, octave-dependent information and some 'unstable' points with half weight."""
+    pose, pixel noise, gross outliers, octave-dependent information and some 'unstable' points with half weight.
+    intr=(fx, fy, cx, cy): another camera than the default one (fx == fy), e.g. an anisotropic one with its principal point elsewhere."""
     rng = np.random.default_rng(seed)
-    fx = fy = 718.856
-    cx, cy = 607.19, 185.22
+    fx, fy, cx, cy = (718.856, 718.856, 607.19, 185.22) if intr is None else (float(v) for v in intr)
     Tgt = _se3_exp(np.r_[0.01, -0.02, 0.005, 0, 0, 0]) @ np.eye(4)
     Tgt[:3, 3] = [0.4, -0.1, 0.2]
     z = rng.uniform(4, 40, n)
@@ -217,17 +217,20 @@ def pnp_problem(n=600, seed=0, outlier_frac=0.15, pose_noise=0.03, pix_noise=0.7
                 pose_gt=Tgt, outlier=out)
 
 
-def proj_problem(n_kpts=2000, n_pts=3000, seed=0, w=1241, h=376, n_levels=8, low_entropy=False, pose_noise=0.002):
+def proj_problem(n_kpts=2000, n_pts=3000, seed=0, w=1241, h=376, n_levels=8, low_entropy=False, pose_noise=0.002, intr=None):
     """Inputs of Map::matchFrameToMapPoints (map.cpp:651-770): a frame (undistorted keypoints with octaves, descriptors, scale
     factors, intrinsics) and candidate map points (position, mean viewing normal, distance-invariance window, descriptor).
     Two thirds of the map points are back-projections of frame keypoints (descriptor = the keypoint's with a few flipped
     bits), the rest are unrelated (behind the camera, outside the image, wrong scale, ...).  low_entropy=True makes most
-    descriptor distances collide so that the best / second-best bookkeeping and its candidate-order dependence are stressed."""
+    descriptor distances collide so that the best / second-best bookkeeping and its candidate-order dependence are stressed.
+    intr=(fx, fy, cx, cy): another camera than the default one (fx == fy)."""
     import oracle_lib
 
     rng = np.random.default_rng(seed)
     fx = fy = 718.856 if w > 1000 else 517.3
     cx, cy = (607.19, 185.22) if w > 1000 else (318.6, 255.3)
+    if intr is not None:
+        fx, fy, cx, cy = (float(v) for v in intr)
     scale = np.float32(1.2) ** np.arange(n_levels, dtype=np.float32)
     sf = np.ones(n_levels, np.float32)
     for i in range(1, n_levels):

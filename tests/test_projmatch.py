@@ -66,7 +66,16 @@ def test_oracle_proj_match_prev_properties(oracle):
     """The restated tracker search (system.cpp:5930-6460) against an independent numpy/python restatement on a small problem:
     brute-force candidates (no kd-tree) in ascending keypoint order cannot reproduce the candidate ORDER, so the comparison is
     made on problems where the order cannot matter (full-entropy descriptors: no equal distances among candidates)."""
-    fr, mp, pose = synth.proj_problem(600, 900, 11)
+    _prev_search_equals_numpy_restatement(oracle, None)
+
+
+def test_oracle_proj_match_prev_properties_on_an_anisotropic_camera(oracle):
+    """The same on a camera with fx != fy and its principal point elsewhere: the restatement names fx and fy on its own."""
+    _prev_search_equals_numpy_restatement(oracle, (655.1, 742.3, 633.7, 171.4))
+
+
+def _prev_search_equals_numpy_restatement(oracle, camera):
+    fr, mp, pose = synth.proj_problem(600, 900, 11, intr=camera)
     minDesc, maxRepj = 75.0, 7.5
     r = oracle_lib.proj_match_prev(oracle, fr, mp, pose, minDesc, maxRepj)
     T = pose.reshape(4, 4)
@@ -124,6 +133,42 @@ def test_oracle_proj_match_prev_properties(oracle):
         assert r["best_kp"][row] == mm["queryIdx"] and r["best_dist"][row] == mm["distance"]
         rivals = np.nonzero(r["best_kp"] == mm["queryIdx"])[0]
         assert mm["distance"] == r["best_dist"][rivals].min()
+
+
+ANISO = (655.1, 742.3, 633.7, 171.4)    # fx != fy, principal point off the default one: every case below has fx == fy
+ANISO_CFG = dict(n_kpts=2000, n_pts=3000, seed=21, intr=ANISO)
+
+
+def test_oracle_proj_match_on_an_anisotropic_camera_notices_swapped_focal_lengths(oracle):
+    """The anisotropic scene of the GPU tests proves something only if the answer depends on which focal length is which."""
+    fr, mp, pose = synth.proj_problem(**ANISO_CFG)
+    assert (fr["fx"], fr["fy"], fr["cx"], fr["cy"]) == ANISO
+    sw = dict(fr, fx=fr["fy"], fy=fr["fx"])
+    a, b = oracle_lib.proj_match(oracle, fr, mp, pose, 100.0, 15.0), oracle_lib.proj_match(oracle, sw, mp, pose, 100.0, 15.0)
+    assert len(a["matches"]) > 500 and a["matches"].tobytes() != b["matches"].tobytes()
+    assert (a["best_kp"] != b["best_kp"]).sum() > 100 and (a["visible"] != b["visible"]).any()
+    # the oracle's visibility flags against brute force in numpy (double), away from every threshold: its projection names fx, fy itself
+    T = pose.reshape(4, 4).astype(np.float64)
+    X = mp["pos3d"].astype(np.float64)
+    cc = -T[:3, :3].T @ T[:3, 3]
+    view = cc - X
+    cos = np.einsum("ij,ij->i", view / np.linalg.norm(view, axis=1, keepdims=True), mp["normal"].astype(np.float64))
+    pc = X @ T[:3, :3].T + T[:3, 3]
+    dist = np.linalg.norm(pc, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = ANISO[0] * pc[:, 0] / pc[:, 2] + ANISO[2], ANISO[1] * pc[:, 1] / pc[:, 2] + ANISO[3]
+    lo, hi = 0.8 * mp["min_dist"].astype(np.float64), 1.2 * mp["max_dist"].astype(np.float64)
+    brute = (cos >= 0.5) & (pc[:, 2] >= 0) & (lo < dist) & (dist < hi) & (u > 0) & (v > 0) & (u < fr["max_xy"][0]) & (v < fr["max_xy"][1])
+    near = (np.abs(cos - 0.5) < 1e-4) | (np.abs(pc[:, 2]) < 1e-4) | (np.abs(dist / lo - 1) < 1e-4) | (np.abs(dist / hi - 1) < 1e-4)
+    near |= (np.abs(u) < 0.05) | (np.abs(v) < 0.05) | (np.abs(u - fr["max_xy"][0]) < 0.05) | (np.abs(v - fr["max_xy"][1]) < 0.05)
+    assert near.mean() < 0.02 and 500 < brute.sum() < len(brute) - 300
+    np.testing.assert_array_equal(a["visible"][~near], brute[~near].astype(np.uint8))
+    a, b = oracle_lib.proj_match_prev(oracle, fr, mp, pose, 75.0, 7.5), oracle_lib.proj_match_prev(oracle, sw, mp, pose, 75.0, 7.5)
+    assert len(a["matches"]) > 200 and (a["best_kp"] != b["best_kp"]).sum() > 100
+    d = synth.proj_problem(300, 200, 5)                      # the default camera is unchanged by the new argument
+    e = synth.proj_problem(300, 200, 5, intr=(718.856, 718.856, 607.19, 185.22))
+    assert all(np.asarray(d[1][k]).tobytes() == np.asarray(e[1][k]).tobytes() for k in d[1]) and d[2].tobytes() == e[2].tobytes()
+    assert d[0]["und_kpts"].tobytes() == e[0]["und_kpts"].tobytes()
 
 
 # ------------------------------------------------------------------------------------------------ GPU
@@ -297,3 +342,30 @@ def test_hip_projmatch_discs_wider_than_64_leaves_take_the_serial_walk(hip_ctx, 
     np.testing.assert_array_equal(got["best_kp"], ref["best_kp"])
     np.testing.assert_array_equal(got["best_dist"], ref["best_dist"])
     assert got["matches"].tobytes() == ref["matches"].tobytes()
+
+
+@pytest.mark.gpu
+def test_hip_projmatch_on_an_anisotropic_camera_matches_oracle(hip_ctx, oracle):
+    """Both match loops on a camera with fx != fy and its principal point elsewhere, bit-exact against the oracle, with the tree in LDS."""
+    from ucoslam_cv3_amd.projmatch import ProjectionMatcher
+
+    fr, mp, pose = synth.proj_problem(**ANISO_CFG)
+    pm = ProjectionMatcher(hip_ctx)
+    pm.setFrame(fr["und_kpts"], fr["desc"], fr["scale_factors"], fr["fx"], fr["fy"], fr["cx"], fr["cy"], fr["min_xy"], fr["max_xy"])
+    for minDesc, maxRepj in ((100.0, 15.0), (8.0, 15.0), (50.0, 2.5)):
+        got = pm.matchFrameToMapPoints(pose, mp["ids"], mp["pos3d"], mp["normal"], mp["min_dist"], mp["max_dist"], mp["desc"], minDesc, maxRepj)
+        ref = oracle_lib.proj_match(oracle, fr, mp, pose, minDesc, maxRepj)
+        np.testing.assert_array_equal(got["visible"], ref["visible"])
+        np.testing.assert_array_equal(got["best_kp"], ref["best_kp"])
+        np.testing.assert_array_equal(got["best_dist"][ref["best_kp"] >= 0], ref["best_dist"][ref["best_kp"] >= 0])
+        assert got["matches"].tobytes() == ref["matches"].tobytes()
+    assert len(oracle_lib.proj_match(oracle, fr, mp, pose, 100.0, 15.0)["matches"]) > 500
+    total = 0
+    for minDesc, maxRepj in ((75.0, 7.5), (100.0, 15.0), (20.0, 2.5)):
+        got = pm.matchFrameToPrevFrame(pose, mp["ids"], mp["pos3d"], mp["octave"], mp["desc"], minDesc, maxRepj)
+        ref = oracle_lib.proj_match_prev(oracle, fr, mp, pose, minDesc, maxRepj)
+        np.testing.assert_array_equal(got["best_kp"], ref["best_kp"])
+        np.testing.assert_array_equal(got["best_dist"], ref["best_dist"])
+        assert got["matches"].tobytes() == ref["matches"].tobytes()
+        total += len(ref["matches"])
+    assert total > 300

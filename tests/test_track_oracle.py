@@ -187,3 +187,32 @@ def test_oracle_empty_inputs(oracle, kpts):
     sc["fr"] = TS.frame(np.zeros(0, oracle_lib.KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8))
     o = _track(oracle, sc)
     assert not o["tracked"] and len(o["matches_all"]) == 0 and o["pose2"].tobytes() == sc["pose0"].tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ another camera than the default one
+def test_scene_camera_argument_leaves_the_default_scene_unchanged(kpts):
+    a, b = TS.scene(*kpts, 5), TS.scene(*kpts, 5, intr=(TS.FX, TS.FY, TS.CX, TS.CY))
+    for part in ("table", "prev", "fr"):
+        for k in a[part]:
+            assert np.asarray(a[part][k]).tobytes() == np.asarray(b[part][k]).tobytes(), (part, k)
+    assert a["pose0"].tobytes() == b["pose0"].tobytes() and a["intr"].tobytes() == TS.INTR.tobytes()
+    assert TS.depths(a, 5).tobytes() == TS.depths(b, 5, intr=(TS.FX, TS.FY, TS.CX, TS.CY)).tobytes()
+
+
+@pytest.mark.parametrize("stereo", [False, True], ids=["mono", "stereo"])
+def test_oracle_on_an_anisotropic_camera_notices_swapped_focal_lengths(oracle, kpts, stereo):
+    """The scene the GPU tests compare on (TS.ANISO, fx != fy, principal point elsewhere) proves something only if the answer depends on
+    which focal length is which: the same scene with fx and fy swapped in the frame gives other matches and another pose."""
+    sc = TS.scene(*kpts, 41, intr=TS.ANISO)
+    assert sc["fr"]["fx"] != sc["fr"]["fy"] and sc["intr"].tolist() == np.array(TS.ANISO, np.float32).tolist()
+    dep = TS.depths(sc, 41) if stereo else None
+    if stereo:
+        assert 0.4 < (dep > 0).mean() < 0.8
+    o = _track(oracle, sc, depth=dep, bl=TS.BL)
+    assert o["tracked"] and o["inliers1"] > 100 and o["inliers2"] > 100
+    sw = dict(sc)
+    sw["fr"] = dict(sc["fr"], fx=sc["fr"]["fy"], fy=sc["fr"]["fx"])
+    w = _track(oracle, sw, depth=dep, bl=TS.BL)
+    assert w["matches_prev"].tobytes() != o["matches_prev"].tobytes() and w["matches_all"].tobytes() != o["matches_all"].tobytes()
+    assert np.abs(w["pose2"] - o["pose2"]).max() > 1e-3 or not w["tracked"]     # (the comparison's pose tolerance is 1e-5)
+    assert w["inliers2"] != o["inliers2"]

@@ -17,19 +17,20 @@ POSE_TOL = 1e-5
 MODES = ["mono", "stereo_prev_weight", "stereo_depth", "stereo_no_depth"]
 
 
-def _frame(hip_ctx, seed, blank=False):
+def _frame(hip_ctx, seed, blank=False, intr=None):
     from ucoslam_cv3_amd.orb import Camera, DeviceFrame, FeatParams, ORBextractor
     from ucoslam_cv3_amd.projmatch import ProjectionMatcher
 
+    fx, fy, cx, cy = (TS.FX, TS.FY, TS.CX, TS.CY) if intr is None else intr
     ext = ORBextractor(hip_ctx)
-    ext.setCamera(Camera(TS.FX, TS.FY, TS.CX, TS.CY, ()))
+    ext.setCamera(Camera(fx, fy, cx, cy, ()))
     fr = DeviceFrame(hip_ctx).setTreeBuilder(False)
     img = np.full((TS.H, TS.W), 90, np.uint8) if blank else synth.frame(TS.W, TS.H, seed=seed)
     kps, desc, und = ext.extractFrameDev(img, fr, FeatParams(maxFeatures=2000, nOctaveLevels=8, scaleFactor=1.2))
     ukp = kps.copy()
     ukp["x"], ukp["y"] = und[:, 0], und[:, 1]
     pm = ProjectionMatcher(hip_ctx)
-    pm.setFrameDev(fr, TS.SF, TS.FX, TS.FY, TS.CX, TS.CY, (0, 0), (TS.W, TS.H), und_kpts=ukp)
+    pm.setFrameDev(fr, TS.SF, fx, fy, cx, cy, (0, 0), (TS.W, TS.H), und_kpts=ukp)
     return dict(pm=pm, ukp=ukp, desc=np.ascontiguousarray(desc).reshape(-1, 32), keep=(ext, fr))
 
 
@@ -48,8 +49,8 @@ def _fused(F, pnp, sc, mode, depth, **kw):
     h = TS.hip_inputs(sc)
     if mode == "mono":
         assert all(sc["table"]["stable"][np.isin(sc["table"]["ids"], h["prev"]["ids"]) & ~np.isin(sc["table"]["ids"], sc["local_ids"])])
-        return F["pm"].trackPose(pnp, sc["pose0"], TS.INTR, TS.INV_SF, h["prev"], h["mp"], prev_map_row=h["prev_row"], map_weight=h["map_weight"], **kw)
-    return F["pm"].trackPoseStereo(pnp, sc["pose0"], TS.INTR, TS.INV_SF, h["prev"], h["mp"], depth=depth, bl=TS.BL, prev_weight=h["prev_weight"],
+        return F["pm"].trackPose(pnp, sc["pose0"], sc["intr"], TS.INV_SF, h["prev"], h["mp"], prev_map_row=h["prev_row"], map_weight=h["map_weight"], **kw)
+    return F["pm"].trackPoseStereo(pnp, sc["pose0"], sc["intr"], TS.INV_SF, h["prev"], h["mp"], depth=depth, bl=TS.BL, prev_weight=h["prev_weight"],
                                    prev_map_row=h["prev_row"], map_weight=h["map_weight"], **kw)
 
 
@@ -157,3 +158,20 @@ def test_fused_tracker_first_solve_outliers_and_seen_points(hip_ctx, oracle, mod
     local = set(sc["local_ids"].tolist())
     assert np.mean([int(v) in local for v in o["matches_prev"]["trainIdx"]]) >= 0.5
     assert set(o["matches_prev"]["trainIdx"][o["bad_prev"] != 0].tolist()) & set(o["matches_all"]["trainIdx"].tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_fused_tracker_agrees_with_oracle_on_an_anisotropic_camera(hip_ctx, oracle, mode):
+    """fx != fy and a principal point elsewhere (TS.ANISO): every other scene has fx == fy, where swapping the two in a projection or a
+    Jacobian row changes nothing.  tests/test_track_oracle.py shows that the oracle's answer on this scene depends on which is which."""
+    from ucoslam_cv3_amd.pnp import PnPSolver
+
+    pnp = PnPSolver(hip_ctx)
+    for seed, kw in ((41, {}), (42, dict(n_prev=1500, n_map=6500))):   # (the last: lists too long for LDS)
+        F = _frame(hip_ctx, seed, intr=TS.ANISO)
+        sc = TS.scene(F["ukp"], F["desc"], seed, stable_outside=(mode == "mono"), intr=TS.ANISO, **kw)
+        assert sc["intr"][0] != sc["intr"][1]
+        depth = _depth(sc, mode, seed)
+        o = _agree(oracle, sc, _fused(F, pnp, sc, mode, depth), depth, f"aniso {mode} seed {seed}")
+        assert o["tracked"] and o["inliers2"] > 100, (seed, o["inliers1"], o["inliers2"])

@@ -147,3 +147,37 @@ def test_track_pose_stereo_refuses_bad_rows_and_baseline(hip_ctx):
     with pytest.raises(UcoslamHipError):
         _fused(sc, pnp, depth=_depths(sc, 7, 1200), bl=0.0)
     _fused(sc, pnp, depth=_depths(sc, 7, 1200), bl=BL)   # the session is still usable
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("host_tree", [False, True], ids=["device_tree", "host_tree"])
+def test_track_pose_stereo_on_an_anisotropic_camera_agrees_with_oracle(hip_ctx, oracle, host_tree):
+    """uh_track_pose_stereo with depths and previous-frame weights on a camera with fx != fy and its principal point elsewhere, against
+    oracle_track_pose (every scene above has fx == fy), with both kd-tree builders.  Comparison rule and exact-equality assertions:
+    tests/test_track_oracle_gpu.py::_agree."""
+    import synth
+    import track_scenes as TS
+    from test_track_oracle_gpu import _agree
+    from ucoslam_cv3_amd.orb import Camera, DeviceFrame, FeatParams, ORBextractor
+    from ucoslam_cv3_amd.pnp import PnPSolver
+    from ucoslam_cv3_amd.projmatch import ProjectionMatcher
+
+    fx, fy, cx, cy = TS.ANISO
+    pnp = PnPSolver(hip_ctx)
+    ext = ORBextractor(hip_ctx)
+    ext.setCamera(Camera(fx, fy, cx, cy, ()))
+    fr = DeviceFrame(hip_ctx).setTreeBuilder(host_tree)
+    kps, desc, und = ext.extractFrameDev(synth.frame(TS.W, TS.H, seed=43), fr, FeatParams(maxFeatures=2000, nOctaveLevels=8, scaleFactor=1.2))
+    ukp = kps.copy()
+    ukp["x"], ukp["y"] = und[:, 0], und[:, 1]
+    pm = ProjectionMatcher(hip_ctx)
+    pm.setFrameDev(fr, TS.SF, fx, fy, cx, cy, (0, 0), (TS.W, TS.H), und_kpts=ukp)
+    sc = TS.scene(ukp, np.ascontiguousarray(desc).reshape(-1, 32), 43, intr=TS.ANISO)
+    depth = TS.depths(sc, 43)
+    assert 0.4 < (depth > 0).mean() < 0.8
+    h = TS.hip_inputs(sc)
+    assert (h["prev_weight"] < 1).any() and (h["prev_row"] < 0).any()
+    f = pm.trackPoseStereo(pnp, sc["pose0"], sc["intr"], TS.INV_SF, h["prev"], h["mp"], depth=depth, bl=TS.BL, prev_weight=h["prev_weight"],
+                           prev_map_row=h["prev_row"], map_weight=h["map_weight"])
+    o = _agree(oracle, sc, f, depth, f"aniso stereo host_tree {host_tree}")
+    assert o["tracked"] and o["inliers2"] > 100

@@ -8,23 +8,32 @@ FX, FY, CX, CY = 718.856, 718.856, 607.19, 185.22
 SF = np.cumprod(np.concatenate([[np.float32(1)], np.full(7, np.float32(1.2))]).astype(np.float32)).astype(np.float32)
 INV_SF = (np.float32(1) / SF).astype(np.float32)
 INTR = np.array([FX, FY, CX, CY], np.float32)
+ANISO = (655.1, 742.3, 633.7, 171.4)   # an anisotropic camera with its principal point elsewhere (fx, fy, cx, cy), for the intr= arguments
 BL = 0.54
 _A = 0.01
 R0 = np.array([[np.cos(_A), 0, np.sin(_A)], [0, 1, 0], [-np.sin(_A), 0, np.cos(_A)]])
 T0 = np.array([0.3, -0.05, 0.1])
 
 
-def frame(ukp, desc):
-    """The oracle's frame dict (synth.proj_problem's layout) for undistorted keypoints ukp (KEYPOINT_DTYPE) and their descriptors."""
-    return dict(und_kpts=np.ascontiguousarray(ukp), desc=np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), scale_factors=SF, fx=FX, fy=FY, cx=CX, cy=CY,
+def _camera(intr):
+    return (FX, FY, CX, CY) if intr is None else tuple(float(v) for v in intr)
+
+
+def frame(ukp, desc, intr=None):
+    """The oracle's frame dict (synth.proj_problem's layout) for undistorted keypoints ukp (KEYPOINT_DTYPE) and their descriptors.
+    intr=(fx, fy, cx, cy) replaces the module's camera."""
+    fx, fy, cx, cy = _camera(intr)
+    return dict(und_kpts=np.ascontiguousarray(ukp), desc=np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), scale_factors=SF, fx=fx, fy=fy, cx=cx, cy=cy,
                 min_xy=(0, 0), max_xy=(W, H))
 
 
-def scene(ukp, desc, seed, n_prev=800, n_map=3000, pose_noise=0.0, in_map=0.7, unstable=0.2, stable_outside=False, uv_noise=0.7):
+def scene(ukp, desc, seed, n_prev=800, n_map=3000, pose_noise=0.0, in_map=0.7, unstable=0.2, stable_outside=False, uv_noise=0.7, intr=None):
     """n_map local-map points (ids 10...) and n_prev previous-frame items, a fraction `in_map` of them local-map points themselves (same
     id, hence the same position and stability), the others points of the table outside the local map (ids 100000...: a copy of a local
     point's geometry and descriptor under an id of their own).  unstable: the fraction of non-stable points (weight 0.5);
-    stable_outside: every point outside the local map is stable (uh_track_pose has no weight input for those)."""
+    stable_outside: every point outside the local map is stable (uh_track_pose has no weight input for those).
+    intr=(fx, fy, cx, cy) replaces the module's camera; the scene carries its camera as "intr" (float32[4])."""
+    FX, FY, CX, CY = _camera(intr)
     rng = np.random.default_rng(seed)
     n_k = len(ukp)
     und = np.stack([ukp["x"], ukp["y"]], 1).astype(np.float64)
@@ -63,12 +72,14 @@ def scene(ukp, desc, seed, n_prev=800, n_map=3000, pose_noise=0.0, in_map=0.7, u
     T[:3, :3], T[:3, 3] = R0, T0
     if pose_noise:
         T[:3, 3] += rng.normal(0, pose_noise, 3)
-    return dict(fr=frame(ukp, desc), table=table, prev=prev, local_ids=local["ids"].copy(), pose0=np.ascontiguousarray(T.astype(np.float32).reshape(16)))
+    return dict(fr=frame(ukp, desc, intr), table=table, prev=prev, local_ids=local["ids"].copy(), pose0=np.ascontiguousarray(T.astype(np.float32).reshape(16)),
+                intr=np.array([FX, FY, CX, CY], np.float32))
 
 
-def depths(sc, seed, frac=0.6):
+def depths(sc, seed, frac=0.6, intr=None):
     """Per keypoint: the camera z of a table point that projects onto it (0.5 % noise), else a depth drawn in [4, 40); then none (0 or
-    < 0) for a fraction 1 - frac of the keypoints."""
+    < 0) for a fraction 1 - frac of the keypoints.  intr: the camera that projects (default: the scene's own)."""
+    FX, FY, CX, CY = _camera(sc["intr"] if intr is None else intr)
     rng = np.random.default_rng(500 + seed)
     kp = sc["fr"]["und_kpts"]
     n = len(kp)
@@ -110,8 +121,10 @@ def _prev_with_pos(sc):
     return dict(ids=sc["prev"]["ids"], pos3d=np.ascontiguousarray(t["pos3d"][tr].reshape(-1, 3)), octave=sc["prev"]["octave"], desc=sc["prev"]["desc"]), tr
 
 
-def shift_point(sc, table_row, rng, lo=6.0, hi=10.0):
-    """Move one table point so that it projects lo..hi px from where it did at pose0 (inside the 15 px disc, chi2 above 5.99 at octave 0)."""
+def shift_point(sc, table_row, rng, lo=6.0, hi=10.0, intr=None):
+    """Move one table point so that it projects lo..hi px from where it did at pose0 (inside the 15 px disc, chi2 above 5.99 at octave 0).
+    intr: the camera that projects (default: the scene's own)."""
+    FX, FY, _, _ = _camera(sc["intr"] if intr is None else intr)
     P = sc["pose0"].reshape(4, 4).astype(np.float64)
     R, t = P[:3, :3], P[:3, 3]
     Xc = R @ sc["table"]["pos3d"][table_row].astype(np.float64) + t
