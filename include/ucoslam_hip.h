@@ -629,8 +629,8 @@ int    uh_fstream_finish_dev(uh_fstream* fs, uh_keypoint* d_kps, uint8_t* d_desc
                              uint8_t* d_bow_valid, int32_t* d_overflow);
 
 /* ------------------------------------------------------------------------
- * Pose-only optimisation — replaces PnPSolver::solvePnp (monocular matches, no markers):
- *   src/optimization/pnpsolver.h:30-38, pnpsolver.cpp:116-409; edge type typesg2o.h:590-650; kernel :82-105.
+ * Pose-only optimisation — replaces PnPSolver::solvePnp (monocular, stereo / RGB-D matches and squared planar markers):
+ *   src/optimization/pnpsolver.h:30-38, pnpsolver.cpp:116-409; edge types typesg2o.h:414-471, :521-650; kernel :82-105.
  * Inputs per match i: map point p3d[i] (float xyz, MapPoint::getCoordinates), undistorted keypoint kp[i] (float x,y),
  * inv_sigma[i] = 1/scaleFactors[octave] (float, :230), weight[i] = 1 or 0.5 for unstable points (:215-216).
  * Outputs: pose (row-major 4x4 float), bad[i] (1 = outlier: the reference marks DMatch::imgIdx = -1), outer iterations of the
@@ -659,6 +659,31 @@ int  uh_pnp_solve_stereo(uh_pnp* pnp, const float* pose_f2g, const float* intr4,
 int  uh_pnp_solve_stereo_dev(uh_pnp* pnp, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                              const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, void* d_work,
                              float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7);
+/* Marker observations (pnpsolver.cpp:280-386): one MarkerEdgeOnlyProject (typesg2o.h:414-471) per marker in the same optimisation as the
+ * keypoint edges.  The caller selects the markers as :281-299 does (the frame's markers with a valid pose_g2m that a neighbour keyframe of
+ * currentKeyFrame sees) and flattens them; the solver does the rest as the reference: weight_marker = (0.3f * (n + markers) / (1 - 0.3f)) /
+ * float(sum of the kernel weights) (+inf without matches), projections rounded to float, g2o's numeric Jacobian with delta = 1e-4f, one Huber
+ * decision per marker (sqrt(15.507)), the kernel dropped for good when the marker's chi2 exceeds 15.507 after a round or from the third
+ * round on.  Markers are never excluded and never counted: the return value stays the number of good keypoint matches.  With markers all
+ * four rounds run (no stop below 10 good matches), and n = 0 matches is valid (p3d, kp, inv_sigma, weight and bad_out may then be NULL).
+ * markers == NULL or markers->n == 0 returns what uh_pnp_solve_stereo returns, bit for bit (n = 0 too: pose in, 0).  Refused before anything
+ * is launched: NULL arrays with n > 0, n outside [0, UH_PNP_MAX_MARKERS], a non-finite or non-positive size. */
+#define UH_PNP_MAX_MARKERS 32
+typedef struct uh_pnp_markers {
+    int32_t n;                 /* marker_poses.size() after the caller's selection (pnpsolver.cpp:281-299); 0..UH_PNP_MAX_MARKERS */
+    const float* pose_g2m;     /* n x 16, row-major 4x4: Marker::pose_g2m */
+    const float* size;         /* n: Marker::size */
+    const float* und_corners;  /* n x 8: MarkerObservation::und_corners, x0 y0 .. x3 y3 */
+} uh_pnp_markers;
+int  uh_pnp_solve_markers(uh_pnp* pnp, const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp,
+                          const float* inv_sigma, const float* weight, const float* depth /* or NULL */, float bl,
+                          const uh_pnp_markers* markers /* or NULL */, float* pose_out, uint8_t* bad_out, int32_t* iters_out4,
+                          double* state_out7);
+/* device-resident form: the three arrays of `markers` are device arrays as well (the sizes are not read on the host); one asynchronous launch */
+int  uh_pnp_solve_markers_dev(uh_pnp* pnp, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
+                              const float* d_inv_sigma, const float* d_weight, const float* d_depth /* or NULL */, float bl,
+                              const uh_pnp_markers* markers /* or NULL */, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
+                              int32_t* d_result5, double* d_state7);
 
 /* ------------------------------------------------------------------------
  * Projection matcher — replaces Map::matchFrameToMapPoints (src/map.cpp:651-770) on flattened inputs:
@@ -779,6 +804,13 @@ typedef struct uh_track_stereo {
     const float* prev_weight;
 } uh_track_stereo;
 int  uh_track_pose_stereo(uh_projmatch* pm, uh_pnp* pnp, const uh_track_args* args, const uh_track_stereo* stereo, uh_track_result* result);
+/* uh_track_pose_stereo for a host that runs with markers: the same markers enter BOTH solves as in uh_pnp_solve_markers (currentKeyFrame is
+ * the same in both reference calls).  Everything else stays as documented above: the first solve runs only with MORE than min_inliers
+ * matches, the frame is tracked iff that solve has MORE than min_inliers inliers (markers are never counted) — a host that wants a
+ * marker-only pose for a frame with too few matches calls uh_pnp_solve_markers itself.  Still one wait and no extra launch.  stereo and
+ * markers may each be NULL; markers == NULL or markers->n == 0 is uh_track_pose_stereo (uh_track_pose when stereo is NULL as well). */
+int  uh_track_pose_markers(uh_projmatch* pm, uh_pnp* pnp, const uh_track_args* args, const uh_track_stereo* stereo /* or NULL */,
+                           const uh_pnp_markers* markers /* or NULL */, uh_track_result* result);
 /* test hook: the flattened kd-tree of the current frame (24-byte nodes {float divlow, divhigh; int32 left, right, leaf_begin;
  * int16 leaf_count, col}), the leaf index list, the root box {x.min, x.max, y.min, y.max} and the tree depth */
 int  uh_projmatch_debug_tree(uh_projmatch* pm, int32_t* n_nodes, const void** nodes24, const uint32_t** leaf_idx,

@@ -311,6 +311,33 @@ class PnPSolver {
         bad.resize(n);
         return rc;
     }
+    // a marker of the frame as solvePnp's marker_poses holds it (pnpsolver.cpp:281-299: the frame's markers with a valid pose_g2m that a
+    // neighbour keyframe of currentKeyFrame sees — the selection stays the caller's)
+    struct Marker {
+        float pose_g2m[16];    // ucoslam::Marker::pose_g2m, row-major 4x4
+        float size;            // ucoslam::Marker::size
+        float und_corners[8];  // ucoslam::MarkerObservation::und_corners: x0 y0 .. x3 y3
+    };
+    // keypoint matches and markers in one optimisation (pnpsolver.cpp:280-386); depth may be NULL (monocular frame).  n = 0 with markers is
+    // a valid, marker-only solve.  The return value stays the number of good keypoint matches.
+    int solvePnp(float* pose_io, const float intr4[4], int n, const float* p3d, const float* kp, const float* inv_sigma, const float* weight,
+                 const float* depth, float bl, const std::vector<Marker>& markers, std::vector<uint8_t>& bad) {
+        bad.assign(n > 0 ? n : 1, 0);
+        std::vector<float> g2m(16 * markers.size()), size(markers.size()), corners(8 * markers.size());
+        for (size_t m = 0; m < markers.size(); m++) {
+            std::copy(markers[m].pose_g2m, markers[m].pose_g2m + 16, g2m.begin() + 16 * m);
+            size[m] = markers[m].size;
+            std::copy(markers[m].und_corners, markers[m].und_corners + 8, corners.begin() + 8 * m);
+        }
+        const uh_pnp_markers mk{(int32_t)markers.size(), g2m.data(), size.data(), corners.data()};
+        float out[16];
+        int32_t iters[4];
+        const int rc = uh_pnp_solve_markers(p_, pose_io, intr4, n, p3d, kp, inv_sigma, weight, depth, bl, &mk, out, bad.data(), iters, nullptr);
+        if (rc < 0) check(rc);
+        std::copy(out, out + 16, pose_io);
+        bad.resize(n);
+        return rc;
+    }
    private:
     std::shared_ptr<Context> ctx_;
     uh_pnp* p_ = nullptr;

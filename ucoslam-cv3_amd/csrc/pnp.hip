@@ -1,6 +1,6 @@
 // Per-frame pose-only optimisation on MI355X (gfx950), fp64, behind the C ABI (uh_pnp_*).
 //
-// Semantic contract = PnPSolver::solvePnp for monocular matches without markers (reference file:line):
+// Semantic contract = PnPSolver::solvePnp for monocular / stereo matches and squared planar markers (reference file:line):
 //   src/optimization/pnpsolver.cpp:116-409  four rounds; each restarts from the INPUT pose (:354), runs optimize(10)
 //                                           (minChi2BetweenIter = 0), reclassifies every match with chi2 > 5.99 as outlier
 //                                           (excluded edges get a fresh error first, :364), drops the robust kernels from the
@@ -8,6 +8,8 @@
 //   src/optimization/typesg2o.h:590-650     EdgeSE3ProjectXYZOnlyPose error and 2x6 Jacobian
 //   src/optimization/typesg2o.h:82-105      WeightedHubberRobustKernel: the weight scales rho (the chi2 sums), not the Jacobian
 //   3rdparty/g2o                            Levenberg loop, lambda init/update, SE3 exp — as in ba.hip
+//   src/optimization/pnpsolver.cpp:280-386  markers (the MARKERS instantiations): one MarkerEdgeOnlyProject (typesg2o.h:414-471) per marker
+//                                           with g2o's numeric Jacobian (base_binary_edge.hpp:165-233), see "markers" below
 //
 // MI355X design: one 6x6 system over a few hundred to a few thousand matches, ~20 dependent Levenberg trials — pure latency, so
 // the WHOLE solve runs inside ONE workgroup of one launch and every trial costs ONE pass over the matches and ONE barrier:
@@ -51,6 +53,11 @@ struct PnpArgs {
     // stereo instantiation only (kept behind the monocular fields: those instantiations read the same offsets as before)
     const float* depth;      // n: Frame::getDepth(queryIdx), <= 0 = monocular match
     float bl;                // imageParams.bl (stereo baseline)
+    // marker instantiations only
+    int n_mk;                // 1..kPnpMaxMarkers
+    const float* mk_pose;    // n_mk x 16: Marker::pose_g2m
+    const float* mk_size;    // n_mk: Marker::size
+    const float* mk_corners; // n_mk x 8: MarkerObservation::und_corners
 };
 
 // one thread: the decision of system.cpp:6646 / :6813 from this solve's inlier count (tracked iff MORE than min_inliers); M = the pose it
@@ -232,7 +239,25 @@ static_assert(sizeof(MatchRec) == 32, "match record");
 // match); kStereo in flags selects EdgeStereoSE3ProjectXYZOnlyPose for the match.  36 bytes per match: 3000 matches = 105.5 KiB of LDS.
 constexpr int kPnpRecBytesStereo = 36;
 
-template <bool CACHED, bool STEREO = false>
+// ---- markers (pnpsolver.cpp:280-386, typesg2o.h:414-471).  The marker vertex is fixed, so a marker is four points of the global frame
+// (g2m applied to the corners (-+s/2, +-s/2, 0), s a float) and their measured, undistorted image positions.  The edge's error rounds
+// every projected coordinate to FLOAT and has no analytic Jacobian: g2o differentiates it numerically, col d = (e(+delta e_d) -
+// e(-delta e_d)) / (2 delta) with delta = (double)(float)1e-4 on those float-quantised errors — the quantisation is part of the
+// behaviour and is reproduced: 13 pose evaluations (the pose itself and exp(+-delta e_d) * pose) x 4 corners per marker and pass.
+// exp(+-delta e_d) * T maps a camera-frame point c of T to R_d(+-delta) c (rotations, SE3Quat::exp's sin / (1 - cos) expressions) or
+// c +- delta e_d (translations), so the perturbed points are formed from the unperturbed one.
+constexpr int kPnpMaxMarkers = UH_PNP_MAX_MARKERS;
+// J, e, rho1, rc: the edge's linearisation at the pose a pass evaluates (numeric Jacobian, errors, the kernel's rho[1] and rho[0]), parked
+// here by the marker's wave, which then forms the marker's share of the sums from it (marker_linearise)
+struct __attribute__((aligned(8))) MarkerRec { double P[4][3]; float uv[8]; int robust, pad; double J[8][6], e[8], rho1, rc; };
+// the marker instantiations' dynamic LDS: [match records of the LDS form | kPnpMaxMarkers marker records | weight_marker | per wave: its
+// markers' share of the 28 sums of a pass]
+constexpr size_t kPnpMarkerLds = kPnpMaxMarkers * sizeof(MarkerRec) + sizeof(double) + 8 * 32 * sizeof(double);
+__host__ __device__ constexpr size_t pnp_marker_offset(int n, bool stereo) {
+    return (((size_t)(n > 1 ? n : 1) * (stereo ? kPnpRecBytesStereo : 32) + 15) / 16) * 16;
+}
+
+template <bool CACHED, bool STEREO = false, bool MARKERS = false>
 __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_cache[];
     __shared__ __attribute__((aligned(16))) double s_part[kPnpWaves * 32];
@@ -252,7 +277,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         // pnpsolver.cpp:149-150: without matches the pose comes back as it went in.  The tracker's first solve (dec.dyn17) runs only with
         // MORE than min_inliers matches (system.cpp:6595); otherwise the reference tries its FrameMatcher fallback, which is the caller's:
         // taken to find nothing, nInliers = 0 and no solve is reported (pose in, no iterations, no outlier flags)
-        if (n <= 0 || (A.dec.dyn17 && n <= A.dec.min_inliers)) {
+        // (with markers a solve without matches runs, pnpsolver.cpp:148-158; the tracker's rule for its first solve stays)
+        if ((!MARKERS && n <= 0) || (A.dec.dyn17 && n <= A.dec.min_inliers)) {
             if (tid < 16) A.pose_out[tid] = A.pose_in[tid];
             if (tid < 5) A.result[tid] = 0;
             for (int e = tid; e < n; e += kPnpThreads) A.bad_out[e] = 0;
@@ -304,8 +330,92 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
             for (int i = 0; i < 12; i++) { s_pose[3][i] = P.Rt[i]; s_pose[1][i] = P.Rt[i]; s_pose[2][i] = P.Rt[i]; }
         }
     }
+    // markers: the records, and weight_marker of pnpsolver.cpp:305-310 in its mixed float / double arithmetic — KpWeightSum is the
+    // double sum of the per-match kernel weights after the stereo doubling (block_sum's fixed pairing instead of the reference's
+    // match order: the same bits whenever the partial sums are exact, as they are for the weights 0.5 / 1 / 2); +inf without matches
+    // (in the dynamic LDS behind the A.n match records the launch sized it for — nothing is added to the marker-free instantiations)
+    const int nmk = MARKERS ? A.n_mk : 0;
+    MarkerRec* s_mk = reinterpret_cast<MarkerRec*>(s_cache + (CACHED ? pnp_marker_offset(A.n, STEREO) : 0));
+    double* s_mkw = reinterpret_cast<double*>(s_mk + kPnpMaxMarkers);
+    double* s_mkpart = s_mkw + 1;
+    // marker i belongs to wave 7 - i % 8: wave 0, whose serial steps every pass waits for, is the last to get one
+    const int mk_first = kPnpWaves - 1 - wv;
+    if constexpr (MARKERS) {
+        double ws = 0;
+        for (int e = tid; e < n; e += kPnpThreads) {   // (this thread's own records: no second trip to the caller's arrays)
+            float w = rec[e].weight;
+            if constexpr (STEREO) { if (rec[e].flags & kStereo) w *= 2.f; }
+            ws += (double)w;
+        }
+        ws = block_sum<kPnpWaves>(ws, s_part);
+        if (tid == 0) *s_mkw = ((double)(0.3f * (float)(n + nmk)) / (1. - (double)0.3f)) / (double)(float)ws;
+        if (tid < nmk) {
+            const float* M = A.mk_pose + 16 * tid;
+            PoseD G;
+            const double R0[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
+            p_quat_from_R(R0, G.q);
+            p_quat_norm(G.q);
+            G.t[0] = M[3]; G.t[1] = M[7]; G.t[2] = M[11];
+            p_set_Rt(G);
+            const float sz = A.mk_size[tid];
+            const double hi = (double)(float)((double)sz / 2.), lo = (double)(float)(-(double)sz / 2.);   // Marker::get3DPointsLocalRefSystem: cv::Point3f
+            const double px[4] = {lo, hi, hi, lo}, py[4] = {hi, hi, lo, lo};
+            MarkerRec& r = s_mk[tid];
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+#pragma unroll
+                for (int a = 0; a < 3; a++) r.P[c][a] = fma(G.Rt[3 * a + 1], py[c], fma(G.Rt[3 * a], px[c], G.Rt[9 + a]));
+#pragma unroll
+            for (int i = 0; i < 8; i++) r.uv[i] = A.mk_corners[8 * tid + i];
+            r.robust = 1; r.pad = 0;
+        }
+    }
     __syncthreads();
     if (A.clk && tid == 0) A.clk[1] = __builtin_readcyclecounter();
+    // the marker edge's kernel: thHuber8D = (float)sqrt(15.507), relabelled against Chi8D = 15.507f
+    constexpr double delta8 = 0x1.f80cep+1, dsqr8 = delta8 * delta8;      // (double)(float)sqrt(15.507) = 3.9378929138183594
+    constexpr double mk_delta = (double)1e-4f, mk_scalar = 1 / (2 * mk_delta);
+    // SE3Quat::exp for omega = delta e_d (theta = delta >= 1e-5): R = I + sin(theta)/theta Omega + (1 - cos(theta))/theta^2 Omega^2, i.e. the
+    // entries (sin(delta) / delta) * delta and 1 - ((1 - cos(delta)) / delta^2) * delta^2 in double, as constants (wave-uniform values
+    // computed at run time would sit in vector registers for the whole solve)
+    constexpr double mk_sin = 0x1.a36e2df44599cp-14, mk_cos = 0x1.ffffffd50ce26p-1;
+    // the error of corner c of a marker at the pose Rt perturbed by pattern k: 0 = not, 1..6 = +delta along dimension k - 1, 7..12 =
+    // -delta along dimension k - 7.  Projections rounded to float (typesg2o.h:461-465)
+    auto marker_err = [&](const MarkerRec& m, int c, int k, const double* Rt, double& ex, double& ey) {
+        const double X0 = m.P[c][0], X1 = m.P[c][1], X2 = m.P[c][2];
+        double p0 = fma(Rt[2], X2, fma(Rt[1], X1, fma(Rt[0], X0, Rt[9])));
+        double p1 = fma(Rt[5], X2, fma(Rt[4], X1, fma(Rt[3], X0, Rt[10])));
+        double p2 = fma(Rt[8], X2, fma(Rt[7], X1, fma(Rt[6], X0, Rt[11])));
+        if (k > 0) {
+            const double sg = k > 6 ? -1.0 : 1.0;
+            const int d = k > 6 ? k - 7 : k - 1;
+            if (d < 3) {   // rotation about axis d: (u, v, w) = the components (d, d + 1, d + 2) cyclically
+                const double v = d == 0 ? p1 : d == 1 ? p2 : p0, w = d == 0 ? p2 : d == 1 ? p0 : p1;
+                const double s = sg * mk_sin;
+                const double v2 = mk_cos * v - s * w, w2 = s * v + mk_cos * w;
+                if (d == 0) { p1 = v2; p2 = w2; } else if (d == 1) { p2 = v2; p0 = w2; } else { p0 = v2; p1 = w2; }
+            } else {
+                const double t = sg * mk_delta;
+                if (d == 3) p0 += t; else if (d == 4) p1 += t; else p2 += t;
+            }
+        }
+        const double projx = (double)(float)((p0 / p2) * fx + cx), projy = (double)(float)((p1 / p2) * fy + cy);
+        ex = (double)m.uv[2 * c] - projx;
+        ey = (double)m.uv[2 * c + 1] - projy;
+    };
+    // chi2 of a marker at Rt (no perturbation), valid in every lane: lane l evaluates corner l & 3, the quad adds up
+    auto marker_chi2 = [&](const MarkerRec& m, const double* Rt) -> double {
+        double ex, ey;
+        marker_err(m, lane & 3, 0, Rt, ex, ey);
+        double c = fma(ex, ex, ey * ey);
+        c += __shfl_xor(c, 1);
+        c += __shfl_xor(c, 2);
+        return c;
+    };
+    auto marker_rho0 = [&](double c) -> double {   // WeightedHubberRobustKernel's rho[0]
+        const double wt = *s_mkw;
+        return c <= dsqr8 ? wt * c : wt * (2 * sqrt(c) * delta8 - dsqr8);
+    };
 
     // chi2 of a match at the pose Rt; xz, yz, invz for the Jacobian
     auto project = [&](const MatchRec& m, const double* Rt, double& ex, double& ey, double& xz, double& yz, double& invz) -> double {
@@ -437,10 +547,68 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         WaveTransposeValu<kNS, 32>::run(acc, lane, off, real);   // lane l ends with the wave total of one value index
         if (real >= 1) s_part[wv * 32 + off] = acc[0];
     };
+    // The markers of a pass, taken before its matches (no sum is live yet; the poses are read from LDS): a wave linearises its markers (mk_first,
+    // mk_first + 8, ...); lane = 4 * pattern + corner (52 of the 64 lanes), the twelve perturbed errors of a corner are gathered into its lane
+    // 0..3, which parks the two Jacobian rows in the marker's record; lane l < 28 then forms the marker's share of sum l — J^T rho1 J (21),
+    // -J^T rho1 e (6), rho[0] (the information is the identity) — and the wave leaves its markers' shares in s_mkpart, where wave 0 adds
+    // them to the totals of the pass.
+    auto marker_linearise = [&](bool classify, bool drop_robust) __attribute__((noinline)) {
+        if (mk_first >= nmk) return;
+        int ja = 0, jc = lane;
+        while (jc >= 6 - ja && ja < 6) { jc -= 6 - ja; ja++; }   // lane < 21: entry (ja, ja + jc) of the upper triangle; 21..26: b[lane - 21]
+        jc += ja;
+        double share = 0;
+        for (int mi = mk_first; mi < nmk; mi += kPnpWaves) {
+            MarkerRec& m = s_mk[mi];
+            int robust = m.robust;
+            if (classify) {
+                // pnpsolver.cpp:376-380: computeError() at the pose the round ended with (the vertex's estimate), the kernel
+                // dropped for good above Chi8D or from the third round on; never excluded, never counted
+                const double c = marker_chi2(m, s_pose[1]);
+                if (c > (double)15.507f || drop_robust) robust = 0;
+                if (lane == 0) m.robust = robust;
+            }
+            const int k = lane < 52 ? lane >> 2 : 0, cn = lane & 3;
+            double ex, ey;
+            marker_err(m, cn, k, s_pose[0], ex, ey);
+#pragma unroll
+            for (int d = 0; d < 6; d++) {
+                const int lp = (1 + d) * 4 + cn, lm = (7 + d) * 4 + cn;
+                const double jx = mk_scalar * (__shfl(ex, lp) - __shfl(ex, lm)), jy = mk_scalar * (__shfl(ey, lp) - __shfl(ey, lm));
+                if (lane < 4) { m.J[2 * cn][d] = jx; m.J[2 * cn + 1][d] = jy; }
+            }
+            double c = fma(ex, ex, ey * ey);   // (lanes 0..3: the unperturbed errors)
+            c += __shfl_xor(c, 1);
+            c += __shfl_xor(c, 2);
+            if (lane < 4) { m.e[2 * cn] = ex; m.e[2 * cn + 1] = ey; }
+            if (lane == 0) {
+                double rho1 = 1.0, rc = c;
+                if (robust) {
+                    rc = marker_rho0(c);
+                    if (!(c <= dsqr8)) rho1 = delta8 / sqrt(c);
+                }
+                m.rho1 = rho1; m.rc = rc;
+            }
+            // (written by this wave: its LDS operations complete in order)
+            double v = 0;
+            if (lane < 21) {
+#pragma unroll
+                for (int r = 0; r < 8; r++) v = fma(m.J[r][ja], m.J[r][jc], v);
+                v *= m.rho1;
+            } else if (lane < 27) {
+#pragma unroll
+                for (int r = 0; r < 8; r++) v = fma(m.J[r][lane - 21], m.e[r], v);
+                v *= -m.rho1;
+            } else if (lane == 27) v = m.rc;
+            share += v;
+        }
+        if (lane < 32) s_mkpart[wv * 32 + lane] = share;
+    };
     // what a pass does is published by wave 0 through s_ctl / s_pose before barrier A
     auto run_published_pass = [&]() -> int {
         const int mode = s_ctl[0];
         if (mode == kModeExit) return mode;
+        if constexpr (MARKERS) { if (mode != kModeClassify) marker_linearise(s_ctl[1] != 0, s_ctl[2] != 0); }
         double RtA[12];
 #pragma unroll
         for (int i = 0; i < 12; i++) RtA[i] = s_pose[0][i];
@@ -515,6 +683,18 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
                 }
             }
         }
+        if constexpr (MARKERS) {
+            // the wave's markers at ALL candidates at once: lane = 4 * candidate + corner (32 lanes), the candidate's pose read from LDS
+            const int kk = lane >> 2;
+            for (int mi = mk_first; mi < nmk; mi += kPnpWaves) {
+                const MarkerRec& m = s_mk[mi];
+                const double c = marker_chi2(m, s_cand[kk < K ? kk : 0]);
+                const double rc = m.robust ? marker_rho0(c) : c;
+#pragma unroll
+                for (int k = 0; k < kLadderMax; k++)
+                    if (k < K && lane == 4 * k) chi[k] += rc;
+            }
+        }
         int off = 0, real = kLadderMax;
         WaveTransposeValu<kLadderMax, 32>::run(chi, lane, off, real);
         if (real >= 1) s_part[wv * 32 + off] = chi[0];
@@ -545,7 +725,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         //        stop on terminate or when the float chi2 no longer decreases }
         //   } classify the last round                                                               -> ST_FINAL
         enum : int { ST_INIT, ST_RELIN, ST_TRIAL, ST_LADDER, ST_FINAL, ST_DONE };
-        int st = n > 0 ? ST_INIT : ST_DONE;
+        int st = (MARKERS || n > 0) ? ST_INIT : ST_DONE;
         // measurement (A.clk != NULL only): cycles of wave 0 by section of a plain pass — [16] request prepared (solve + update), [17] barrier A,
         // [18] its share of the matches + butterfly, [19] barrier B, [20] totals + decision; [21] ladder passes as a whole
         long long ph[6] = {0, 0, 0, 0, 0, 0}, tp = A.clk ? (long long)__builtin_readcyclecounter() : 0;
@@ -696,6 +876,10 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
                 double mine = s_part[lane];
 #pragma unroll
                 for (int w2 = 1; w2 < kPnpWaves; w2++) mine += s_part[w2 * 32 + lane];   // wave order
+                if constexpr (MARKERS) {
+                    if (mode == kModeEval)
+                        for (int j = 0; j < nmk && j < kPnpWaves; j++) mine += s_mkpart[(kPnpWaves - 1 - j) * 32 + lane];   // marker order
+                }
                 s_tot[lane] = mine;
             }
             if (mode == kModeEval && lane < 12) s_pose[2][lane] = s_pose[0][lane];   // the pose the edges' errors now belong to
@@ -704,7 +888,9 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
             if (st == ST_INIT) {
                 if (round > 0) {
                     good = (int)good_sum;
-                    if (good < 10) { st = ST_DONE; continue; }
+                    if constexpr (!MARKERS) {   // pnpsolver.cpp:383: the stop below ten good matches applies only without markers
+                        if (good < 10) { st = ST_DONE; continue; }
+                    }
                 }
                 if (lane < 27) s_H[lane] = s_tot[lane];          // the totals of the pass are the normal equations of the pose it evaluated
                 currentChi = chi_sum; lastChiRaw = chi_sum; ni = 2;
@@ -775,7 +961,7 @@ struct uh_pnp {
     uh::DevBuf d_work;
     uh::MappedBuf h_io;      // pinned, device-visible: [completion word | results | inputs]
     unsigned long long seq = 0;
-    bool attr_set[2] = {false, false};   // the LDS attribute of pnp_solve_kernel<true, STEREO>, per STEREO
+    bool attr_set[2][2] = {{false, false}, {false, false}};   // the LDS attribute of pnp_solve_kernel<true, STEREO, MARKERS>, per [MARKERS][STEREO]
     long long* d_clk = nullptr;   // measurement hook (uh_pnp_debug_clocks)
     ~uh_pnp() { if (d_clk) (void)hipFree(d_clk); }
 };
@@ -794,9 +980,24 @@ PnpArgs pnp_args(const float* pose, const float* intr, int n, const float* p3d, 
 }
 
 // the dynamic-LDS limit of a CACHED instantiation, set once per solver object
-int lds_attr(uh_pnp* p, const void* kernel, bool stereo) {
-    if (!p->attr_set[stereo]) UH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kPnpLdsMatches * pnp_rec_bytes(stereo))));
-    p->attr_set[stereo] = true;
+int lds_attr(uh_pnp* p, const void* kernel, bool stereo, bool markers = false) {
+    const size_t most = markers ? pnp_marker_offset(kPnpLdsMatches, stereo) + kPnpMarkerLds : kPnpLdsMatches * pnp_rec_bytes(stereo);
+    if (!p->attr_set[markers][stereo]) UH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+    p->attr_set[markers][stereo] = true;
+    return UH_OK;
+}
+
+// the marker arrays of a solve (device-visible pointers); n_mk == 0: no markers, the marker-free instantiations run
+struct PnpMarkers { int n = 0; const float* pose = nullptr; const float* size = nullptr; const float* corners = nullptr; };
+void set_markers(PnpArgs& A, const PnpMarkers& m) { A.n_mk = m.n; A.mk_pose = m.pose; A.mk_size = m.size; A.mk_corners = m.corners; }
+
+// what every entry checks of a uh_pnp_markers before anything is launched; host_arrays: the sizes can be read here
+int check_markers(const char* fn, const uh_pnp_markers* m, bool host_arrays) {
+    if (!m) return UH_OK;
+    UH_REQUIRE(m->n >= 0 && m->n <= UH_PNP_MAX_MARKERS, "%s: %d markers outside [0, %d]", fn, m->n, UH_PNP_MAX_MARKERS);
+    if (m->n > 0) UH_REQUIRE(m->pose_g2m && m->size && m->und_corners, "%s: NULL marker arrays", fn);
+    if (host_arrays)
+        for (int i = 0; i < m->n; i++) UH_REQUIRE(std::isfinite(m->size[i]) && m->size[i] > 0.f, "%s: marker %d has size %g", fn, i, (double)m->size[i]);
     return UH_OK;
 }
 
@@ -806,29 +1007,45 @@ int launch(uh_pnp* p, PnpArgs& A) {
     const bool cached = A.n <= kPnpLdsMatches, stereo = A.depth != nullptr;
     const size_t lds = cached ? (size_t)std::max(A.n, 1) * pnp_rec_bytes(stereo) : 0;
     int rc;
-    // (stereo first, LDS form first in each: the order in which the instantiations have always been named, which fixes their order in the device code)
-    if (stereo) {
-        if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true, true>), true))) return rc;
-        if (cached) UH_LAUNCH(p->ctx, (pnp_solve_kernel<true, true>), dim3(1), dim3(kPnpThreads), lds, A);
-        else UH_LAUNCH(p->ctx, (pnp_solve_kernel<false, true>), dim3(1), dim3(kPnpThreads), 0, A);
-    } else {
-        if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true>), false))) return rc;
-        if (cached) UH_LAUNCH(p->ctx, pnp_solve_kernel<true>, dim3(1), dim3(kPnpThreads), lds, A);
-        else UH_LAUNCH(p->ctx, pnp_solve_kernel<false>, dim3(1), dim3(kPnpThreads), 0, A);
+    if (A.n_mk <= 0) {
+        // (stereo first, LDS form first in each: the order in which the instantiations have always been named, which fixes their order in the device code)
+        if (stereo) {
+            if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true, true>), true))) return rc;
+            if (cached) UH_LAUNCH(p->ctx, (pnp_solve_kernel<true, true>), dim3(1), dim3(kPnpThreads), lds, A);
+            else UH_LAUNCH(p->ctx, (pnp_solve_kernel<false, true>), dim3(1), dim3(kPnpThreads), 0, A);
+        } else {
+            if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true>), false))) return rc;
+            if (cached) UH_LAUNCH(p->ctx, pnp_solve_kernel<true>, dim3(1), dim3(kPnpThreads), lds, A);
+            else UH_LAUNCH(p->ctx, pnp_solve_kernel<false>, dim3(1), dim3(kPnpThreads), 0, A);
+        }
+    } else {   // the marker instantiations, only ever launched with markers
+        const size_t lds_mk = (cached ? pnp_marker_offset(A.n, stereo) : 0) + kPnpMarkerLds;
+#define UH_PNP_LAUNCH_MK(C_, S_)                                                                                                     \
+    do {                                                                                                                             \
+        if (C_ && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<C_, S_, true>), S_, true))) return rc;            \
+        UH_LAUNCH(p->ctx, (pnp_solve_kernel<C_, S_, true>), dim3(1), dim3(kPnpThreads), lds_mk, A);                                   \
+    } while (0)
+        if (stereo) { if (cached) UH_PNP_LAUNCH_MK(true, true); else UH_PNP_LAUNCH_MK(false, true); }
+        else { if (cached) UH_PNP_LAUNCH_MK(true, false); else UH_PNP_LAUNCH_MK(false, false); }
+#undef UH_PNP_LAUNCH_MK
     }
     UH_HIP_CHECK(hipGetLastError());
     return UH_OK;
 }
 
-// uh_pnp_solve_dev (d_depth == NULL) and uh_pnp_solve_stereo_dev
+// uh_pnp_solve_dev (d_depth == NULL), uh_pnp_solve_stereo_dev and uh_pnp_solve_markers_dev (mk: device arrays, or NULL)
 int solve_dev(const char* fn, uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-              const float* d_weight, const float* d_depth, float bl, void* d_work, float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
+              const float* d_weight, const float* d_depth, float bl, const uh_pnp_markers* mk, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
+              int32_t* d_result5, double* d_state7) {
     UH_REQUIRE(p && d_pose_f2g && d_intr4 && d_pose_out && d_result5, "%s: NULL argument", fn);
     UH_REQUIRE(n >= 0, "%s: negative match count", fn);
     if (d_depth) UH_REQUIRE(bl > 0.f, "%s: a depth array needs a baseline > 0 (bl = %g)", fn, (double)bl);
+    int rc;
+    if ((rc = check_markers(fn, mk, false))) return rc;
     if (n > 0) UH_REQUIRE(d_p3d && d_kp && d_inv_sigma && d_weight && d_work && d_bad_out, "%s: NULL match arrays", fn);
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     PnpArgs A = pnp_args(d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    if (mk && mk->n > 0) { PnpMarkers m; m.n = mk->n; m.pose = mk->pose_g2m; m.size = mk->size; m.corners = mk->und_corners; set_markers(A, m); }
     return launch(p, A);
 }
 
@@ -843,13 +1060,15 @@ int pnp_reserve(uh_pnp* p, int n_cap, bool stereo) {
 // the solve behind uh_track_pose: everything resident, the match count decided by an earlier launch of the same stream
 // d_depth != NULL: the stereo form (per-match depth, baseline bl)
 int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl) {
+                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl,
+                    int n_mk, const float* d_mk_pose, const float* d_mk_size, const float* d_mk_corners) {
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     int rc;
     if ((rc = pnp_reserve(p, n_cap, d_depth != nullptr))) return rc;
     PnpArgs A = pnp_args(d_pose, d_intr4, n_cap, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, p->d_work.p, d_pose_out, d_bad_out, d_result5, nullptr);
     A.n_dev = d_n;
     if (dec) A.dec = *dec;
+    if (n_mk > 0) { PnpMarkers m; m.n = n_mk; m.pose = d_mk_pose; m.size = d_mk_size; m.corners = d_mk_corners; set_markers(A, m); }
     return launch(p, A);
 }
 }  // namespace uh
@@ -870,7 +1089,7 @@ void uh_pnp_destroy(uh_pnp* p) { delete p; }
 int uh_pnp_solve_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                      const float* d_inv_sigma, const float* d_weight, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
                      int32_t* d_result5, double* d_state7) {
-    return solve_dev("uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, nullptr, 0.f, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    return solve_dev("uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, nullptr, 0.f, nullptr, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
 // Stereo / RGB-D form of uh_pnp_solve_dev: d_depth (n floats, device) as in uh_pnp_solve_stereo; d_work = n * 36 bytes when d_depth is given.
@@ -879,7 +1098,18 @@ int uh_pnp_solve_stereo_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_i
                             const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, void* d_work, float* d_pose_out,
                             uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
     return solve_dev(d_depth ? "uh_pnp_solve_stereo_dev" : "uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth,
-                     d_depth ? bl : 0.f, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+                     d_depth ? bl : 0.f, nullptr, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+}
+
+// uh_pnp_solve_stereo_dev with markers: the three arrays of `markers` are device arrays too (the struct itself is the host's).  The sizes
+// are not read on the host.  markers == NULL or n == 0 markers is uh_pnp_solve_stereo_dev itself.
+int uh_pnp_solve_markers_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
+                             const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, const uh_pnp_markers* markers,
+                             void* d_work, float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
+    if (!markers || markers->n == 0)
+        return uh_pnp_solve_stereo_dev(p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    return solve_dev("uh_pnp_solve_markers_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, d_depth ? bl : 0.f, markers, d_work,
+                     d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
 // Host-pointer form: PnPSolver::solvePnp(frame, map, matches, pose): returns the inlier count (>= 0) or a negative error.
@@ -894,11 +1124,23 @@ int uh_pnp_solve(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, co
 // is uh_pnp_solve itself.
 int uh_pnp_solve_stereo(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* inv_sigma,
                         const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out, int32_t* iters_out4, double* state_out7) {
-    const char* fn = depth ? "uh_pnp_solve_stereo" : "uh_pnp_solve";
+    return uh_pnp_solve_markers(p, pose_f2g, intr4, n, p3d, kp, inv_sigma, weight, depth, bl, nullptr, pose_out, bad_out, iters_out4, state_out7);
+}
+
+// uh_pnp_solve_stereo with the frame's markers (pnpsolver.cpp:280-386).  markers == NULL or n == 0 markers: uh_pnp_solve_stereo itself, the
+// marker-free kernels on the same staging block.  Without matches but with markers the solve runs (the match arrays may be NULL).
+int uh_pnp_solve_markers(uh_pnp* p, const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* inv_sigma,
+                         const float* weight, const float* depth, float bl, const uh_pnp_markers* markers, float* pose_out, uint8_t* bad_out,
+                         int32_t* iters_out4, double* state_out7) {
+    const int nmk = markers ? markers->n : 0;
+    const char* fn = nmk ? "uh_pnp_solve_markers" : depth ? "uh_pnp_solve_stereo" : "uh_pnp_solve";
     UH_REQUIRE(p && pose_f2g && intr4 && pose_out, "%s: NULL argument", fn);
     UH_REQUIRE(n >= 0, "%s: negative match count", fn);
-    if (n == 0) { memcpy(pose_out, pose_f2g, 64); if (iters_out4) memset(iters_out4, 0, 16); return 0; }   // pnpsolver.cpp:149-150
-    UH_REQUIRE(p3d && kp && inv_sigma && weight && bad_out, "%s: NULL match arrays", fn);
+    int rc;
+    if ((rc = check_markers("uh_pnp_solve_markers", markers, true))) return rc;
+    if (n == 0 && nmk == 0) { memcpy(pose_out, pose_f2g, 64); if (iters_out4) memset(iters_out4, 0, 16); return 0; }   // pnpsolver.cpp:149-150
+    if (n > 0) UH_REQUIRE(p3d && kp && inv_sigma && weight && bad_out, "%s: NULL match arrays", fn);
+    if (n == 0) depth = nullptr;
     const bool any_depth = depth && std::any_of(depth, depth + n, [](float d) { return !(d <= 0.f); });
     UH_REQUIRE(!any_depth || bl > 0.f, "uh_pnp_solve_stereo: stereo matches need a baseline > 0 (bl = %g)", (double)bl);
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
@@ -906,22 +1148,30 @@ int uh_pnp_solve_stereo(uh_pnp* p, const float* pose_f2g, const float* intr4, in
     uh::Layout L{64};   // the pinned block, 64-byte regions: [0, 64) the completion word, the results, the inputs
     const size_t o_pout = L.take<float>(16, 64), o_res = L.take<int>(5, 64), o_state = L.take<double>(7, 64), o_pose = L.take<float>(16, 64), o_intr = L.take<float>(4, 64);
     const size_t o_p3d = L.take<float>(3 * nf, 64), o_kp = L.take<float>(2 * nf, 64), o_is = L.take<float>(nf, 64), o_w = L.take<float>(nf, 64), o_bad = L.take<unsigned char>(nf, 64),
-                 o_dep = L.take<float>(depth ? nf : 0, 64), total = L.take<char>(0, 64);
-    int rc;
+                 o_dep = L.take<float>(depth ? nf : 0, 64), o_mkp = L.take<float>(16 * (size_t)nmk, 64), o_mks = L.take<float>((size_t)nmk, 64),
+                 o_mkc = L.take<float>(8 * (size_t)nmk, 64), total = L.take<char>(0, 64);
     if ((rc = p->h_io.reserve(total))) return rc;
     if ((rc = uh::pnp_reserve(p, n, depth != nullptr))) return rc;
     char* h = p->h_io.host<char>();
     char* d = p->h_io.dev<char>();
     memcpy(h + o_pose, pose_f2g, 64);
     memcpy(h + o_intr, intr4, 16);
-    memcpy(h + o_p3d, p3d, nf * 12);
-    memcpy(h + o_kp, kp, nf * 8);
-    memcpy(h + o_is, inv_sigma, nf * 4);
-    memcpy(h + o_w, weight, nf * 4);
+    if (n > 0) {
+        memcpy(h + o_p3d, p3d, nf * 12);
+        memcpy(h + o_kp, kp, nf * 8);
+        memcpy(h + o_is, inv_sigma, nf * 4);
+        memcpy(h + o_w, weight, nf * 4);
+    }
     if (depth) memcpy(h + o_dep, depth, nf * 4);
+    if (nmk) {
+        memcpy(h + o_mkp, markers->pose_g2m, (size_t)nmk * 64);
+        memcpy(h + o_mks, markers->size, (size_t)nmk * 4);
+        memcpy(h + o_mkc, markers->und_corners, (size_t)nmk * 32);
+    }
     PnpArgs A = pnp_args((const float*)(d + o_pose), (const float*)(d + o_intr), n, (const float*)(d + o_p3d), (const float*)(d + o_kp), (const float*)(d + o_is),
                          (const float*)(d + o_w), depth ? (const float*)(d + o_dep) : nullptr, bl, p->d_work.p, (float*)(d + o_pout), (unsigned char*)(d + o_bad),
                          (int*)(d + o_res), (double*)(d + o_state));
+    if (nmk) { PnpMarkers m; m.n = nmk; m.pose = (const float*)(d + o_mkp); m.size = (const float*)(d + o_mks); m.corners = (const float*)(d + o_mkc); set_markers(A, m); }
     A.host_done = (unsigned long long*)d;
     A.done_word = ++p->seq;
     std::atomic_thread_fence(std::memory_order_release);
@@ -930,7 +1180,7 @@ int uh_pnp_solve_stereo(uh_pnp* p, const float* pose_f2g, const float* intr4, in
     int32_t res[5];
     memcpy(res, h + o_res, 20);
     memcpy(pose_out, h + o_pout, 64);
-    memcpy(bad_out, h + o_bad, nf);
+    if (n > 0) memcpy(bad_out, h + o_bad, nf);
     if (state_out7) memcpy(state_out7, h + o_state, 56);
     if (iters_out4) memcpy(iters_out4, res + 1, 16);
     return res[0];

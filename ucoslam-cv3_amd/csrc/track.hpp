@@ -26,7 +26,8 @@
 
 namespace uh {
 int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl);
+                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl,
+                    int n_mk, const float* d_mk_pose, const float* d_mk_size, const float* d_mk_corners);
 int pnp_reserve(uh_pnp* p, int n_cap, bool stereo);
 uh_ctx* pnp_ctx(uh_pnp* p);
 }
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(kTrkThreads) void track_publish_kernel(TrkPublish p
 
 struct uh_track_state {
     uh::DevBuf d;          // header | poses | PmDyn | lists | solver arrays | scratch (TrkLayout)
-    uh::MappedBuf h_par;   // pinned, read by the launches in place: [completion word | pose0 | intr | inv sigma per level | depth per keypoint]
+    uh::MappedBuf h_par;   // pinned, read by the launches in place: [completion word | pose0 | intr | inv sigma per level | depth per keypoint | markers]
     uh::MappedBuf h_out;   // pinned: the results
     unsigned long long seq = 0;
     bool attr_set = false;
@@ -253,10 +254,10 @@ struct TrkLayout {
     int cap1, cap2, capa, capn;   // the first search's list, the second's, the union; capn: a filtered list holds one match per keypoint at most
     size_t hdr, pose1, pose2, m1, bad1, m2, ma, bada, out_bytes;
     size_t pose_map, dyn, src1, src2, srca, p3d, kp, isg, wgt, sa, sb, pos_prev, pos_map, aux_prev, aux_map, dep_kp, dep, seen, d_bytes;
-    size_t par_pose0, par_intr, par_isl, par_dep, par_bytes;
+    size_t par_pose0, par_intr, par_isl, par_dep, par_mkp, par_mks, par_mkc, par_bytes;
 };
 
-TrkLayout trk_layout(int np, int nm, int nk, bool stereo) {
+TrkLayout trk_layout(int np, int nm, int nk, bool stereo, int n_mk) {
     TrkLayout L;
     L.cap1 = std::max(np, 1); L.cap2 = std::max(nm, 1); L.capa = std::max(np + nm, 1); L.capn = std::min(L.capa, std::max(nk, 1));
     const size_t c1 = L.cap1, c2 = L.cap2, ca = L.capa;
@@ -271,6 +272,7 @@ TrkLayout trk_layout(int np, int nm, int nk, bool stereo) {
     L.d_bytes = d.take<char>(0);
     uh::Layout p{64};
     L.par_pose0 = p.take<float>(16, 64); L.par_intr = p.take<float>(4, 64); L.par_isl = p.take<float>(16, 64); L.par_dep = p.take<float>(stereo ? nk : 0, 64);
+    L.par_mkp = p.take<float>(16 * (size_t)n_mk, 64); L.par_mks = p.take<float>((size_t)n_mk, 64); L.par_mkc = p.take<float>(8 * (size_t)n_mk, 64);   // (uh_track_pose_markers)
     L.par_bytes = p.off;
     return L;
 }
@@ -278,9 +280,14 @@ TrkLayout trk_layout(int np, int nm, int nk, bool stereo) {
 // a block's base + offset, as whatever pointer it is assigned to
 struct TrkAt { char* p; template <typename T> operator T*() const { return reinterpret_cast<T*>(p); } };
 
-// Every check of uh_track_pose (sx == NULL) and uh_track_pose_stereo, before anything is staged
-int track_validate(const uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, const uh_track_result* r) {
+// Every check of uh_track_pose (sx == NULL), uh_track_pose_stereo and uh_track_pose_markers (mk != NULL), before anything is staged
+int track_validate(const uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, const uh_pnp_markers* mk, const uh_track_result* r) {
     UH_REQUIRE(h && pnp && a && r, "uh_track_pose: NULL argument");
+    if (mk) {
+        UH_REQUIRE(mk->n >= 0 && mk->n <= UH_PNP_MAX_MARKERS, "uh_track_pose_markers: %d markers outside [0, %d]", mk->n, UH_PNP_MAX_MARKERS);
+        if (mk->n > 0) UH_REQUIRE(mk->pose_g2m && mk->size && mk->und_corners, "uh_track_pose_markers: NULL marker arrays");
+        for (int i = 0; i < mk->n; i++) UH_REQUIRE(std::isfinite(mk->size[i]) && mk->size[i] > 0.f, "uh_track_pose_markers: marker %d has size %g", i, (double)mk->size[i]);
+    }
     UH_REQUIRE(h->have_frame && h->dev, "uh_track_pose: needs a device-resident frame (uh_orb_extract_frame_dev + uh_projmatch_set_frame_dev)");
     UH_REQUIRE(a->pose0 && a->intr4 && a->prev && a->map && a->inv_sigma_levels, "uh_track_pose: NULL input");
     UH_REQUIRE(a->n_levels >= 1 && a->n_levels <= 16, "uh_track_pose: %d levels", a->n_levels);
@@ -325,16 +332,17 @@ int select_launch(uh_projmatch* h, const TrkSelect& s, int capa) {
     return UH_OK;
 }
 
-// uh_track_pose (sx == NULL) and uh_track_pose_stereo
-int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, uh_track_result* r) {
+// uh_track_pose (sx == NULL), uh_track_pose_stereo and uh_track_pose_markers (mk: the markers of both solves, or NULL)
+int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* sx, const uh_pnp_markers* mk, uh_track_result* r) {
     int rc;
-    if ((rc = track_validate(h, pnp, a, sx, r))) return rc;
+    if ((rc = track_validate(h, pnp, a, sx, mk, r))) return rc;
+    const int n_mk = mk ? mk->n : 0;
     UH_HIP_CHECK(hipSetDevice(h->ctx->device));
     if (!h->track) h->track = new uh_track_state();
     uh_track_state& T = *h->track;
     const int np = a->prev->n, nm = a->map->n, nk = h->n_kpts;
     const bool stereo = sx && sx->depth;
-    const TrkLayout L = trk_layout(np, nm, nk, stereo);
+    const TrkLayout L = trk_layout(np, nm, nk, stereo, n_mk);
     static const bool trk_clk = getenv("UH_TRK_CLK") != nullptr;
     // ---- every buffer of the call before its first launch (a buffer that grows is freed, which synchronises the device)
     if ((rc = T.d.reserve(L.d_bytes)) || (rc = T.h_par.reserve(L.par_bytes)) || (rc = T.h_out.reserve(L.out_bytes))) return rc;
@@ -349,6 +357,11 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     std::memcpy(hp + L.par_intr, a->intr4, 16);
     std::memcpy(hp + L.par_isl, a->inv_sigma_levels, 4 * (size_t)a->n_levels);
     if (stereo && nk) std::memcpy(hp + L.par_dep, sx->depth, 4 * (size_t)nk);
+    if (n_mk) {   // (both solves read the markers in place, as they read the intrinsics)
+        std::memcpy(hp + L.par_mkp, mk->pose_g2m, 64 * (size_t)n_mk);
+        std::memcpy(hp + L.par_mks, mk->size, 4 * (size_t)n_mk);
+        std::memcpy(hp + L.par_mkc, mk->und_corners, 32 * (size_t)n_mk);
+    }
     std::atomic_thread_fence(std::memory_order_release);   // (every header field the publish reads is written by one of the launches below)
     int* hdr = at(L.hdr);
     // the select launch behind search k (0: the previous frame's items, 1: the local map's points; the second also forms the union)
@@ -385,7 +398,7 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     static_assert(sizeof(PmDyn) == 17 * 4, "PmDyn is what pnp_decide writes");
     const uh::PnpDecide dec{a->min_inliers, a->map_radius_tracked, a->map_radius_lost, at(L.dyn), at(L.pose_map), hdr + kTrkTracked};
     if ((rc = uh::pnp_enqueue_dev(pnp, par(L.par_pose0), par(L.par_intr), std::min(L.cap1, L.capn), hdr + kTrkN1, s1.p3d, s1.kp, s1.isg, s1.wgt, at(L.pose1), at(L.bad1),
-                                  hdr + kTrkRes1, &dec, s1.dep, bl))) return rc;
+                                  hdr + kTrkRes1, &dec, s1.dep, bl, n_mk, par(L.par_mkp), par(L.par_mks), par(L.par_mkc)))) return rc;
     // ---- 2: the search of the local map at the decided pose / radius (slot 1), the union, the second solve
     if (nm) {
         const PmTrack t{nullptr, a->map_weight, nullptr, at(L.pos_map), at(L.aux_map)};
@@ -394,7 +407,7 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     const TrkSelect s2 = select_args(1, pd2);
     if ((rc = select_launch(h, s2, L.capa))) return rc;
     if ((rc = uh::pnp_enqueue_dev(pnp, at(L.pose_map), par(L.par_intr), L.capn, hdr + kTrkNA, s2.p3d, s2.kp, s2.isg, s2.wgt, at(L.pose2), at(L.bada), hdr + kTrkRes2, nullptr,
-                                  s2.dep, bl))) return rc;
+                                  s2.dep, bl, n_mk, par(L.par_mkp), par(L.par_mks), par(L.par_mkc)))) return rc;
     // ---- 3: everything back in one block
     const TrkPublish pb{hdr, at(L.pose1), at(L.pose2), at(L.m1), at(L.bad1), at(L.m2), at(L.ma), at(L.bada), L.cap1, L.cap2, L.capa,   // (the pinned twins at the same offsets)
                         out(L.hdr), out(L.pose1), out(L.pose2), out(L.m1), out(L.bad1), out(L.m2), out(L.ma), out(L.bada), T.h_par.dev<unsigned long long>(), ++T.seq};
@@ -433,11 +446,15 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
 
 extern "C" {
 
-int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track_result* r) { return track_pose(h, pnp, a, nullptr, r); }
+int uh_track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, uh_track_result* r) { return track_pose(h, pnp, a, nullptr, nullptr, r); }
 
 int uh_track_pose_stereo(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* stereo, uh_track_result* r) {
     UH_REQUIRE(stereo, "uh_track_pose_stereo: NULL stereo argument");
-    return track_pose(h, pnp, a, stereo, r);
+    return track_pose(h, pnp, a, stereo, nullptr, r);
+}
+
+int uh_track_pose_markers(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_track_stereo* stereo, const uh_pnp_markers* markers, uh_track_result* r) {
+    return track_pose(h, pnp, a, stereo, markers, r);
 }
 
 }  // extern "C"

@@ -52,6 +52,7 @@ class _TrackStereo(C.Structure):
 def _declare(L, sig):
     sig("uh_track_pose", I, VP, VP, C.POINTER(_TrackArgs), C.POINTER(_TrackResult))
     sig("uh_track_pose_stereo", I, VP, VP, C.POINTER(_TrackArgs), C.POINTER(_TrackStereo), C.POINTER(_TrackResult))
+    sig("uh_track_pose_markers", I, VP, VP, C.POINTER(_TrackArgs), C.POINTER(_TrackStereo), VP, C.POINTER(_TrackResult))
     sig("uh_projmatch_create", I, VP, C.POINTER(VP))
     sig("uh_projmatch_destroy", None, VP)
     sig("uh_projmatch_set_frame", I, VP, C.POINTER(_ProjFrame))
@@ -188,8 +189,17 @@ class ProjectionMatcher:
         return self._track(pnp, pose0, intr4, inv_sigma_levels, prev, mp, prev_map_row, map_weight, prev_min_desc_dist, prev_max_repj_dist,
                            map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, (depth, bl, prev_weight))
 
+    def trackPoseMarkers(self, pnp, pose0, intr4, inv_sigma_levels, prev, mp, markers=None, depth=None, bl=0.0, prev_weight=None, prev_map_row=None,
+                         map_weight=None, prev_min_desc_dist=75.0, prev_max_repj_dist=15.0, map_min_desc_dist=100.0, map_radius_tracked=4.0,
+                         map_radius_lost=15.0, min_inliers=30):
+        """uh_track_pose_markers: trackPoseStereo whose two solves also see the frame's selected markers (markers = dict(pose_g2m, size,
+        und_corners) as PnPSolver.solvePnp takes them, or None).  depth / prev_weight None: the monocular tracker.  Same result dict."""
+        stereo = None if depth is None and prev_weight is None else (depth, bl, prev_weight)
+        return self._track(pnp, pose0, intr4, inv_sigma_levels, prev, mp, prev_map_row, map_weight, prev_min_desc_dist, prev_max_repj_dist,
+                           map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, stereo, markers, True)
+
     def _track(self, pnp, pose0, intr4, inv_sigma_levels, prev, mp, prev_map_row, map_weight, prev_min_desc_dist, prev_max_repj_dist,
-               map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, stereo):
+               map_min_desc_dist, map_radius_tracked, map_radius_lost, min_inliers, stereo, markers=None, markers_entry=False):
         pose = np.ascontiguousarray(pose0, np.float32).reshape(16)
         intr = np.ascontiguousarray(intr4, np.float32).reshape(4)
         isl = np.ascontiguousarray(inv_sigma_levels, np.float32)
@@ -211,7 +221,21 @@ class ProjectionMatcher:
         m2 = np.zeros(max(n_m, 1), DMATCH_DTYPE)
         mA = np.zeros(max(n_p + n_m, 1), DMATCH_DTYPE); bA = np.zeros(max(n_p + n_m, 1), np.uint8)
         res = _TrackResult(np_ptr(m1), np_ptr(b1), len(m1), np_ptr(m2), len(m2), np_ptr(mA), np_ptr(bA), len(mA))
-        if stereo is None:
+        sx = None
+        if stereo is not None:
+            dep = np.ascontiguousarray(stereo[0], np.float32) if stereo[0] is not None else None
+            pw = np.ascontiguousarray(stereo[2], np.float32) if stereo[2] is not None else None
+            if pw is not None and pw.shape != (n_p,):
+                raise ValueError(f"prev_weight: expected {n_p} values, got shape {pw.shape}")
+            sx = _TrackStereo(np_ptr(dep) if dep is not None else None, float(stereo[1]), np_ptr(pw) if pw is not None and n_p else None)
+        if markers_entry:
+            from .pnp import pack_markers
+
+            mk, keep = pack_markers(markers) if markers is not None else (None, None)
+            check(lib().uh_track_pose_markers(self._h, pnp._h, C.byref(args), C.byref(sx) if sx is not None else None,
+                                              C.cast(C.pointer(mk), VP) if mk is not None else None, C.byref(res)))
+            del keep
+        elif stereo is None:
             check(lib().uh_track_pose(self._h, pnp._h, C.byref(args), C.byref(res)))
         else:
             dep = np.ascontiguousarray(stereo[0], np.float32) if stereo[0] is not None else None
