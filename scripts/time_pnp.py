@@ -2,7 +2,8 @@
 """Pose-only solve (uh_pnp_solve, host in / host out): wall time per call and the kernel's own clock stamps, by match count.
 --stereo: uh_pnp_solve_stereo on tests/stereo_synth.py problems (about 60 % of the matches with a depth); --n N1,N2,..: the match counts;
 --markers M1,M2,..: every match count also with that many markers (tests/marker_synth.py; 0 = the marker-free call, uh_pnp_solve_markers
-with one or more); --reps R: the wall time R times over (the spread of a number measured against another build)."""
+with one or more); --reps R: the wall time R times over (the spread of a number measured against another build); --dump FILE: pose,
+state, bad, iters and ngood of one solve per configuration into FILE (.npz), to compare two builds byte for byte."""
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -23,6 +24,7 @@ marker_counts = (0,)
 if "--markers" in sys.argv:
     marker_counts = tuple(int(v) for v in sys.argv[sys.argv.index("--markers") + 1].split(","))
 reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 1
+dump, dumped = (sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None), {}
 for n, n_mk in ((n, m) for n in counts for m in marker_counts):
     pr = stereo_synth.stereo_pnp_problem(n, seed=3) if stereo else synth.pnp_problem(n, seed=3)
     args = (pr["pose"], pr["intr"], pr["p3d"], pr["kp"], pr["invsig"], pr["weight"])
@@ -38,6 +40,8 @@ for n, n_mk in ((n, m) for n in counts for m in marker_counts):
             r = sol.solvePnp(*args, **kw)
         walls.append((time.perf_counter() - t) / 50 * 1e6)
     wall = walls[-1]
+    for k in ("pose", "state", "bad", "iters", "ngood") if dump else ():
+        dumped[f"{'stereo' if stereo else 'mono'}_n{n}_mk{n_mk}_{k}"] = np.asarray(r[k])
     sol.debug_clocks(True)
     sol.solvePnp(*args, **kw)
     c = sol.debug_clocks(True)
@@ -51,3 +55,5 @@ for n, n_mk in ((n, m) for n in counts for m in marker_counts):
     if reps > 1:
         print("   wall per call over the repetitions [us]:", " ".join(f"{w:.1f}" for w in walls))
     print(f"{'stereo ' if stereo else ''}{f'markers {n_mk} ' if n_mk else ''}n={n:5d} wall {wall:7.1f} us  iters {r['iters'].tolist()} passes {c[4]}  clk: stage {c[1]-c[0]} rounds {c[2]-c[1]} post {c[3]-c[2]} total {tot}  per pass {(c[2]-c[1])/max(c[4],1):.0f}")
+if dump:
+    np.savez(dump, **dumped)

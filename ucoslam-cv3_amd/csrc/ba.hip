@@ -139,41 +139,7 @@ struct BAPtrs {
 __device__ __forceinline__ void uh_latency_critical() { __builtin_amdgcn_s_setprio(3); }
 
 // ------------------------------------------------------------------------------------------------ small fp64 helpers
-__device__ __forceinline__ void quat_to_R(const double* q, double* R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-__device__ __forceinline__ void quat_from_R(const double* R, double* q) {   // Eigen::Quaternion(Matrix3)
-    double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else if (!(R[4] > R[0]) && !(R[8] > R[0])) {   // i = 0, j = 1, k = 2   (static indices: a runtime-indexed R[] would live in scratch)
-        t = sqrt(R[0] - R[4] - R[8] + 1.0);
-        q[0] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[7] - R[5]) * t; q[1] = (R[3] + R[1]) * t; q[2] = (R[6] + R[2]) * t;
-    } else if (R[4] > R[0] && !(R[8] > R[4])) {    // i = 1, j = 2, k = 0
-        t = sqrt(R[4] - R[8] - R[0] + 1.0);
-        q[1] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[2] - R[6]) * t; q[2] = (R[7] + R[5]) * t; q[0] = (R[1] + R[3]) * t;
-    } else {                                     // i = 2, j = 0, k = 1
-        t = sqrt(R[8] - R[0] - R[4] + 1.0);
-        q[2] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[3] - R[1]) * t; q[0] = (R[2] + R[6]) * t; q[1] = (R[5] + R[7]) * t;
-    }
-}
-__device__ __forceinline__ void quat_norm_pos(double* q) {
-    if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
+#include "se3.hpp"   // quat_to_R, quat_from_R, quat_norm_pos
 __device__ __forceinline__ void inv3(const double* M, double* I) {
     const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
     const double id = 1.0 / (M[0] * c00 + M[1] * c01 + M[2] * c02);

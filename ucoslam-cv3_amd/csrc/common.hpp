@@ -207,6 +207,8 @@ namespace uh {
 // and the small disc, else the predicted pose and the wide radius" (system.cpp:6762-6881) — and leaves the local-map search its pose (rows +
 // camera centre, 15 floats), radius (float 15) and a zero word (16) at dyn17, the chosen pose at pose_map (16 floats), the flag at tracked
 struct PnpDecide { int min_inliers; float r_tracked, r_lost; float* dyn17; float* pose_map; int* tracked; };
+// the match arrays of a pose-only solve (device-visible, one entry per match); depth: NULL, or Frame::getDepth per match with the baseline bl
+struct PnpMatches { const float* p3d; const float* kp; const float* inv_sigma; const float* weight; const float* depth; float bl; };
 }  // namespace uh
 
 #define UH_LAUNCH(ctx, kernel, grid, block, shmem, ...)                                        \

@@ -1,15 +1,22 @@
 // Per-frame pose-only optimisation on MI355X (gfx950), fp64, behind the C ABI (uh_pnp_*).
 //
-// Semantic contract = PnPSolver::solvePnp for monocular / stereo matches and squared planar markers (reference file:line):
+// Semantic contract = PnPSolver::solvePnp (reference file:line):
 //   src/optimization/pnpsolver.cpp:116-409  four rounds; each restarts from the INPUT pose (:354), runs optimize(10)
-//                                           (minChi2BetweenIter = 0), reclassifies every match with chi2 > 5.99 as outlier
+//                                           (minChi2BetweenIter = 0), reclassifies every match with chi2 above its limit as outlier
 //                                           (excluded edges get a fresh error first, :364), drops the robust kernels from the
 //                                           third round on (:368) and stops early below 10 inliers (:379)
-//   src/optimization/typesg2o.h:590-650     EdgeSE3ProjectXYZOnlyPose error and 2x6 Jacobian
-//   src/optimization/typesg2o.h:82-105      WeightedHubberRobustKernel: the weight scales rho (the chi2 sums), not the Jacobian
 //   3rdparty/g2o                            Levenberg loop, lambda init/update, SE3 exp — as in ba.hip
-//   src/optimization/pnpsolver.cpp:280-386  markers (the MARKERS instantiations): one MarkerEdgeOnlyProject (typesg2o.h:414-471) per marker
-//                                           with g2o's numeric Jacobian (base_binary_edge.hpp:165-233), see "markers" below
+//   src/optimization/typesg2o.h:82-105      WeightedHubberRobustKernel: the weight scales rho (the chi2 sums), not the Jacobian
+// and its three edge types, one template parameter each where they cost anything:
+//   typesg2o.h:590-650   EdgeSE3ProjectXYZOnlyPose        two rows, limit 5.99: every match without a depth               (project)
+//   typesg2o.h:521-590   EdgeStereoSE3ProjectXYZOnlyPose  three rows, limit 7.815, kernel weight doubled: a match with a
+//                        depth (pnpsolver.cpp:239-276), STEREO instantiations only                                        (project_st)
+//   typesg2o.h:414-471   MarkerEdgeOnlyProject            eight rows per marker, g2o's numeric Jacobian (base_binary_edge.hpp:165-233),
+//                        pnpsolver.cpp:280-386, MARKERS instantiations only, see "markers" below                          (marker_err)
+// A match goes through ONE evaluation whatever its type: `edge` (project or project_st) and `robust` (the one `huber` with the edge type's
+// weight and threshold) are what the classification, the accumulation and the damping ladder all call; `to_camera` is the transform of all
+// three edge types; `rt_from_pose16` makes the input pose and the markers' poses.  An instantiation without stereo holds st == false as a
+// constant: the three-row branch is not in its code.
 //
 // MI355X design: one 6x6 system over a few hundred to a few thousand matches, ~20 dependent Levenberg trials — pure latency, so
 // the WHOLE solve runs inside ONE workgroup of one launch and every trial costs ONE pass over the matches and ONE barrier:
@@ -32,6 +39,7 @@
 
 #include "common.hpp"
 #include "reduce.hpp"
+#include "se3.hpp"
 
 namespace {
 
@@ -79,42 +87,25 @@ __device__ void pnp_decide(const PnpArgs& A, int inliers, const float* M) {
     *A.dec.tracked = tracked;
 }
 
-struct PoseD { double q[4], t[3], Rt[12]; };
-
-__device__ __forceinline__ void p_quat_to_R(const double* q, double* R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3], txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy; R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+// row-major float[16] -> Rt[12] (R row-major, then t) as g2o::SE3Quat(R, t) holds it: the rotation is the one of the NORMALISED quaternion.
+// (q, t and Rt as one local object that is copied out: written so, both callers compile to the code they had with the steps written out)
+__device__ __forceinline__ void rt_from_pose16(const float* M, double* Rt) {
+    struct { double q[4], t[3], Rt[12]; } P;
+    const double R0[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
+    quat_from_R(R0, P.q);
+    quat_norm_pos(P.q);
+    P.t[0] = M[3]; P.t[1] = M[7]; P.t[2] = M[11];
+    quat_to_R(P.q, P.Rt);
+    P.Rt[9] = P.t[0]; P.Rt[10] = P.t[1]; P.Rt[11] = P.t[2];
+#pragma unroll
+    for (int i = 0; i < 12; i++) Rt[i] = P.Rt[i];
 }
-__device__ __forceinline__ void p_quat_from_R(const double* R, double* q) {
-    double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else if (!(R[4] > R[0]) && !(R[8] > R[0])) {   // i = 0, j = 1, k = 2   (static indices: a runtime-indexed R[] would live in scratch)
-        t = sqrt(R[0] - R[4] - R[8] + 1.0);
-        q[0] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[7] - R[5]) * t; q[1] = (R[3] + R[1]) * t; q[2] = (R[6] + R[2]) * t;
-    } else if (R[4] > R[0] && !(R[8] > R[4])) {    // i = 1, j = 2, k = 0
-        t = sqrt(R[4] - R[8] - R[0] + 1.0);
-        q[1] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[2] - R[6]) * t; q[2] = (R[7] + R[5]) * t; q[0] = (R[1] + R[3]) * t;
-    } else {                                     // i = 2, j = 0, k = 1
-        t = sqrt(R[8] - R[0] - R[4] + 1.0);
-        q[2] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[3] - R[1]) * t; q[0] = (R[2] + R[6]) * t; q[1] = (R[5] + R[7]) * t;
-    }
+// the camera-frame point of X under Rt
+__device__ __forceinline__ void to_camera(const double* Rt, double X0, double X1, double X2, double& p0, double& p1, double& p2) {
+    p0 = fma(Rt[2], X2, fma(Rt[1], X1, fma(Rt[0], X0, Rt[9])));
+    p1 = fma(Rt[5], X2, fma(Rt[4], X1, fma(Rt[3], X0, Rt[10])));
+    p2 = fma(Rt[8], X2, fma(Rt[7], X1, fma(Rt[6], X0, Rt[11])));
 }
-__device__ __forceinline__ void p_quat_norm(double* q) {
-    if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-__device__ __forceinline__ void p_set_Rt(PoseD& T) { p_quat_to_R(T.q, T.Rt); T.Rt[9] = T.t[0]; T.Rt[10] = T.t[1]; T.Rt[11] = T.t[2]; }
 // ---- fp64 primitives of the serial path: v_rcp_f64 / v_rsq_f64 + two Newton steps (<= 1 ulp) instead of the IEEE division /
 // square-root expansions (a dozen instructions each, on a path where every instruction is latency)
 __device__ __forceinline__ double rcp_nr(double x) {
@@ -318,16 +309,11 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         rec[e] = r;
     }
     {
-        PoseD P;
-        const float* M = A.pose_in;
-        const double R0[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
-        p_quat_from_R(R0, P.q);       // g2o::SE3Quat(R, t): the rotation the optimisation starts from is the one of the NORMALISED quaternion
-        p_quat_norm(P.q);
-        P.t[0] = M[3]; P.t[1] = M[7]; P.t[2] = M[11];
-        p_set_Rt(P);
+        double Rt0[12];
+        rt_from_pose16(A.pose_in, Rt0);
         if (tid == 0) {
 #pragma unroll
-            for (int i = 0; i < 12; i++) { s_pose[3][i] = P.Rt[i]; s_pose[1][i] = P.Rt[i]; s_pose[2][i] = P.Rt[i]; }
+            for (int i = 0; i < 12; i++) { s_pose[3][i] = Rt0[i]; s_pose[1][i] = Rt0[i]; s_pose[2][i] = Rt0[i]; }
         }
     }
     // markers: the records, and weight_marker of pnpsolver.cpp:305-310 in its mixed float / double arithmetic — KpWeightSum is the
@@ -350,13 +336,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         ws = block_sum<kPnpWaves>(ws, s_part);
         if (tid == 0) *s_mkw = ((double)(0.3f * (float)(n + nmk)) / (1. - (double)0.3f)) / (double)(float)ws;
         if (tid < nmk) {
-            const float* M = A.mk_pose + 16 * tid;
-            PoseD G;
-            const double R0[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
-            p_quat_from_R(R0, G.q);
-            p_quat_norm(G.q);
-            G.t[0] = M[3]; G.t[1] = M[7]; G.t[2] = M[11];
-            p_set_Rt(G);
+            double G[12];   // Marker::pose_g2m
+            rt_from_pose16(A.mk_pose + 16 * tid, G);
             const float sz = A.mk_size[tid];
             const double hi = (double)(float)((double)sz / 2.), lo = (double)(float)(-(double)sz / 2.);   // Marker::get3DPointsLocalRefSystem: cv::Point3f
             const double px[4] = {lo, hi, hi, lo}, py[4] = {hi, hi, lo, lo};
@@ -364,7 +345,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
 #pragma unroll
             for (int c = 0; c < 4; c++)
 #pragma unroll
-                for (int a = 0; a < 3; a++) r.P[c][a] = fma(G.Rt[3 * a + 1], py[c], fma(G.Rt[3 * a], px[c], G.Rt[9 + a]));
+                for (int a = 0; a < 3; a++) r.P[c][a] = fma(G[3 * a + 1], py[c], fma(G[3 * a], px[c], G[9 + a]));
 #pragma unroll
             for (int i = 0; i < 8; i++) r.uv[i] = A.mk_corners[8 * tid + i];
             r.robust = 1; r.pad = 0;
@@ -382,10 +363,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     // the error of corner c of a marker at the pose Rt perturbed by pattern k: 0 = not, 1..6 = +delta along dimension k - 1, 7..12 =
     // -delta along dimension k - 7.  Projections rounded to float (typesg2o.h:461-465)
     auto marker_err = [&](const MarkerRec& m, int c, int k, const double* Rt, double& ex, double& ey) {
-        const double X0 = m.P[c][0], X1 = m.P[c][1], X2 = m.P[c][2];
-        double p0 = fma(Rt[2], X2, fma(Rt[1], X1, fma(Rt[0], X0, Rt[9])));
-        double p1 = fma(Rt[5], X2, fma(Rt[4], X1, fma(Rt[3], X0, Rt[10])));
-        double p2 = fma(Rt[8], X2, fma(Rt[7], X1, fma(Rt[6], X0, Rt[11])));
+        double p0, p1, p2;
+        to_camera(Rt, m.P[c][0], m.P[c][1], m.P[c][2], p0, p1, p2);
         if (k > 0) {
             const double sg = k > 6 ? -1.0 : 1.0;
             const int d = k > 6 ? k - 7 : k - 1;
@@ -419,10 +398,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
 
     // chi2 of a match at the pose Rt; xz, yz, invz for the Jacobian
     auto project = [&](const MatchRec& m, const double* Rt, double& ex, double& ey, double& xz, double& yz, double& invz) -> double {
-        const double X0 = m.X, X1 = m.Y, X2 = m.Z;
-        const double p0 = fma(Rt[2], X2, fma(Rt[1], X1, fma(Rt[0], X0, Rt[9])));
-        const double p1 = fma(Rt[5], X2, fma(Rt[4], X1, fma(Rt[3], X0, Rt[10])));
-        const double p2 = fma(Rt[8], X2, fma(Rt[7], X1, fma(Rt[6], X0, Rt[11])));
+        double p0, p1, p2;
+        to_camera(Rt, m.X, m.Y, m.Z, p0, p1, p2);
         invz = rcp_nr(p2);
         xz = p0 * invz; yz = p1 * invz;
         ex = (double)m.u - fma(xz, fx, cx);
@@ -433,10 +410,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     // double, un-fused; the Jacobian uses the double 1/z (invz, as the monocular edge's).  er = kp_ur - (u_proj - bf / z).
     auto project_st = [&](const MatchRec& m, float ur, const double* Rt, double& ex, double& ey, double& er, double& xz, double& yz,
                           double& invz) -> double {
-        const double X0 = m.X, X1 = m.Y, X2 = m.Z;
-        const double p0 = fma(Rt[2], X2, fma(Rt[1], X1, fma(Rt[0], X0, Rt[9])));
-        const double p1 = fma(Rt[5], X2, fma(Rt[4], X1, fma(Rt[3], X0, Rt[10])));
-        const double p2 = fma(Rt[8], X2, fma(Rt[7], X1, fma(Rt[6], X0, Rt[11])));
+        double p0, p1, p2;
+        to_camera(Rt, m.X, m.Y, m.Z, p0, p1, p2);
         invz = rcp_nr(p2);
         xz = p0 * invz; yz = p1 * invz;
         const double izf = (double)(float)(1.0 / p2);
@@ -446,6 +421,26 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         ey = (double)m.v - r1;
         er = (double)ur - r2;
         return (double)m.invsig * fma(er, er, fma(ex, ex, ey * ey));
+    };
+    // ---- the one edge evaluation of classify, accumulate and the ladder.  st: the match has the three-row edge (STEREO instantiations only;
+    // in the others it is the constant false and everything stereo folds away)
+    auto edge = [&](const MatchRec& m, bool st, float ur, const double* Rt, double& ex, double& ey, double& er, double& xz, double& yz, double& invz) -> double {
+        if constexpr (STEREO) { if (st) return project_st(m, ur, Rt, ex, ey, er, xz, yz, invz); }
+        return project(m, Rt, ex, ey, xz, yz, invz);
+    };
+    // WeightedHubberRobustKernel: returns rho[0] and leaves rho[1] in rho1 above the threshold (the caller's 1 stays below it)
+    auto huber = [&](double c, double wt, double dl, double ds, double& rho1) -> double {
+        if (c <= ds) return wt * c;
+        const double rs = rsq_nr(c);
+        const double rc = wt * fma(2 * (c * rs), dl, -ds);   // (rho[0] before rho[1]: the other order renames the monocular kernels' registers)
+        rho1 = dl * rs;
+        return rc;
+    };
+    // the kernel of a match: the stereo edge's weight is doubled in float (pnpsolver.cpp:258) and its threshold is thHuber3D
+    auto robust = [&](const MatchRec& m, bool st, double c, double& rho1) -> double {
+        double wt = m.weight, dl = delta, ds = dsqr;
+        if constexpr (STEREO) { if (st) { wt = (double)(m.weight * 2.f); dl = delta3; ds = dsqr3; } }
+        return huber(c, wt, dl, ds, rho1);
     };
 
     // One pass over this thread's matches (every wave).  classify: first the reclassification that ends a round
@@ -460,48 +455,26 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
         for (int e = tid; e < n; e += kPnpThreads) {
             const MatchRec m = rec[e];
             unsigned f = m.flags;
-            double ex, ey, xz, yz, invz;
-            bool st = false;   // STEREO: this match has the three-row edge
+            double ex, ey, er = 0, xz, yz, invz;
+            bool st = false;
             float ur = 0.f;
-            double er = 0;
             if constexpr (STEREO) { st = (f & kStereo) != 0; ur = urs[e]; }
             if (classify) {
                 double Rs[12];
 #pragma unroll
                 for (int i = 0; i < 12; i++) Rs[i] = s_pose[(f & kBad) ? 1 : 2][i];   // (read per match: four classifying passes per solve)
-                double c;
-                bool b;
-                if constexpr (STEREO) {
-                    c = st ? project_st(m, ur, Rs, ex, ey, er, xz, yz, invz) : project(m, Rs, ex, ey, xz, yz, invz);
-                    b = c > (st ? (double)7.815f : (double)5.99f);
-                } else {
-                    c = project(m, Rs, ex, ey, xz, yz, invz);
-                    b = c > (double)5.99f;
-                }
+                const double c = edge(m, st, ur, Rs, ex, ey, er, xz, yz, invz);
+                const bool b = c > (double)(st ? 7.815f : 5.99f);   // Chi3D, Chi2D
                 f = (b ? kBad : kActive) | (drop_robust ? 0u : (f & kRobust));
                 if constexpr (STEREO) f |= m.flags & kStereo;
                 rec[e].flags = f;
                 acc[28] += b ? 0.0 : 1.0;
             }
             if (!(f & kActive) || !accumulate) continue;
-            double c;
-            if constexpr (STEREO) c = st ? project_st(m, ur, RtA, ex, ey, er, xz, yz, invz) : project(m, RtA, ex, ey, xz, yz, invz);
-            else c = project(m, RtA, ex, ey, xz, yz, invz);
+            const double c = edge(m, st, ur, RtA, ex, ey, er, xz, yz, invz);
             const double w = m.invsig;
             double rho1 = 1.0, rc = c;
-            if (f & kRobust) {
-                if constexpr (STEREO) {
-                    // the stereo edge's kernel weight is doubled in float (pnpsolver.cpp:258) and its threshold is thHuber3D
-                    const double wt = st ? (double)(m.weight * 2.f) : (double)m.weight;
-                    const double dl = st ? delta3 : delta, ds = st ? dsqr3 : dsqr;
-                    if (c <= ds) rc = wt * c;
-                    else { const double rs = rsq_nr(c); rc = wt * fma(2 * (c * rs), dl, -ds); rho1 = dl * rs; }
-                } else {
-                    const double wt = m.weight;
-                    if (c <= dsqr) rc = wt * c;
-                    else { const double rs = rsq_nr(c); rc = wt * fma(2 * (c * rs), delta, -dsqr); rho1 = delta * rs; }
-                }
-            }
+            if (f & kRobust) rc = robust(m, st, c, rho1);
             acc[27] += rc;
             // 2x6 Jacobian rows (typesg2o.h:614-650): j = d ex / d xi, k = d ey / d xi; j[4] = k[3] = 0
             const double zf = invz * fx, zg = invz * fy, xf = xz * fx, yg = yz * fy;
@@ -657,28 +630,12 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
                 for (int e = tid; e < n; e += kPnpThreads) {
                     const MatchRec m = rec[e];
                     if (!(m.flags & kActive)) continue;
-                    double ex, ey, xz, yz, invz;
-                    double rc;
-                    if constexpr (STEREO) {
-                        const bool st = (m.flags & kStereo) != 0;
-                        double er;
-                        const double c = st ? project_st(m, urs[e], Rt, ex, ey, er, xz, yz, invz) : project(m, Rt, ex, ey, xz, yz, invz);
-                        rc = c;
-                        if (m.flags & kRobust) {
-                            const double wt = st ? (double)(m.weight * 2.f) : (double)m.weight;
-                            const double dl = st ? delta3 : delta, ds = st ? dsqr3 : dsqr;
-                            if (c <= ds) rc = wt * c;
-                            else rc = wt * fma(2 * (c * rsq_nr(c)), dl, -ds);
-                        }
-                    } else {
-                        const double c = project(m, Rt, ex, ey, xz, yz, invz);
-                        rc = c;
-                        if (m.flags & kRobust) {
-                            const double wt = m.weight;
-                            if (c <= dsqr) rc = wt * c;
-                            else rc = wt * fma(2 * (c * rsq_nr(c)), delta, -dsqr);
-                        }
-                    }
+                    double ex, ey, er, xz, yz, invz, rho1;
+                    bool st = false;
+                    if constexpr (STEREO) st = (m.flags & kStereo) != 0;
+                    const double c = edge(m, st, st ? urs[e] : 0.f, Rt, ex, ey, er, xz, yz, invz);   // (kp_ur read only for a stereo match: read for every match, a stereo pass costs 1-2 % more clocks)
+                    double rc = c;
+                    if (m.flags & kRobust) rc = robust(m, st, c, rho1);
                     chi[k] += rc;
                 }
             }
@@ -925,19 +882,15 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
             double Tend[12];
 #pragma unroll
             for (int i = 0; i < 12; i++) Tend[i] = s_pose[1][i];
-            float* M = A.pose_out;
+            float M[16];   // the pose this solve returns: pose_out, and what the tracker's decision reads
             for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) M[r * 4 + c] = (float)Tend[r * 3 + c]; M[r * 4 + 3] = (float)Tend[9 + r]; }
             M[12] = M[13] = M[14] = 0.f; M[15] = 1.f;
-            if (A.dec.dyn17) {
-                float Mv[16];
-                for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Mv[r * 4 + c] = (float)Tend[r * 3 + c]; Mv[r * 4 + 3] = (float)Tend[9 + r]; }
-                Mv[12] = Mv[13] = Mv[14] = 0.f; Mv[15] = 1.f;
-                pnp_decide(A, n > 0 ? good : 0, Mv);
-            }
+            for (int i = 0; i < 16; i++) A.pose_out[i] = M[i];
+            if (A.dec.dyn17) pnp_decide(A, n > 0 ? good : 0, M);
             if (A.state_out) {
                 double q[4];
-                p_quat_from_R(Tend, q);
-                p_quat_norm(q);
+                quat_from_R(Tend, q);
+                quat_norm_pos(q);
                 for (int i = 0; i < 4; i++) A.state_out[i] = q[i];
                 for (int i = 0; i < 3; i++) A.state_out[4 + i] = Tend[9 + i];
             }
@@ -953,6 +906,15 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
     }
     if (A.clk && tid == 0) A.clk[3] = __builtin_readcyclecounter();
 }
+// the eight instantiations, in the order the device code has always held them (launch_as below would name them in another)
+template __global__ void pnp_solve_kernel<true, true, false>(PnpArgs);
+template __global__ void pnp_solve_kernel<false, true, false>(PnpArgs);
+template __global__ void pnp_solve_kernel<true, false, false>(PnpArgs);
+template __global__ void pnp_solve_kernel<false, false, false>(PnpArgs);
+template __global__ void pnp_solve_kernel<true, true, true>(PnpArgs);
+template __global__ void pnp_solve_kernel<false, true, true>(PnpArgs);
+template __global__ void pnp_solve_kernel<true, false, true>(PnpArgs);
+template __global__ void pnp_solve_kernel<false, false, true>(PnpArgs);
 
 }  // namespace
 
@@ -970,26 +932,16 @@ namespace {
 
 constexpr size_t pnp_rec_bytes(bool stereo) { return stereo ? kPnpRecBytesStereo : sizeof(MatchRec); }
 
-// the fields every entry sets; the callers add the device-side match count, the decision or the completion word
-PnpArgs pnp_args(const float* pose, const float* intr, int n, const float* p3d, const float* kp, const float* inv_sigma, const float* weight, const float* depth,
-                 float bl, void* work, float* pose_out, unsigned char* bad_out, int* result, double* state_out) {
+// the fields every entry sets; the callers add the device-side match count, the decision or the completion word.  mk: device-visible
+// arrays; NULL or no markers: the marker-free instantiations run
+PnpArgs pnp_args(const float* pose, const float* intr, int n, const uh::PnpMatches& m, const uh_pnp_markers* mk, void* work, float* pose_out, unsigned char* bad_out,
+                 int* result, double* state_out) {
     PnpArgs A{};
-    A.pose_in = pose; A.intr = intr; A.n = n; A.p3d = p3d; A.kp = kp; A.invsig = inv_sigma; A.weight = weight; A.depth = depth; A.bl = bl;
+    A.pose_in = pose; A.intr = intr; A.n = n; A.p3d = m.p3d; A.kp = m.kp; A.invsig = m.inv_sigma; A.weight = m.weight; A.depth = m.depth; A.bl = m.bl;
     A.work = work; A.pose_out = pose_out; A.bad_out = bad_out; A.result = result; A.state_out = state_out;
+    if (mk && mk->n > 0) { A.n_mk = mk->n; A.mk_pose = mk->pose_g2m; A.mk_size = mk->size; A.mk_corners = mk->und_corners; }
     return A;
 }
-
-// the dynamic-LDS limit of a CACHED instantiation, set once per solver object
-int lds_attr(uh_pnp* p, const void* kernel, bool stereo, bool markers = false) {
-    const size_t most = markers ? pnp_marker_offset(kPnpLdsMatches, stereo) + kPnpMarkerLds : kPnpLdsMatches * pnp_rec_bytes(stereo);
-    if (!p->attr_set[markers][stereo]) UH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    p->attr_set[markers][stereo] = true;
-    return UH_OK;
-}
-
-// the marker arrays of a solve (device-visible pointers); n_mk == 0: no markers, the marker-free instantiations run
-struct PnpMarkers { int n = 0; const float* pose = nullptr; const float* size = nullptr; const float* corners = nullptr; };
-void set_markers(PnpArgs& A, const PnpMarkers& m) { A.n_mk = m.n; A.mk_pose = m.pose; A.mk_size = m.size; A.mk_corners = m.corners; }
 
 // what every entry checks of a uh_pnp_markers before anything is launched; host_arrays: the sizes can be read here
 int check_markers(const char* fn, const uh_pnp_markers* m, bool host_arrays) {
@@ -1001,51 +953,47 @@ int check_markers(const char* fn, const uh_pnp_markers* m, bool host_arrays) {
     return UH_OK;
 }
 
-// the instantiation: matches in LDS up to kPnpLdsMatches (CACHED), the stereo edges with a depth array (STEREO)
+// one instantiation: the dynamic-LDS limit of a CACHED one is set once per solver object
+template <bool C, bool S, bool M>
+int launch_as(uh_pnp* p, const PnpArgs& A, size_t lds) {
+    if (C && !p->attr_set[M][S]) {
+        const size_t most = M ? pnp_marker_offset(kPnpLdsMatches, S) + kPnpMarkerLds : kPnpLdsMatches * pnp_rec_bytes(S);
+        UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_solve_kernel<C, S, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+        p->attr_set[M][S] = true;
+    }
+    static constexpr const char* scope[2][2][2] = {   // [C][S][M], the source spelling as UH_LAUNCH's scopes have it
+        {{"pnp_solve_kernel<false, false, false>", "pnp_solve_kernel<false, false, true>"}, {"pnp_solve_kernel<false, true, false>", "pnp_solve_kernel<false, true, true>"}},
+        {{"pnp_solve_kernel<true, false, false>", "pnp_solve_kernel<true, false, true>"}, {"pnp_solve_kernel<true, true, false>", "pnp_solve_kernel<true, true, true>"}}};
+    uh::ProfScope ps(p->ctx, scope[C][S][M]);
+    hipLaunchKernelGGL((pnp_solve_kernel<C, S, M>), dim3(1), dim3(kPnpThreads), lds, p->ctx->stream, A);
+    return UH_OK;
+}
+
+// the instantiation: matches in LDS up to kPnpLdsMatches (CACHED), the stereo edges with a depth array (STEREO), the marker edges with markers
 int launch(uh_pnp* p, PnpArgs& A) {
     A.clk = p->d_clk;
-    const bool cached = A.n <= kPnpLdsMatches, stereo = A.depth != nullptr;
-    const size_t lds = cached ? (size_t)std::max(A.n, 1) * pnp_rec_bytes(stereo) : 0;
-    int rc;
-    if (A.n_mk <= 0) {
-        // (stereo first, LDS form first in each: the order in which the instantiations have always been named, which fixes their order in the device code)
-        if (stereo) {
-            if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true, true>), true))) return rc;
-            if (cached) UH_LAUNCH(p->ctx, (pnp_solve_kernel<true, true>), dim3(1), dim3(kPnpThreads), lds, A);
-            else UH_LAUNCH(p->ctx, (pnp_solve_kernel<false, true>), dim3(1), dim3(kPnpThreads), 0, A);
-        } else {
-            if (cached && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<true>), false))) return rc;
-            if (cached) UH_LAUNCH(p->ctx, pnp_solve_kernel<true>, dim3(1), dim3(kPnpThreads), lds, A);
-            else UH_LAUNCH(p->ctx, pnp_solve_kernel<false>, dim3(1), dim3(kPnpThreads), 0, A);
-        }
-    } else {   // the marker instantiations, only ever launched with markers
-        const size_t lds_mk = (cached ? pnp_marker_offset(A.n, stereo) : 0) + kPnpMarkerLds;
-#define UH_PNP_LAUNCH_MK(C_, S_)                                                                                                     \
-    do {                                                                                                                             \
-        if (C_ && (rc = lds_attr(p, reinterpret_cast<const void*>(pnp_solve_kernel<C_, S_, true>), S_, true))) return rc;            \
-        UH_LAUNCH(p->ctx, (pnp_solve_kernel<C_, S_, true>), dim3(1), dim3(kPnpThreads), lds_mk, A);                                   \
-    } while (0)
-        if (stereo) { if (cached) UH_PNP_LAUNCH_MK(true, true); else UH_PNP_LAUNCH_MK(false, true); }
-        else { if (cached) UH_PNP_LAUNCH_MK(true, false); else UH_PNP_LAUNCH_MK(false, false); }
-#undef UH_PNP_LAUNCH_MK
-    }
+    const bool cached = A.n <= kPnpLdsMatches, stereo = A.depth != nullptr, markers = A.n_mk > 0;
+    const size_t lds = markers ? (cached ? pnp_marker_offset(A.n, stereo) : 0) + kPnpMarkerLds : cached ? (size_t)std::max(A.n, 1) * pnp_rec_bytes(stereo) : 0;
+    static constexpr int (*as[2][2][2])(uh_pnp*, const PnpArgs&, size_t) = {
+        {{launch_as<false, false, false>, launch_as<false, false, true>}, {launch_as<false, true, false>, launch_as<false, true, true>}},
+        {{launch_as<true, false, false>, launch_as<true, false, true>}, {launch_as<true, true, false>, launch_as<true, true, true>}}};
+    const int rc = as[cached][stereo][markers](p, A, lds);
+    if (rc) return rc;
     UH_HIP_CHECK(hipGetLastError());
     return UH_OK;
 }
 
 // uh_pnp_solve_dev (d_depth == NULL), uh_pnp_solve_stereo_dev and uh_pnp_solve_markers_dev (mk: device arrays, or NULL)
-int solve_dev(const char* fn, uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-              const float* d_weight, const float* d_depth, float bl, const uh_pnp_markers* mk, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
-              int32_t* d_result5, double* d_state7) {
+int solve_dev(const char* fn, uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const uh::PnpMatches& m, const uh_pnp_markers* mk, void* d_work,
+              float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
     UH_REQUIRE(p && d_pose_f2g && d_intr4 && d_pose_out && d_result5, "%s: NULL argument", fn);
     UH_REQUIRE(n >= 0, "%s: negative match count", fn);
-    if (d_depth) UH_REQUIRE(bl > 0.f, "%s: a depth array needs a baseline > 0 (bl = %g)", fn, (double)bl);
+    if (m.depth) UH_REQUIRE(m.bl > 0.f, "%s: a depth array needs a baseline > 0 (bl = %g)", fn, (double)m.bl);
     int rc;
     if ((rc = check_markers(fn, mk, false))) return rc;
-    if (n > 0) UH_REQUIRE(d_p3d && d_kp && d_inv_sigma && d_weight && d_work && d_bad_out, "%s: NULL match arrays", fn);
+    if (n > 0) UH_REQUIRE(m.p3d && m.kp && m.inv_sigma && m.weight && d_work && d_bad_out, "%s: NULL match arrays", fn);
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
-    PnpArgs A = pnp_args(d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
-    if (mk && mk->n > 0) { PnpMarkers m; m.n = mk->n; m.pose = mk->pose_g2m; m.size = mk->size; m.corners = mk->und_corners; set_markers(A, m); }
+    PnpArgs A = pnp_args(d_pose_f2g, d_intr4, n, m, mk, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
     return launch(p, A);
 }
 
@@ -1058,17 +1006,15 @@ int pnp_reserve(uh_pnp* p, int n_cap, bool stereo) {
     return n_cap > kPnpLdsMatches ? p->d_work.reserve((size_t)n_cap * pnp_rec_bytes(stereo)) : UH_OK;
 }
 // the solve behind uh_track_pose: everything resident, the match count decided by an earlier launch of the same stream
-// d_depth != NULL: the stereo form (per-match depth, baseline bl)
-int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl,
-                    int n_mk, const float* d_mk_pose, const float* d_mk_size, const float* d_mk_corners) {
+// m.depth != NULL: the stereo form; d_mk: NULL, or the frame's markers (device-visible arrays)
+int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const PnpMatches& m, const uh_pnp_markers* d_mk, float* d_pose_out,
+                    unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec) {
     UH_HIP_CHECK(hipSetDevice(p->ctx->device));
     int rc;
-    if ((rc = pnp_reserve(p, n_cap, d_depth != nullptr))) return rc;
-    PnpArgs A = pnp_args(d_pose, d_intr4, n_cap, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, p->d_work.p, d_pose_out, d_bad_out, d_result5, nullptr);
+    if ((rc = pnp_reserve(p, n_cap, m.depth != nullptr))) return rc;
+    PnpArgs A = pnp_args(d_pose, d_intr4, n_cap, m, d_mk, p->d_work.p, d_pose_out, d_bad_out, d_result5, nullptr);
     A.n_dev = d_n;
     if (dec) A.dec = *dec;
-    if (n_mk > 0) { PnpMarkers m; m.n = n_mk; m.pose = d_mk_pose; m.size = d_mk_size; m.corners = d_mk_corners; set_markers(A, m); }
     return launch(p, A);
 }
 }  // namespace uh
@@ -1089,7 +1035,7 @@ void uh_pnp_destroy(uh_pnp* p) { delete p; }
 int uh_pnp_solve_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                      const float* d_inv_sigma, const float* d_weight, void* d_work, float* d_pose_out, uint8_t* d_bad_out,
                      int32_t* d_result5, double* d_state7) {
-    return solve_dev("uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, nullptr, 0.f, nullptr, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    return solve_dev("uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, {d_p3d, d_kp, d_inv_sigma, d_weight, nullptr, 0.f}, nullptr, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
 // Stereo / RGB-D form of uh_pnp_solve_dev: d_depth (n floats, device) as in uh_pnp_solve_stereo; d_work = n * 36 bytes when d_depth is given.
@@ -1097,8 +1043,8 @@ int uh_pnp_solve_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, i
 int uh_pnp_solve_stereo_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_intr4, int n, const float* d_p3d, const float* d_kp,
                             const float* d_inv_sigma, const float* d_weight, const float* d_depth, float bl, void* d_work, float* d_pose_out,
                             uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
-    return solve_dev(d_depth ? "uh_pnp_solve_stereo_dev" : "uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth,
-                     d_depth ? bl : 0.f, nullptr, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
+    return solve_dev(d_depth ? "uh_pnp_solve_stereo_dev" : "uh_pnp_solve_dev", p, d_pose_f2g, d_intr4, n, {d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, d_depth ? bl : 0.f},
+                     nullptr, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
 // uh_pnp_solve_stereo_dev with markers: the three arrays of `markers` are device arrays too (the struct itself is the host's).  The sizes
@@ -1108,7 +1054,7 @@ int uh_pnp_solve_markers_dev(uh_pnp* p, const float* d_pose_f2g, const float* d_
                              void* d_work, float* d_pose_out, uint8_t* d_bad_out, int32_t* d_result5, double* d_state7) {
     if (!markers || markers->n == 0)
         return uh_pnp_solve_stereo_dev(p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, bl, d_work, d_pose_out, d_bad_out, d_result5, d_state7);
-    return solve_dev("uh_pnp_solve_markers_dev", p, d_pose_f2g, d_intr4, n, d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, d_depth ? bl : 0.f, markers, d_work,
+    return solve_dev("uh_pnp_solve_markers_dev", p, d_pose_f2g, d_intr4, n, {d_p3d, d_kp, d_inv_sigma, d_weight, d_depth, d_depth ? bl : 0.f}, markers, d_work,
                      d_pose_out, d_bad_out, d_result5, d_state7);
 }
 
@@ -1168,10 +1114,10 @@ int uh_pnp_solve_markers(uh_pnp* p, const float* pose_f2g, const float* intr4, i
         memcpy(h + o_mks, markers->size, (size_t)nmk * 4);
         memcpy(h + o_mkc, markers->und_corners, (size_t)nmk * 32);
     }
-    PnpArgs A = pnp_args((const float*)(d + o_pose), (const float*)(d + o_intr), n, (const float*)(d + o_p3d), (const float*)(d + o_kp), (const float*)(d + o_is),
-                         (const float*)(d + o_w), depth ? (const float*)(d + o_dep) : nullptr, bl, p->d_work.p, (float*)(d + o_pout), (unsigned char*)(d + o_bad),
-                         (int*)(d + o_res), (double*)(d + o_state));
-    if (nmk) { PnpMarkers m; m.n = nmk; m.pose = (const float*)(d + o_mkp); m.size = (const float*)(d + o_mks); m.corners = (const float*)(d + o_mkc); set_markers(A, m); }
+    auto df = [d](size_t o) { return (const float*)(d + o); };
+    const uh::PnpMatches dm{df(o_p3d), df(o_kp), df(o_is), df(o_w), depth ? df(o_dep) : nullptr, bl};
+    const uh_pnp_markers dmk{nmk, df(o_mkp), df(o_mks), df(o_mkc)};
+    PnpArgs A = pnp_args(df(o_pose), df(o_intr), n, dm, nmk ? &dmk : nullptr, p->d_work.p, (float*)(d + o_pout), (unsigned char*)(d + o_bad), (int*)(d + o_res), (double*)(d + o_state));
     A.host_done = (unsigned long long*)d;
     A.done_word = ++p->seq;
     std::atomic_thread_fence(std::memory_order_release);

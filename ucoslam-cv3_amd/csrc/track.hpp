@@ -25,9 +25,8 @@
 #pragma once
 
 namespace uh {
-int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const float* d_p3d, const float* d_kp, const float* d_inv_sigma,
-                    const float* d_weight, float* d_pose_out, unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec, const float* d_depth, float bl,
-                    int n_mk, const float* d_mk_pose, const float* d_mk_size, const float* d_mk_corners);
+int pnp_enqueue_dev(uh_pnp* p, const float* d_pose, const float* d_intr4, int n_cap, const int* d_n, const PnpMatches& m, const uh_pnp_markers* d_mk, float* d_pose_out,
+                    unsigned char* d_bad_out, int* d_result5, const PnpDecide* dec);
 int pnp_reserve(uh_pnp* p, int n_cap, bool stereo);
 uh_ctx* pnp_ctx(uh_pnp* p);
 }
@@ -383,7 +382,9 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
         if (stereo && !k) s.dep_src = par(L.par_dep);   // (the first select launch leaves the frame's depths in dep_kp)
         return s;
     };
-    const float bl = stereo ? sx->bl : 0.f;
+    // what both solves share: the markers (read in place) and the baseline; the match arrays are those their select launch filled
+    const uh_pnp_markers d_mk{n_mk, par(L.par_mkp), par(L.par_mks), par(L.par_mkc)};
+    auto matches_of = [bl = stereo ? sx->bl : 0.f](const TrkSelect& s) { return uh::PnpMatches{s.p3d, s.kp, s.isg, s.wgt, s.dep, bl}; };
     TrkInFlight in_flight{h};
     // ---- 1: the search against the previous frame (slot 0), its list and look-ups, the first solve
     PmPending pd1, pd2;
@@ -397,8 +398,8 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     // (the decision — refined pose + small disc or predicted pose + wide radius — rides on the solve's last thread)
     static_assert(sizeof(PmDyn) == 17 * 4, "PmDyn is what pnp_decide writes");
     const uh::PnpDecide dec{a->min_inliers, a->map_radius_tracked, a->map_radius_lost, at(L.dyn), at(L.pose_map), hdr + kTrkTracked};
-    if ((rc = uh::pnp_enqueue_dev(pnp, par(L.par_pose0), par(L.par_intr), std::min(L.cap1, L.capn), hdr + kTrkN1, s1.p3d, s1.kp, s1.isg, s1.wgt, at(L.pose1), at(L.bad1),
-                                  hdr + kTrkRes1, &dec, s1.dep, bl, n_mk, par(L.par_mkp), par(L.par_mks), par(L.par_mkc)))) return rc;
+    if ((rc = uh::pnp_enqueue_dev(pnp, par(L.par_pose0), par(L.par_intr), std::min(L.cap1, L.capn), hdr + kTrkN1, matches_of(s1), &d_mk, at(L.pose1), at(L.bad1), hdr + kTrkRes1, &dec)))
+        return rc;
     // ---- 2: the search of the local map at the decided pose / radius (slot 1), the union, the second solve
     if (nm) {
         const PmTrack t{nullptr, a->map_weight, nullptr, at(L.pos_map), at(L.aux_map)};
@@ -406,8 +407,7 @@ int track_pose(uh_projmatch* h, uh_pnp* pnp, const uh_track_args* a, const uh_tr
     }
     const TrkSelect s2 = select_args(1, pd2);
     if ((rc = select_launch(h, s2, L.capa))) return rc;
-    if ((rc = uh::pnp_enqueue_dev(pnp, at(L.pose_map), par(L.par_intr), L.capn, hdr + kTrkNA, s2.p3d, s2.kp, s2.isg, s2.wgt, at(L.pose2), at(L.bada), hdr + kTrkRes2, nullptr,
-                                  s2.dep, bl, n_mk, par(L.par_mkp), par(L.par_mks), par(L.par_mkc)))) return rc;
+    if ((rc = uh::pnp_enqueue_dev(pnp, at(L.pose_map), par(L.par_intr), L.capn, hdr + kTrkNA, matches_of(s2), &d_mk, at(L.pose2), at(L.bada), hdr + kTrkRes2, nullptr))) return rc;
     // ---- 3: everything back in one block
     const TrkPublish pb{hdr, at(L.pose1), at(L.pose2), at(L.m1), at(L.bad1), at(L.m2), at(L.ma), at(L.bada), L.cap1, L.cap2, L.capa,   // (the pinned twins at the same offsets)
                         out(L.hdr), out(L.pose1), out(L.pose2), out(L.m1), out(L.bad1), out(L.m2), out(L.ma), out(L.bada), T.h_par.dev<unsigned long long>(), ++T.seq};

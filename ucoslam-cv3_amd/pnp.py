@@ -64,26 +64,21 @@ class PnPSolver:
         a = [np.ascontiguousarray(x, np.float32) for x in (pose_f2g, intr, p3d, kp, inv_sigma, weight)]
         n = len(a[4])
         out = dict(pose=np.zeros(16, np.float32), bad=np.zeros(max(n, 1), np.uint8), iters=np.zeros(4, np.int32), state=np.zeros(7, np.float64))
-        if markers is not None:
-            mk, keep = pack_markers(markers)
-            d = None
-            if depth is not None:
-                d = np.ascontiguousarray(depth, np.float32)
-                if d.shape != (n,):
-                    raise ValueError(f"depth: expected {n} values, got shape {d.shape}")
-            rc = lib().uh_pnp_solve_markers(self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]),
-                                            None if d is None else np_ptr(d), float(bl), C.byref(mk), np_ptr(out["pose"]), np_ptr(out["bad"]),
-                                            np_ptr(out["iters"]), np_ptr(out["state"]))
-            del keep
-        elif depth is None:
-            rc = lib().uh_pnp_solve(self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]), np_ptr(out["pose"]),
-                                    np_ptr(out["bad"]), np_ptr(out["iters"]), np_ptr(out["state"]))
-        else:
+        mk, keep = pack_markers(markers) if markers is not None else (None, None)
+        d = None
+        if depth is not None:
             d = np.ascontiguousarray(depth, np.float32)
             if d.shape != (n,):
                 raise ValueError(f"depth: expected {n} values, got shape {d.shape}")
-            rc = lib().uh_pnp_solve_stereo(self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]), np_ptr(d),
-                                           float(bl), np_ptr(out["pose"]), np_ptr(out["bad"]), np_ptr(out["iters"]), np_ptr(out["state"]))
+        common = (self._h, np_ptr(a[0]), np_ptr(a[1]), n, np_ptr(a[2]), np_ptr(a[3]), np_ptr(a[4]), np_ptr(a[5]))
+        res = (np_ptr(out["pose"]), np_ptr(out["bad"]), np_ptr(out["iters"]), np_ptr(out["state"]))
+        if mk is not None:
+            rc = lib().uh_pnp_solve_markers(*common, None if d is None else np_ptr(d), float(bl), C.byref(mk), *res)
+            del keep
+        elif d is None:
+            rc = lib().uh_pnp_solve(*common, *res)
+        else:
+            rc = lib().uh_pnp_solve_stereo(*common, np_ptr(d), float(bl), *res)
         if rc < 0:
             check(rc)
         out["ngood"] = rc
