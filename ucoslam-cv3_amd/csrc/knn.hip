@@ -15,8 +15,8 @@
 // in lane (= train index) order, on a heap that is DISTRIBUTED OVER LANES (lane j = heap slot j)
 // and manipulated with v_readlane / masked moves -- no LDS, no scratch, wave-uniform control flow.
 //
-// Large query sets (>= 6000 queries, k <= 16) take the two-phase form further down: an accept-list scan with two queries per wave and
-// a replay with one lane per query on register heaps ("two-phase exact search").
+// k <= 16 mostly takes an accept-list form further down ("two-phase exact search"): a scan that lists the rows the heap would accept, and a replay with one lane per
+// query on register heaps, as two launches or streamed through one.  Which form serves which (query count, k) is decided in plan_search() alone (table: DESIGN.md 4.2).
 //
 // Sharding (multi-GPU, row (e) of the scope table): a shard scan starts from an empty heap, so
 // its accept test is looser than the global one; it emits everything it accepted (a superset of
@@ -1677,17 +1677,15 @@ struct uh_knn {
     const int32_t* d_valid_rows = nullptr;   // uh_knn_set_valid_rows_dev: the shard scan's query rows from *d_valid_rows on get empty lists
     int row_offset = 0;           // global index of row 0 (uh_knn_set_row_offset): an index that holds only one tile of a sharded train set
     int qpw = 1;                  // queries per wave of the exact search (uh_knn_set_queries_per_wave)
-    // Exact search, nn <= 16, which kernels run (MI355X, 10 000 train rows; scripts/knn_forms.py): below 3000 queries the fused one-wave-per-query
-    // search (2000 x nn 10: 73 us, the list forms ~75-90); from 3000 queries on the accept-list forms — nn >= 6: scan and replay in ONE launch
-    // (knn_stream_kernel; 8000 x nn 10: 105 us against 126 as two launches and 154 fused), nn <= 5: two launches (the replay is short and the
-    // plain scan faster than the streaming one: 8000 x nn 2: 73 against 81 us).  UH_KNN_FORM=fused | twophase | stream forces one form.
-    int two_phase_min_nq = 3000;
-    int stream_min_nn = 6;
-    int stream_min_nq = 1;        // round 5: nn >= stream_min_nn takes the stream form at every size (2000 queries: 43 us against 74 fused, 64 queries: 33 against 61)
-    bool stream_when_few = true;  // ... and EVERY nn <= 16 while the one-query-per-wave form applies (queries + replay workgroups <= 2 per SIMD, ~2000 queries):
-                                  // nn 2: 20-34 us against 29-36 fused, nn 5: 24-37 against 42-52 (scripts/knn_nq_sweep.py, profiles/r05_knn_nq_sweep.txt)
-    unsigned replay_attr = 0;     // bit k: knn_replay_lane_kernel<k>'s dynamic-LDS attribute has been set on this index's device
+    // Thresholds of plan_search(), which alone decides the form of an exact search (table: DESIGN.md §4.2; measured on MI355X at 10 000 train rows,
+    // scripts/knn_forms.py, scripts/knn_nq_sweep.py).  UH_KNN_FORM=fused | twophase | stream moves them so that one form runs wherever it can.
+    int two_phase_min_nq = 3000;  // from here on every nn <= 16 takes an accept-list form (8000 x nn 10: 105 us as one launch, 126 as two, 154 fused)
+    int stream_min_nn = 6;        // the list form of nn >= this is the ONE-launch stream form; below, two launches (the replay is short and the plain scan faster than the streaming one: 8000 x nn 2: 73 against 81 us)
+    int stream_min_nq = 1;        // ... and nn >= stream_min_nn takes it from this many queries on: every size (2000 queries: 43 us against 74 fused, 64: 33 against 61)
+    bool stream_when_few = true;  // nn < stream_min_nn takes the stream form too while one query per scan wave fits at three waves per SIMD (~3000 queries): nn 2: 20-34 us against 29-36 fused, nn 5: 24-37 against 42-52 (profiles/r05_knn_nq_sweep.txt)
+    unsigned lds_attr[2] = {0, 0};   // bit k of [0] / [1]: the dynamic-LDS attribute of knn_replay_lane_kernel<k> / knn_replay_shards_lane_kernel<k> has been set on this index's device
     int accept_qpw = 2;           // queries per wave of the accept scan (UH_KNN_ACCEPT_QPW=1 for the A/B)
+    enum ShardForm { kShardAuto, kShardLanes, kShardWaves } shard_form = kShardAuto;   // UH_KNN_SHARD_FORM: unset, "lanes", anything else ("old")
     unsigned stream_tag = 0;      // launch tag of the streamed lists (0 = the value freshly cleared memory holds, never used)
     unsigned stream_tag0 = 0;     // UH_KNN_TAG0: first tag of a fresh buffer (test hook for the wrap)
     uh::DevBuf redo_buf;
@@ -1695,7 +1693,7 @@ struct uh_knn {
     unsigned stream_gen = 0;            // ... and its allocation generation (hipFree + hipMalloc may hand back the same base address)
     uh::DevBuf list_buf;          // accept lists, counts and redo flags of the two-phase search
     uh::DevBuf q_buf, idx_buf, dist_buf;  // staging for the host-pointer API
-    bool split_form = false;              // UH_KNN_FORM=split: the range-split form of small query sets (see uh_knn_search_dev)
+    bool split_form = false;              // UH_KNN_FORM=split: the range-split form of small query sets (see run_split)
     uh::MappedBuf h_word;                 // completion word of a host-pointer search with pinned buffers
     unsigned long long host_seq = 0;
     // hierarchical k-means form of the same index (uh_knn_build_kmeans)
@@ -1714,45 +1712,192 @@ struct uh_knn {
     bool km_attr = false;
 };
 
-// ancestor-walk depth of the lane-distributed heap by nn (see WaveHeap::push_accepted)
-static void launch_replay(uh_knn* idx, dim3 grid, dim3 block, const ShardBounds& sb, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist,
-                          const uint64_t* d_cand, const int32_t* d_counts, int cap, int32_t* d_indices, int32_t* d_distances, int* d_overflow,
-                          size_t cand_stride = 0, size_t count_stride = 0) {
-    if (!cand_stride) cand_stride = (size_t)nq * cap;
-    if (!count_stride) count_stride = (size_t)nq;
-    if (nn <= 3) UH_LAUNCH(idx->ctx, knn_replay_kernel<1>, grid, block, 0, idx->d_train, sb, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_cand, d_counts, cap, d_indices, d_distances, d_overflow, cand_stride, count_stride);
-    else if (nn <= 15) UH_LAUNCH(idx->ctx, knn_replay_kernel<3>, grid, block, 0, idx->d_train, sb, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_cand, d_counts, cap, d_indices, d_distances, d_overflow, cand_stride, count_stride);
-    else UH_LAUNCH(idx->ctx, knn_replay_kernel<6>, grid, block, 0, idx->d_train, sb, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_cand, d_counts, cap, d_indices, d_distances, d_overflow, cand_stride, count_stride);
+// ---- host side of the exact search: one dispatcher per template axis, the launches the forms share, the form decision, the five forms
+namespace {
+// UH_LAUNCH for an instantiation a dispatcher picked.  The profiler scope stays the one UH_LAUNCH gives the written-out launch, the source spelling `head a[, b] tail`:
+// "knn_redo_kernel<3>", "(knn_stream_kernel<10, 2>)".
+struct ScopeName { char s[48]; };
+constexpr ScopeName scope_name(const char* head, int a, int b, const char* tail) {
+    ScopeName r{}; int n = 0;
+    auto number = [&](int v) { if (v >= 10) r.s[n++] = (char)('0' + v / 10); r.s[n++] = (char)('0' + v % 10); };
+    for (; *head; head++) r.s[n++] = *head;
+    number(a); if (b >= 0) { r.s[n++] = ','; r.s[n++] = ' '; number(b); }
+    for (; *tail; tail++) r.s[n++] = *tail;
+    return r;
 }
-
-// tile lists -> rows with one lane per query (k <= 16, rows below 2^23, no rescan); false: the caller uses the wave-per-query replay
-static bool launch_replay_lanes(uh_knn* idx, int nq, int nn, int sorted, int max_dist, const uint64_t* d_cand, size_t cand_stride, const int32_t* d_counts,
-                                size_t count_stride, int nshards, int cap, int32_t* d_indices, int32_t* d_distances, int* d_overflow,
-                                int* d_redo_list = nullptr, int* d_redo_count = nullptr) {
-    // One lane per query steps through EVERY listed row in lockstep over 64 queries, the wave-per-query replay pays per ACCEPTED push: with
-    // one list (world 1: 70 rows listed, 79 accepted overall) the lane form wins (42 vs 51 us for 2000 queries), with the 8 lists of 8 tiles
-    // (425 rows listed per query) it loses (158 vs 52 us; scripts/time_shard_replay.py).  UH_KNN_SHARD_FORM=lanes / old force one for the A/B.
-    const char* form = getenv("UH_KNN_SHARD_FORM");
-    const bool force_lanes = form && std::string(form) == "lanes";
-    if (nn > kRpK || cap > 256 || (form && !force_lanes) || (nshards > 1 && !force_lanes && !d_redo_list)) return false;
-    if (!cand_stride) cand_stride = (size_t)nq * cap;
-    if (!count_stride) count_stride = (size_t)nq;
-    const dim3 grid(uh_div_up(nq, kWave)), block(kWave);
-    const size_t lds = (size_t)cap * kWave * 8;
-#define UH_KNN_RPS(K) case K: { static bool attr##K = false; if (!attr##K) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_replay_shards_lane_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * kWave * 8); attr##K = true; } \
-        UH_LAUNCH(idx->ctx, knn_replay_shards_lane_kernel<K>, grid, block, lds, d_cand, cand_stride, d_counts, count_stride, nshards, nq, sorted ? 1 : 0, max_dist, cap, d_indices, d_distances, d_overflow, d_redo_list, d_redo_count); } break
-    switch (nn) {
-        UH_KNN_RPS(1); UH_KNN_RPS(2); UH_KNN_RPS(3); UH_KNN_RPS(4); UH_KNN_RPS(5); UH_KNN_RPS(6); UH_KNN_RPS(7); UH_KNN_RPS(8);
-        UH_KNN_RPS(9); UH_KNN_RPS(10); UH_KNN_RPS(11); UH_KNN_RPS(12); UH_KNN_RPS(13); UH_KNN_RPS(14); UH_KNN_RPS(15); UH_KNN_RPS(16);
-        default: return false;
-    }
-#undef UH_KNN_RPS
-    return true;
+#define UH_LAUNCH_AS(ctx, head, a, b, tail, kernel, grid, block, shmem, ...)                                                                                      \
+    do { static constexpr ScopeName _sn = scope_name(head, a, b, tail); uh::ProfScope _ps((ctx), _sn.s); hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->stream, __VA_ARGS__); } while (0)
+template <int N> using int_c = std::integral_constant<int, N>;
+// K of the register-heap kernels: f(int_c<nn>) for nn in [1, kRpK], which every caller has established; returns what f returns
+template <typename F, int... I> int with_k(int nn, F&& f, std::integer_sequence<int, I...>) {
+    int rc = UH_EINVAL;
+    (void)((nn == I + 1 && ((rc = f(int_c<I + 1>{})), true)) || ...);
+    return rc;
 }
-
+template <typename F> int with_k(int nn, F&& f) { return with_k(nn, f, std::make_integer_sequence<int, kRpK>{}); }
+// LV of the lane-distributed heap: the ancestor-walk depth by nn (see WaveHeap::push_accepted)
+template <typename F> void with_heap_depth(int nn, F&& f) { if (nn <= 3) f(int_c<1>{}); else if (nn <= 15) f(int_c<3>{}); else f(int_c<6>{}); }
+struct SearchArgs { const uint8_t* d_queries; int nq, nn; int32_t* d_indices; int32_t* d_distances; int sorted, max_dist; };   // what one search call asks for
+const dim3 kBlock(kWave * kWavesPerBlock);
+// the full rescan of the queries whose accept list overflowed, behind a two-launch or split search
+void launch_redo(uh_knn* idx, const SearchArgs& a, const int* d_redo, const int* d_nredo) {
+    with_heap_depth(a.nn, [&](auto lv) { constexpr int LV = decltype(lv)::value;
+        UH_LAUNCH_AS(idx->ctx, "knn_redo_kernel<", LV, -1, ">", knn_redo_kernel<LV>, dim3(64), kBlock, 0, idx->d_train, idx->shard_begin, idx->shard_end, a.d_queries, a.nn, a.sorted ? 1 : 0, a.max_dist, a.d_indices, a.d_distances, d_redo, d_nredo); });
+}
+// shard lists -> rows with one wave per query (any nn; d_overflow NULL: an overflowed list is rescanned over sb); shard s's block begins cand_stride / count_stride ELEMENTS behind shard s-1's
+void launch_replay(uh_knn* idx, const ShardBounds& sb, const SearchArgs& a, const uint64_t* d_cand, size_t cand_stride, const int32_t* d_counts, size_t count_stride, int cap, int* d_overflow) {
+    with_heap_depth(a.nn, [&](auto lv) { constexpr int LV = decltype(lv)::value;
+        UH_LAUNCH_AS(idx->ctx, "knn_replay_kernel<", LV, -1, ">", knn_replay_kernel<LV>, dim3(uh_div_up(a.nq, kWavesPerBlock)), kBlock, 0, idx->d_train, sb, a.d_queries, a.nq, a.nn, a.sorted ? 1 : 0, a.max_dist, d_cand, d_counts, cap, a.d_indices, a.d_distances, d_overflow, cand_stride, count_stride); });
+}
+// the lane replays stage their lists in dynamic LDS: the limit is raised once per index (hence per device) and K, to the largest list area a launch may ask for (256 entries x 64 lanes x 8 bytes); which: row of uh_knn::lds_attr
+int raise_lds_limit(uh_knn* idx, int which, int K, const void* kernel) {
+    if (!(idx->lds_attr[which] & (1u << K))) UH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * kWave * 8));
+    idx->lds_attr[which] |= 1u << K;
+    return UH_OK;
+}
+// Shard lists -> rows with one lane per query (k <= 16, rows below 2^23, no rescan), or with one wave?  One lane per query steps through EVERY listed row in lockstep over 64 queries,
+// the wave-per-query replay pays per ACCEPTED push: with one list (world 1: 70 rows listed, 79 accepted overall) the lane form wins (42 vs 51 us for 2000 queries), with the 8 lists of 8
+// tiles (425 rows listed per query) it loses (158 vs 52 us; scripts/time_shard_replay.py) — the split form, with a redo list, uses it all the same.  UH_KNN_SHARD_FORM=lanes / old force one.
+bool replay_lanes_apply(const uh_knn* idx, int nn, int cap, int nshards, bool has_redo_list) {
+    if (nn > kRpK || cap > 256 || idx->shard_form == uh_knn::kShardWaves) return false;
+    return nshards == 1 || idx->shard_form == uh_knn::kShardLanes || has_redo_list;
+}
+int launch_replay_lanes(uh_knn* idx, const SearchArgs& a, const uint64_t* d_cand, size_t cand_stride, const int32_t* d_counts, size_t count_stride, int nshards, int cap, int* d_overflow, int* d_redo_list, int* d_redo_count) {
+    return with_k(a.nn, [&](auto k) { constexpr int K = decltype(k)::value;
+        const int rc = raise_lds_limit(idx, 1, K, reinterpret_cast<const void*>(knn_replay_shards_lane_kernel<K>));
+        if (!rc) UH_LAUNCH_AS(idx->ctx, "knn_replay_shards_lane_kernel<", K, -1, ">", knn_replay_shards_lane_kernel<K>, dim3(uh_div_up(a.nq, kWave)), dim3(kWave), (size_t)cap * kWave * 8, d_cand, cand_stride, d_counts, count_stride, nshards, a.nq, a.sorted ? 1 : 0, a.max_dist, cap, a.d_indices, a.d_distances, d_overflow, d_redo_list, d_redo_count);
+        return rc; });
+}
 // compute units the context's stream can really use (a CU-masked context reports its share, ADVICE r5: the replay workgroups of the stream
 // form barrier on each other inside the launch and must all be resident — the capacity tests must not assume more CUs than the mask gives)
-static inline int km_cus(const uh_ctx* c) { return c->num_cus > 0 ? c->num_cus : 64; }
+inline int km_cus(const uh_ctx* c) { return c->num_cus > 0 ? c->num_cus : 64; }
+// Accept-list capacity: the expected number of accepted pushes is k (1 + ln(N / k)) (a record process), its spread ~ sqrt of that; lists that still overflow
+// (distances descending with the row index) are redone (knn_redo_kernel, the stream form's own redo).  Two-launch and stream form: 1.6 x + 32, at most the rows ...
+int list_cap(int nrows, int nn) {
+    const double expect = nn * (1.0 + std::log(std::max((double)nrows / nn, 1.0)));
+    return std::min(std::min(std::max(((int)(1.6 * expect) + 32 + 31) & ~31, 32), std::max((nrows + 31) & ~31, 32)), 256);
+}
+// ... split form, per slice of nrows / S rows: expectation + 4 sigma, as the callers of the sharded search size theirs (scripts/time_shard_replay.py)
+int split_cap(int nrows, int S, int nn) {
+    const double rows_s = (double)nrows / S, expect = nn * (1.0 + std::log(std::max(rows_s / nn, 1.0)));
+    return std::min(256, std::max(32, (((int)(expect + 4.0 * std::sqrt(expect)) + 15) & ~15)));
+}
+enum class Form { fused, fused_mq, split, two_launch, stream };
+// cap: accept-list entries per query (and slice), 0 in the fused forms; W: waves per SIMD the stream launch is compiled for (2, 3, 4: one query per scan wave,
+// 5: two); S: slices of the split form; qpw: queries per wave in effect (fused forms)
+struct SearchPlan { Form form; int cap, W, S, qpw; };
+// Which form serves nq queries x nn neighbours on this index: arithmetic only (no HIP call, no allocation).  DESIGN.md §4.2 has the outcome as a table.
+SearchPlan plan_search(const uh_knn* idx, int nq, int nn) {
+    // queries per wave (uh_knn_set_queries_per_wave): 2 or 4 queries share every train row a wave loads — the search itself gets slower (the pushes of a wave's queries
+    // serialise), its L1/L2 traffic and its resident waves drop to 1/2 or 1/4, which is what a latency-bound neighbour on another stream (the local BA) needs
+    SearchPlan p{Form::fused, 0, 5, 1, nn <= 15 ? idx->qpw : 1};
+    const int cus = km_cus(idx->ctx), nrows = idx->shard_end - idx->shard_begin;
+    const bool lists = nn <= kRpK && idx->shard_end <= (1 << 23);   // the list forms: register heaps for k <= 16; the replay packs distance and row index into 32 bits
+    // waves per SIMD a stream launch takes with ONE query per scan wave: its one-wave workgroups (one per 64 queries for the replay, one per query) over the SIMDs.  Up to two it is compiled
+    // for two (~2000 queries on 256 CUs), then for three (~3000; 170 registers) and four (~4000; two row groups in rotation: 128 registers); beyond that two queries share a scan wave, at five
+    const long long occupancy = ((long long)uh_div_up(nq, kWave) + nq + 4 * cus - 1) / (4 * cus);
+    p.W = occupancy <= 2 ? 2 : occupancy <= 4 ? (int)occupancy : 5;
+    // "few queries": one query per scan wave; nn < stream_min_nn only up to three waves per SIMD (at 4000 queries the two launches win: nn 2 51 us against 58)
+    const bool few = idx->stream_when_few && occupancy <= (nn >= idx->stream_min_nn ? 4 : 3);
+    if (lists && (nq >= idx->two_phase_min_nq || (nn >= idx->stream_min_nn && nq >= idx->stream_min_nq) || few)) {
+        p.cap = list_cap(std::max(nrows, 1), nn);
+        // the replay workgroups of the stream form wait for each other at the end (the shared redo, the hand-over to the host): ALL of them must be resident at once — they are the first
+        // workgroups of the grid, and they are kept to at most two per compute unit (32 768 queries on MI355X; a 20th of the one-wave slots); larger batches take the two launches
+        const bool stream_fits = uh_div_up(nq, kWave) <= 2 * cus;
+        const bool stream = stream_fits && (nn >= idx->stream_min_nn || few)
+                            && p.cap >= kWave                                // the vector first step writes a whole step before the list-full test
+                            && idx->accept_qpw == 2                          // UH_KNN_ACCEPT_QPW=1 is the A/B of the accept kernel, which the stream form has not
+                            && (size_t)nq * p.cap * 8 < ((size_t)1 << 31);   // record offsets are 32-bit buffer offsets
+        p.form = stream ? Form::stream : Form::two_launch;
+        return p;
+    }
+    // UH_KNN_FORM=split (see run_split): slices of at least 512 rows, at most 16 and ~8192 scan queries in all; not with several queries per wave, and only where the lane replay applies
+    const int S = std::min(std::min(16, std::max(1, 8192 / std::max(nq, 1))), nrows / 512);
+    if (idx->split_form && lists && S >= 2 && p.qpw == 1) {
+        const SearchPlan split{Form::split, split_cap(nrows, S, nn), p.W, S, 1};
+        if (replay_lanes_apply(idx, nn, split.cap, S, true)) return split;
+    }
+    if (p.qpw > 1) p.form = Form::fused_mq;
+    return p;
+}
+// scan and replay in ONE launch (knn_stream_kernel); ho: where the replay workgroups hand the rows to the host themselves
+int run_stream(uh_knn* idx, const SearchPlan& p, const SearchArgs& a, KnnHostOut ho) {
+    const int nq = a.nq, cap = p.cap; int rc;
+    if ((rc = idx->list_buf.reserve((size_t)nq * cap * 8 + (size_t)nq * 16 + 256))) return rc;
+    uint64_t* d_cand = idx->list_buf.as<uint64_t>();
+    uint64_t* d_prog = d_cand + (size_t)nq * cap;          // (list_buf holds tagged words only: any layout of an earlier launch is harmless)
+    const unsigned had = idx->redo_buf.gen;
+    if ((rc = idx->redo_buf.reserve((size_t)(nq + 8) * 4))) return rc;
+    int* d_nredo = idx->redo_buf.as<int>();                // [parity]: queries to redo, [2 / 4 / 6 + parity]: replay workgroups through their lists / redo share / host copy; then the compacted list of the queries to redo
+    int* d_redo = d_nredo + 8;
+    if (had != idx->redo_buf.gen) UH_HIP_CHECK(hipMemsetAsync(d_nredo, 0, 32, idx->ctx->stream));
+    const bool same_mem = idx->stream_buf == idx->list_buf.p && idx->stream_gen == idx->list_buf.gen;
+    if (!same_mem || idx->stream_tag == 0xFFFFFFFFu) {   // new memory, or the tag wraps: no stale word may match
+        UH_HIP_CHECK(hipMemsetAsync(idx->list_buf.p, 0, idx->list_buf.cap, idx->ctx->stream));
+        idx->stream_tag = same_mem ? 0 : idx->stream_tag0;
+        idx->stream_buf = idx->list_buf.p;
+        idx->stream_gen = idx->list_buf.gen;
+        // the overflow counters are picked by tag parity and a launch clears only the NEXT launch's slot: after a tag reset the slot of the coming launch may still
+        // hold the count an earlier launch of the same parity left behind (stale query ids would be replayed by knn_redo_kernel) — clear both
+        UH_HIP_CHECK(hipMemsetAsync(d_nredo, 0, 32, idx->ctx->stream));
+    }
+    const unsigned tag = ++idx->stream_tag;
+    static const long long stream_timeout = [] { const char* e = getenv("UH_KNN_STREAM_TIMEOUT_MS"); const long long ms = e ? atoll(e) : 0; return ms > 0 ? ms * 100000ll : kStreamTimeoutDefault; }();
+    const int nrep = uh_div_up(nq, kWave);
+    const dim3 grid(nrep + (p.W < 5 ? nq : uh_div_up(nq, 2)));   // the replay workgroups, then the scan waves: of one query each (W < 5) or of two
+    auto launch = [&](auto k, auto w) { constexpr int K = decltype(k)::value, W = decltype(w)::value;
+        UH_LAUNCH_AS(idx->ctx, "(knn_stream_kernel<", K, W, ">)", (knn_stream_kernel<K, W>), grid, dim3(kWave), 0, idx->d_train, idx->shard_begin, idx->shard_end, a.d_queries, nq, a.sorted ? 1 : 0, a.max_dist,
+                     d_cand, d_prog, cap, tag, nrep, a.d_indices, a.d_distances, d_redo, d_nredo + (tag & 1u), d_nredo + ((tag + 1u) & 1u), stream_timeout, ho);
+        return (int)UH_OK; };
+    return with_k(a.nn, [&](auto k) { return p.W == 2 ? launch(k, int_c<2>{}) : p.W == 3 ? launch(k, int_c<3>{}) : p.W == 4 ? launch(k, int_c<4>{}) : launch(k, int_c<5>{}); });
+}
+// accept-list scan, then the lane replay on register heaps, then the redo of the overflowed lists
+int run_two_launch(uh_knn* idx, const SearchPlan& p, const SearchArgs& a) {
+    const int nq = a.nq, cap = p.cap; int rc;
+    if ((rc = idx->list_buf.reserve((size_t)nq * cap * 8 + (size_t)nq * 16 + 256))) return rc;
+    idx->stream_buf = nullptr;   // (untagged words go into the buffer the stream form keeps its tagged ones in)
+    uint64_t* d_cand = idx->list_buf.as<uint64_t>();
+    int32_t* d_counts = reinterpret_cast<int32_t*>(d_cand + (size_t)nq * cap);
+    int* d_redo = d_counts + nq;       // [nq] compacted list of overflowed queries, [nq] their number
+    int* d_nredo = d_redo + nq;
+    auto accept = [&](auto q) { constexpr int Q = decltype(q)::value;   // queries per wave of the accept scan (default 2: one is L1-bandwidth bound)
+        UH_LAUNCH_AS(idx->ctx, "knn_accept_kernel<", Q, -1, ">", knn_accept_kernel<Q>, dim3(uh_div_up(nq, kWavesPerBlock * Q)), kBlock, 0, idx->d_train, idx->shard_begin, idx->shard_end, a.d_queries, nq, a.nn, a.max_dist, d_cand, d_counts, cap, d_nredo); };
+    if (idx->accept_qpw == 1) accept(int_c<1>{}); else accept(int_c<2>{});
+    rc = with_k(a.nn, [&](auto k) { constexpr int K = decltype(k)::value;
+        const int e = raise_lds_limit(idx, 0, K, reinterpret_cast<const void*>(&knn_replay_lane_kernel<K>));
+        if (!e) UH_LAUNCH_AS(idx->ctx, "knn_replay_lane_kernel<", K, -1, ">", knn_replay_lane_kernel<K>, dim3(uh_div_up(nq, kWave)), dim3(kWave), (size_t)cap * kWave * 8 /* cap <= 256: at most 128 KB */, d_cand, d_counts, nq, a.sorted ? 1 : 0, a.max_dist, cap, a.d_indices, a.d_distances, d_redo, d_nredo);
+        return e; });
+    if (!rc) launch_redo(idx, a, d_redo, d_nredo);
+    return rc;
+}
+// UH_KNN_FORM=split (measured and NOT chosen): for ONE frame's queries the range is cut into S slices scanned by S times as many waves (the threshold-only scan of the sharded
+// search, exact lists per slice) and a lane-per-query replay walks the slices' lists in row order.  The scan gets S times shorter, but every slice starts from an empty heap and lists
+// 65 rows where the global heap accepts 79 in all: the replay wades through 260 entries per query in lockstep over 64 queries — 2000 x 10 000, nn 10: 144 us against 77 fused / 73 as
+// one stream-form launch.  Kept as the single-GPU rehearsal of the sharded search (same kernels).
+int run_split(uh_knn* idx, const SearchPlan& p, const SearchArgs& a) {
+    const int nq = a.nq, cap = p.cap, S = p.S; int rc;
+    if ((rc = idx->list_buf.reserve((size_t)S * nq * cap * 8 + (size_t)S * nq * 4 + (size_t)(nq + 2) * 4 + 256))) return rc;
+    idx->stream_buf = nullptr;   // (untagged words go into the buffer the stream form keeps its tagged ones in)
+    uint64_t* d_cand = idx->list_buf.as<uint64_t>();
+    int32_t* d_counts = reinterpret_cast<int32_t*>(d_cand + (size_t)S * nq * cap);
+    int* d_redo = d_counts + (size_t)S * nq;
+    int* d_nredo = d_redo + nq;
+    UH_LAUNCH(idx->ctx, knn_scan_shard2_kernel, dim3(uh_div_up(uh_div_up(nq, 2), kWavesPerBlock), S), kBlock, 0, idx->d_train, idx->shard_begin, idx->shard_end, a.d_queries, nq, a.nn, a.max_dist, d_cand, d_counts, cap, d_nredo, static_cast<const int32_t*>(nullptr));
+    if ((rc = launch_replay_lanes(idx, a, d_cand, (size_t)nq * cap, d_counts, (size_t)nq, S, cap, nullptr, d_redo, d_nredo))) return rc;
+    launch_redo(idx, a, d_redo, d_nredo);
+    return UH_OK;
+}
+// the fused scan + lane-distributed heap: one wave per query (any nn), or per p.qpw queries (nn <= 15: heap depths 1 and 3 only, <6, Q> would be an instantiation nobody launches)
+void run_fused(uh_knn* idx, const SearchPlan& p, const SearchArgs& a) {
+    const dim3 grid(uh_div_up(a.nq, kWavesPerBlock * p.qpw));
+    auto mq = [&](auto lv, auto q) { constexpr int LV = decltype(lv)::value, Q = decltype(q)::value;
+        UH_LAUNCH_AS(idx->ctx, "(knn_search_mq_kernel<", LV, Q, ">)", (knn_search_mq_kernel<LV, Q>), grid, kBlock, 0, idx->d_train, idx->shard_begin, idx->shard_end, a.d_queries, a.nq, a.nn, a.sorted ? 1 : 0, a.max_dist, a.d_indices, a.d_distances); };
+    if (p.form == Form::fused_mq && a.nn <= 3) { if (p.qpw == 2) mq(int_c<1>{}, int_c<2>{}); else mq(int_c<1>{}, int_c<4>{}); }
+    else if (p.form == Form::fused_mq) { if (p.qpw == 2) mq(int_c<3>{}, int_c<2>{}); else mq(int_c<3>{}, int_c<4>{}); }
+    else with_heap_depth(a.nn, [&](auto lv) { constexpr int LV = decltype(lv)::value;
+        UH_LAUNCH_AS(idx->ctx, "knn_search_kernel<", LV, -1, ">", knn_search_kernel<LV>, grid, kBlock, 0, idx->d_train, idx->shard_begin, idx->shard_end, a.d_queries, a.nq, a.nn, a.sorted ? 1 : 0, a.max_dist, a.d_indices, a.d_distances); });
+}
+}  // namespace
 
 extern "C" {
 
@@ -1768,6 +1913,7 @@ int uh_knn_create(uh_ctx* ctx, uh_knn** out) {
         else if (f == "stream") { k->two_phase_min_nq = 0; k->stream_min_nn = 0; }
     }
     if (const char* f = getenv("UH_KNN_ACCEPT_QPW")) k->accept_qpw = atoi(f) == 1 ? 1 : 2;
+    if (const char* f = getenv("UH_KNN_SHARD_FORM")) k->shard_form = std::string(f) == "lanes" ? uh_knn::kShardLanes : uh_knn::kShardWaves;
     if (const char* f = getenv("UH_KNN_TAG0")) k->stream_tag0 = (unsigned)strtoul(f, nullptr, 0);
     *out = k;
     return UH_OK;
@@ -1856,136 +2002,15 @@ static int knn_search_dev_impl(uh_knn* idx, const uint8_t* d_queries, int nq, in
     if (rc) return rc;
     if (nq == 0) return UH_OK;
     UH_HIP_CHECK(hipSetDevice(idx->ctx->device));
-    dim3 grid(uh_div_up(nq, kWavesPerBlock)), block(kWave * kWavesPerBlock);
-    // queries per wave (uh_knn_set_queries_per_wave): 2 or 4 queries share every train row a wave loads — the search itself gets
-    // slower (the pushes of a wave's queries serialise), its L1/L2 traffic and its resident waves drop to 1/2 or 1/4, which is what a
-    // latency-bound neighbour on another stream (the local BA) needs
-    const int qpw = nn <= 15 ? idx->qpw : 1;
-    const bool few_form = uh_div_up(nq, kWave) + nq <= 2 * 4 * km_cus(idx->ctx);
-    // one query per scan wave at up to four waves per SIMD (~4000 queries); nn <= 5: up to three (at 4000 queries the two launches win: nn 2 51 us against 58)
-    const bool few_any = uh_div_up(nq, kWave) + nq <= (nn >= idx->stream_min_nn ? 4 : 3) * 4 * km_cus(idx->ctx);   // at most two one-wave workgroups per SIMD with ONE query per scan wave (knn_stream_kernel<K, 2>)
-    if (nn <= kRpK && (nq >= idx->two_phase_min_nq || (nn >= idx->stream_min_nn && nq >= idx->stream_min_nq) || (few_any && idx->stream_when_few)) && idx->shard_end <= (1 << 23)) {   // (the replay packs distance and row index into 32 bits)
-        // accept-list capacity: the expected number of accepted pushes is k (1 + ln(N / k)) (a record process), its spread ~ sqrt of
-        // that; lists that still overflow (distances descending with the row index) are redone by knn_redo_kernel
-        const int nrows = std::max(idx->shard_end - idx->shard_begin, 1);
-        const double expect = nn * (1.0 + std::log(std::max((double)nrows / nn, 1.0)));
-        const int cap = std::min(std::min(std::max(((int)(1.6 * expect) + 32 + 31) & ~31, 32), std::max((nrows + 31) & ~31, 32)), 256);
-        int rc;
-        if ((rc = idx->list_buf.reserve((size_t)nq * cap * 8 + (size_t)nq * 16 + 256))) return rc;
-        // the replay workgroups of the stream form wait for each other at the end (the shared redo, the hand-over to the host): ALL of them must be
-        // resident at once — they are the first workgroups of the grid, and they are kept to at most two per compute unit (32 768 queries on
-        // MI355X; a 20th of the one-wave slots); larger batches take the two launches
-        const bool stream_fits = uh_div_up(nq, kWave) <= 2 * km_cus(idx->ctx);
-        if (stream_fits && cap >= kWave /* (the vector first step writes a whole step before the list-full test: ADVICE r5) */ && (nn >= idx->stream_min_nn || (few_any && idx->stream_when_few)) && idx->accept_qpw == 2 && (size_t)nq * cap * 8 < ((size_t)1 << 31)) {   // (record offsets are 32-bit buffer offsets)
-            uint64_t* d_cand = idx->list_buf.as<uint64_t>();
-            uint64_t* d_prog = d_cand + (size_t)nq * cap;          // (list_buf holds tagged words only: any layout of an earlier launch is harmless)
-            const unsigned had = idx->redo_buf.gen;
-            if ((rc = idx->redo_buf.reserve((size_t)(nq + 8) * 4))) return rc;
-            int* d_nredo = idx->redo_buf.as<int>();                // [parity]: queries to redo, [2 / 4 / 6 + parity]: replay workgroups through their lists / redo share / host copy; then the compacted list of the queries to redo
-            int* d_redo = d_nredo + 8;
-            if (had != idx->redo_buf.gen) UH_HIP_CHECK(hipMemsetAsync(d_nredo, 0, 32, idx->ctx->stream));
-            const bool same_mem = idx->stream_buf == idx->list_buf.p && idx->stream_gen == idx->list_buf.gen;
-            if (!same_mem || idx->stream_tag == 0xFFFFFFFFu) {   // new memory, or the tag wraps: no stale word may match
-                UH_HIP_CHECK(hipMemsetAsync(idx->list_buf.p, 0, idx->list_buf.cap, idx->ctx->stream));
-                idx->stream_tag = same_mem ? 0 : idx->stream_tag0;
-                idx->stream_buf = idx->list_buf.p;
-                idx->stream_gen = idx->list_buf.gen;
-                // the overflow counters are picked by tag parity and a launch clears only the NEXT launch's slot: after a tag reset the slot
-                // of the coming launch may still hold the count an earlier launch of the same parity left behind (stale query ids would
-                // be replayed by knn_redo_kernel) — clear both
-                UH_HIP_CHECK(hipMemsetAsync(d_nredo, 0, 32, idx->ctx->stream));
-            }
-            const unsigned tag = ++idx->stream_tag;
-            static const long long stream_timeout = [] { const char* e = getenv("UH_KNN_STREAM_TIMEOUT_MS"); const long long ms = e ? atoll(e) : 0; return ms > 0 ? ms * 100000ll : kStreamTimeoutDefault; }();
-            const int nrep = uh_div_up(nq, kWave);
-            const bool few = few_form;
-            const bool few3 = !few && nrep + nq <= 3 * 4 * km_cus(idx->ctx);   // one query per scan wave at three waves per SIMD (2000 < queries <= ~3000; 170 registers)
-            const bool few4 = !few && !few3 && nrep + nq <= 4 * 4 * km_cus(idx->ctx);   // ... at four (two row groups in rotation: 128 registers)
-            const dim3 gs(nrep + (few || few3 || few4 ? nq : uh_div_up(nq, 2)));
-#define UH_KNN_STREAM_W(K, W) UH_LAUNCH(idx->ctx, (knn_stream_kernel<K, W>), gs, dim3(kWave), 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, sorted ? 1 : 0, max_dist, \
-            d_cand, d_prog, cap, tag, nrep, d_indices, d_distances, d_redo, d_nredo + (tag & 1u), d_nredo + ((tag + 1u) & 1u), stream_timeout, ho)
-#define UH_KNN_STREAM(K) case K: if (few) UH_KNN_STREAM_W(K, 2); else if (few3) UH_KNN_STREAM_W(K, 3); else if (few4) UH_KNN_STREAM_W(K, 4); else UH_KNN_STREAM_W(K, 5); break
-            switch (nn) {
-                UH_KNN_STREAM(1); UH_KNN_STREAM(2); UH_KNN_STREAM(3); UH_KNN_STREAM(4); UH_KNN_STREAM(5); UH_KNN_STREAM(6); UH_KNN_STREAM(7); UH_KNN_STREAM(8);
-                UH_KNN_STREAM(9); UH_KNN_STREAM(10); UH_KNN_STREAM(11); UH_KNN_STREAM(12); UH_KNN_STREAM(13); UH_KNN_STREAM(14); UH_KNN_STREAM(15); UH_KNN_STREAM(16);
-                default: break;
-            }
-#undef UH_KNN_STREAM
-#undef UH_KNN_STREAM_W
-            UH_HIP_CHECK(hipGetLastError());
-            if (handed) *handed = ho.host_done != nullptr;
-            return UH_OK;
-        }
-        idx->stream_buf = nullptr;   // (the two-launch form writes untagged words into the same buffer)
-        uint64_t* d_cand = idx->list_buf.as<uint64_t>();
-        int32_t* d_counts = reinterpret_cast<int32_t*>(d_cand + (size_t)nq * cap);
-        int* d_redo = d_counts + nq;       // [nq] compacted list of overflowed queries, [nq] their number
-        int* d_nredo = d_redo + nq;
-        const int aq = idx->accept_qpw;   // queries per wave of the accept scan (default 2: one is L1-bandwidth bound)
-        const dim3 ga(uh_div_up(nq, kWavesPerBlock * aq));
-#define UH_KNN_ACCEPT(Q) UH_LAUNCH(idx->ctx, knn_accept_kernel<Q>, ga, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, nn, max_dist, d_cand, d_counts, cap, d_nredo)
-        if (aq == 1) UH_KNN_ACCEPT(1); else UH_KNN_ACCEPT(2);
-#undef UH_KNN_ACCEPT
-        const dim3 gr(uh_div_up(nq, kWave));
-        const size_t lds_lists = (size_t)cap * kWave * 8;   // cap <= 256: at most 128 KB
-        // (the attribute is raised once per k to the largest list area the replay may ask for: 256 entries x 64 lanes x 8 bytes)
-#define UH_KNN_REPLAY(K) case K: if (!(idx->replay_attr & (1u << K))) { UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_replay_lane_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * kWave * 8)); idx->replay_attr |= 1u << K; } \
-        UH_LAUNCH(idx->ctx, knn_replay_lane_kernel<K>, gr, dim3(kWave), lds_lists, d_cand, d_counts, nq, sorted ? 1 : 0, max_dist, cap, d_indices, d_distances, d_redo, d_nredo); break
-        switch (nn) {
-            UH_KNN_REPLAY(1); UH_KNN_REPLAY(2); UH_KNN_REPLAY(3); UH_KNN_REPLAY(4); UH_KNN_REPLAY(5); UH_KNN_REPLAY(6); UH_KNN_REPLAY(7); UH_KNN_REPLAY(8);
-            UH_KNN_REPLAY(9); UH_KNN_REPLAY(10); UH_KNN_REPLAY(11); UH_KNN_REPLAY(12); UH_KNN_REPLAY(13); UH_KNN_REPLAY(14); UH_KNN_REPLAY(15); UH_KNN_REPLAY(16);
-            default: break;
-        }
-#undef UH_KNN_REPLAY
-        const dim3 gd(64);
-        if (nn <= 3) UH_LAUNCH(idx->ctx, knn_redo_kernel<1>, gd, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances, (const int*)d_redo, (const int*)d_nredo);
-        else if (nn <= 15) UH_LAUNCH(idx->ctx, knn_redo_kernel<3>, gd, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances, (const int*)d_redo, (const int*)d_nredo);
-        else UH_LAUNCH(idx->ctx, knn_redo_kernel<6>, gd, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances, (const int*)d_redo, (const int*)d_nredo);
-        UH_HIP_CHECK(hipGetLastError());
-        return UH_OK;
+    const SearchArgs a{d_queries, nq, nn, d_indices, d_distances, sorted, max_dist};
+    const SearchPlan plan = plan_search(idx, nq, nn);
+    switch (plan.form) {
+        case Form::stream: rc = run_stream(idx, plan, a, ho); if (!rc && handed) *handed = ho.host_done != nullptr; break;
+        case Form::two_launch: rc = run_two_launch(idx, plan, a); break;
+        case Form::split: rc = run_split(idx, plan, a); break;
+        case Form::fused: case Form::fused_mq: run_fused(idx, plan, a); break;
     }
-    // ---- UH_KNN_FORM=split (measured and NOT chosen): for ONE frame's queries the range is cut into S slices scanned by S times as many
-    // waves (the threshold-only scan of the sharded search, exact lists per slice) and a lane-per-query replay walks the slices' lists in
-    // row order.  The scan gets S times shorter, but every slice starts from an empty heap and lists 65 rows where the global heap accepts
-    // 79 in all: the replay wades through 260 entries per query in lockstep over 64 queries — 2000 x 10 000, nn 10: 144 us against 77
-    // fused / 73 as one stream-form launch.  Kept as the single-GPU rehearsal of the sharded search (same kernels).
-    {
-        const int nrows = idx->shard_end - idx->shard_begin;
-        const bool no_split = !idx->split_form;
-        int S = std::min(16, std::max(1, 8192 / std::max(nq, 1)));
-        S = std::min(S, nrows / 512);
-        if (!no_split && nn <= kRpK && S >= 2 && idx->shard_end <= (1 << 23) && qpw == 1) {
-            const double rows_s = (double)nrows / S, expect = nn * (1.0 + std::log(std::max(rows_s / nn, 1.0)));
-            const int cap = std::min(256, std::max(32, (((int)(expect + 4.0 * std::sqrt(expect)) + 15) & ~15)));
-            int rc;
-            if ((rc = idx->list_buf.reserve((size_t)S * nq * cap * 8 + (size_t)S * nq * 4 + (size_t)(nq + 2) * 4 + 256))) return rc;
-            idx->stream_buf = nullptr;   // (untagged words go into the buffer the stream form keeps its tagged ones in)
-            uint64_t* d_cand = idx->list_buf.as<uint64_t>();
-            int32_t* d_counts = reinterpret_cast<int32_t*>(d_cand + (size_t)S * nq * cap);
-            int* d_redo = d_counts + (size_t)S * nq;
-            int* d_nredo = d_redo + nq;
-            const dim3 gs(uh_div_up(uh_div_up(nq, 2), kWavesPerBlock), S);
-            UH_LAUNCH(idx->ctx, knn_scan_shard2_kernel, gs, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, nn, max_dist, d_cand, d_counts, cap, d_nredo, static_cast<const int32_t*>(nullptr));
-            if (launch_replay_lanes(idx, nq, nn, sorted, max_dist, d_cand, 0, d_counts, 0, S, cap, d_indices, d_distances, nullptr, d_redo, d_nredo)) {
-                const dim3 gd(64);
-                if (nn <= 3) UH_LAUNCH(idx->ctx, knn_redo_kernel<1>, gd, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances, (const int*)d_redo, (const int*)d_nredo);
-                else if (nn <= 15) UH_LAUNCH(idx->ctx, knn_redo_kernel<3>, gd, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances, (const int*)d_redo, (const int*)d_nredo);
-                else UH_LAUNCH(idx->ctx, knn_redo_kernel<6>, gd, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances, (const int*)d_redo, (const int*)d_nredo);
-                UH_HIP_CHECK(hipGetLastError());
-                return UH_OK;
-            }
-        }
-    }
-    if (qpw > 1) {
-        const dim3 gq(uh_div_up(nq, kWavesPerBlock * qpw));
-#define UH_KNN_MQ(LV, Q) UH_LAUNCH(idx->ctx, (knn_search_mq_kernel<LV, Q>), gq, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances)
-        if (nn <= 3) { if (qpw == 2) UH_KNN_MQ(1, 2); else UH_KNN_MQ(1, 4); }
-        else { if (qpw == 2) UH_KNN_MQ(3, 2); else UH_KNN_MQ(3, 4); }
-#undef UH_KNN_MQ
-    } else
-    if (nn <= 3) UH_LAUNCH(idx->ctx, knn_search_kernel<1>, grid, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances);
-    else if (nn <= 15) UH_LAUNCH(idx->ctx, knn_search_kernel<3>, grid, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances);
-    else UH_LAUNCH(idx->ctx, knn_search_kernel<6>, grid, block, 0, idx->d_train, idx->shard_begin, idx->shard_end, d_queries, nq, nn, sorted ? 1 : 0, max_dist, d_indices, d_distances);
+    if (rc) return rc;
     UH_HIP_CHECK(hipGetLastError());
     return UH_OK;
 }
@@ -2053,7 +2078,7 @@ int uh_knn_scan_shard_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn,
     dim3 grid(uh_div_up(nq, kWavesPerBlock)), block(kWave * kWavesPerBlock);
     // rows [shard_begin, shard_end) of this index carry the global indices row_offset + row: the kernel indexes a virtual base that
     // lies row_offset rows in front of the tile (only rows inside the tile are ever addressed)
-    if (nn <= kRpK && (long long)idx->row_offset + idx->shard_end <= (1 << 23) && !getenv("UH_KNN_SHARD_FORM")) {   // the threshold-only scan, two queries per wave
+    if (nn <= kRpK && (long long)idx->row_offset + idx->shard_end <= (1 << 23) && idx->shard_form == uh_knn::kShardAuto) {   // the threshold-only scan, two queries per wave
         const dim3 g2(uh_div_up(uh_div_up(nq, 2), kWavesPerBlock));
         UH_LAUNCH(idx->ctx, knn_scan_shard2_kernel, g2, block, 0, idx->d_train - (size_t)idx->row_offset * 32, idx->row_offset + idx->shard_begin,
                   idx->row_offset + idx->shard_end, d_queries, nq, nn, max_dist, d_cand, d_counts, cap, static_cast<int*>(nullptr), idx->d_valid_rows);
@@ -2076,65 +2101,40 @@ int uh_knn_set_valid_rows_dev(uh_knn* idx, const int32_t* d_valid_rows) {
     return UH_OK;
 }
 
-int uh_knn_replay_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist,
-                      const uint64_t* d_cand_all, const int32_t* d_counts_all, int nshards, int cap,
+// The three replay entries.  tiles: the caller holds only its own tile of the train set — no rescan, *d_overflow is OR-ed with 1 if some list overflowed, and one lane per query where that
+// form applies (replay_lanes_apply); else one wave per query, an overflowed list rescanned.  Strides as launch_replay's.
+static int replay_lists(const char* who, uh_knn* idx, const SearchArgs& a, const uint64_t* d_cand_all, size_t cand_stride, const int32_t* d_counts_all, size_t count_stride, int nshards, int cap, int32_t* d_overflow, bool tiles) {
+    int rc = check_search_args(idx, a.d_queries, a.nq, a.nn, a.d_indices, a.d_distances);
+    if (rc) return rc;
+    UH_REQUIRE(nshards >= 1 && nshards <= kMaxShards, "%s: nshards=%d outside [1,%d]", who, nshards, kMaxShards);
+    UH_REQUIRE(cap >= 1 && d_cand_all && d_counts_all && (d_overflow || !tiles), "%s: bad candidate buffers", who);
+    UH_REQUIRE(nshards == 1 || (cand_stride >= (size_t)a.nq * cap && count_stride >= (size_t)a.nq), "%s: strides shorter than a shard's block", who);
+    if (a.nq == 0) return UH_OK;
+    ShardBounds sb{nshards, {}};   // shard s covers rows [s*nt/n, (s+1)*nt/n): the same split every rank uses (see parallel.py); never used, and left 0, where there is no rescan
+    for (int s = 0; s <= nshards && !tiles; ++s) sb.b[s] = (int)((long long)idx->nt * s / nshards);
+    UH_HIP_CHECK(hipSetDevice(idx->ctx->device));
+    if (tiles && replay_lanes_apply(idx, a.nn, cap, nshards, false)) {
+        if ((rc = launch_replay_lanes(idx, a, d_cand_all, cand_stride, d_counts_all, count_stride, nshards, cap, (int*)d_overflow, nullptr, nullptr))) return rc;
+    } else launch_replay(idx, sb, a, d_cand_all, cand_stride, d_counts_all, count_stride, cap, (int*)d_overflow);
+    UH_HIP_CHECK(hipGetLastError());
+    return UH_OK;
+}
+
+int uh_knn_replay_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist, const uint64_t* d_cand_all, const int32_t* d_counts_all, int nshards, int cap,
                       int32_t* d_indices, int32_t* d_distances) {
-    int rc = check_search_args(idx, d_queries, nq, nn, d_indices, d_distances);
-    if (rc) return rc;
-    UH_REQUIRE(nshards >= 1 && nshards <= kMaxShards, "uh_knn_replay_dev: nshards=%d outside [1,%d]", nshards, kMaxShards);
-    UH_REQUIRE(cap >= 1 && d_cand_all && d_counts_all, "uh_knn_replay_dev: bad candidate buffers");
-    if (nq == 0) return UH_OK;
-    // shard s covers rows [s*nt/n, (s+1)*nt/n): the same split every rank uses (see parallel.py)
-    ShardBounds sb;
-    sb.n = nshards;
-    for (int s = 0; s <= nshards; ++s) sb.b[s] = (int)((long long)idx->nt * s / nshards);
-    UH_HIP_CHECK(hipSetDevice(idx->ctx->device));
-    dim3 grid(uh_div_up(nq, kWavesPerBlock)), block(kWave * kWavesPerBlock);
-    launch_replay(idx, grid, block, sb, d_queries, nq, nn, sorted, max_dist, d_cand_all, d_counts_all, cap, d_indices, d_distances, nullptr);
-    UH_HIP_CHECK(hipGetLastError());
-    return UH_OK;
+    return replay_lists("uh_knn_replay_dev", idx, SearchArgs{d_queries, nq, nn, d_indices, d_distances, sorted, max_dist}, d_cand_all, (size_t)nq * cap, d_counts_all, (size_t)nq, nshards, cap, nullptr, false);
 }
 
-// replay for ranks that hold only their own tile of the train set: no rescan; *d_overflow is OR-ed with 1 if some list overflowed
-int uh_knn_replay_tiles_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist,
-                            const uint64_t* d_cand_all, const int32_t* d_counts_all, int nshards, int cap,
+// replay for ranks that hold only their own tile of the train set, the gathered lists back to back
+int uh_knn_replay_tiles_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist, const uint64_t* d_cand_all, const int32_t* d_counts_all, int nshards, int cap,
                             int32_t* d_indices, int32_t* d_distances, int32_t* d_overflow) {
-    int rc = check_search_args(idx, d_queries, nq, nn, d_indices, d_distances);
-    if (rc) return rc;
-    UH_REQUIRE(nshards >= 1 && nshards <= kMaxShards, "uh_knn_replay_tiles_dev: nshards=%d outside [1,%d]", nshards, kMaxShards);
-    UH_REQUIRE(cap >= 1 && d_cand_all && d_counts_all && d_overflow, "uh_knn_replay_tiles_dev: bad candidate buffers");
-    if (nq == 0) return UH_OK;
-    ShardBounds sb;
-    sb.n = nshards;
-    for (int s = 0; s <= nshards; ++s) sb.b[s] = 0;   // never used: there is no rescan in this form
-    UH_HIP_CHECK(hipSetDevice(idx->ctx->device));
-    dim3 grid(uh_div_up(nq, kWavesPerBlock)), block(kWave * kWavesPerBlock);
-    if (!launch_replay_lanes(idx, nq, nn, sorted, max_dist, d_cand_all, 0, d_counts_all, 0, nshards, cap, d_indices, d_distances, (int*)d_overflow))
-        launch_replay(idx, grid, block, sb, d_queries, nq, nn, sorted, max_dist, d_cand_all, d_counts_all, cap, d_indices, d_distances, (int*)d_overflow);
-    UH_HIP_CHECK(hipGetLastError());
-    return UH_OK;
+    return replay_lists("uh_knn_replay_tiles_dev", idx, SearchArgs{d_queries, nq, nn, d_indices, d_distances, sorted, max_dist}, d_cand_all, (size_t)nq * cap, d_counts_all, (size_t)nq, nshards, cap, d_overflow, true);
 }
 
-// the same replay on lists that still sit inside the gathered messages: shard s's block begins cand_stride / count_stride ELEMENTS behind shard
-// s-1's (the sharded frame stream, csrc/fstream.hip: nothing is unpacked before the replay)
-int uh_knn_replay_tiles_strided_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist,
-                                    const uint64_t* d_cand_all, size_t cand_stride, const int32_t* d_counts_all, size_t count_stride, int nshards, int cap,
-                                    int32_t* d_indices, int32_t* d_distances, int32_t* d_overflow) {
-    int rc = check_search_args(idx, d_queries, nq, nn, d_indices, d_distances);
-    if (rc) return rc;
-    UH_REQUIRE(nshards >= 1 && nshards <= kMaxShards, "uh_knn_replay_tiles_strided_dev: nshards=%d outside [1,%d]", nshards, kMaxShards);
-    UH_REQUIRE(cap >= 1 && d_cand_all && d_counts_all && d_overflow, "uh_knn_replay_tiles_strided_dev: bad candidate buffers");
-    UH_REQUIRE(nshards == 1 || (cand_stride >= (size_t)nq * cap && count_stride >= (size_t)nq), "uh_knn_replay_tiles_strided_dev: strides shorter than a shard's block");
-    if (nq == 0) return UH_OK;
-    ShardBounds sb;
-    sb.n = nshards;
-    for (int s = 0; s <= nshards; ++s) sb.b[s] = 0;
-    UH_HIP_CHECK(hipSetDevice(idx->ctx->device));
-    dim3 grid(uh_div_up(nq, kWavesPerBlock)), block(kWave * kWavesPerBlock);
-    if (!launch_replay_lanes(idx, nq, nn, sorted, max_dist, d_cand_all, cand_stride, d_counts_all, count_stride, nshards, cap, d_indices, d_distances, (int*)d_overflow))
-        launch_replay(idx, grid, block, sb, d_queries, nq, nn, sorted, max_dist, d_cand_all, d_counts_all, cap, d_indices, d_distances, (int*)d_overflow, cand_stride, count_stride);
-    UH_HIP_CHECK(hipGetLastError());
-    return UH_OK;
+// the same replay on lists that still sit inside the gathered messages (the sharded frame stream, csrc/fstream.hip: nothing is unpacked before the replay)
+int uh_knn_replay_tiles_strided_dev(uh_knn* idx, const uint8_t* d_queries, int nq, int nn, int sorted, int max_dist, const uint64_t* d_cand_all, size_t cand_stride,
+                                    const int32_t* d_counts_all, size_t count_stride, int nshards, int cap, int32_t* d_indices, int32_t* d_distances, int32_t* d_overflow) {
+    return replay_lists("uh_knn_replay_tiles_strided_dev", idx, SearchArgs{d_queries, nq, nn, d_indices, d_distances, sorted, max_dist}, d_cand_all, cand_stride, d_counts_all, count_stride, nshards, cap, d_overflow, true);
 }
 
 int uh_knn_set_row_offset(uh_knn* idx, int offset) {
