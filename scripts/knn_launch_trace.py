@@ -81,14 +81,14 @@ def run():
                     case("shards form=%s world=%d nn=%d cap=%d" % (form or "unset", world, nn, cap), shard_case)
 
 
-def launches(path):
-    """One line per knn_* dispatch of a rocprofv3 kernel trace, in dispatch order."""
+def launches(path, prefix="knn_"):
+    """One line per dispatch of a rocprofv3 kernel trace whose kernel name begins with `prefix`, in dispatch order."""
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
     def dims(r, what):
         return "x".join(r[k] for k in (what + "_X", what + "_Y", what + "_Z")) if what + "_X" in r else r[what]
     out = []
     for r in rows:
-        m = re.search(r"knn_\w+(<[^>]*>)?", r["Kernel_Name"])
+        m = re.search(prefix + r"\w+(<[^>]*>)?", r["Kernel_Name"])
         if m:
             out.append("%s grid %s block %s lds %s" % (m.group(0), dims(r, "Grid_Size"), dims(r, "Workgroup_Size"), r["LDS_Block_Size"]))
     return out
@@ -98,8 +98,8 @@ def scopes(path):
     return [l.rstrip("\n") for l in open(path) if l.startswith("scopes ")]
 
 
-def compare(args):
-    a, b = launches(args.a), launches(args.b)
+def compare(args, prefix="knn_"):   # (scripts/ba_launch_trace.py: prefix "ba_")
+    a, b = launches(args.a, prefix), launches(args.b, prefix)
     if args.log_a and args.log_b:
         a += scopes(args.log_a); b += scopes(args.log_b)
     if args.out:

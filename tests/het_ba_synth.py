@@ -145,7 +145,7 @@ MUTANTS = ("intr0", "fxfy", "bl0", "prefix")
 
 # ------------------------------------------------------------------------------------------------ which form a window runs in
 def planned_form(nfree, stereo):
-    """The optimiser's plan for a window of nfree free keyframes with its defaults (ba.hip: plan_persistent / uh_ba_set_problem)."""
+    """The optimiser's plan for a window of nfree free keyframes with its defaults (ba.hip: plan_ba)."""
     if nfree > 64:
         return "wide"
     if stereo or nfree > 16:

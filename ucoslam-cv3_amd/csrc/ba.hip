@@ -13,8 +13,8 @@
 // MI355X design.  The problem is tiny for this chip (~26k edges, 3000 landmarks, <=64 free poses), so the enemy is latency,
 // not bandwidth: the whole LM control flow lives in a device-resident state machine (BAState) and the host only enqueues a
 // fixed sequence of "steps" (one LM trial each) — no host synchronisation inside a pass.  Every kernel starts by reading the
-// state and returns immediately once the pass is done.  One step = TWO launches (+ lin in front of a pass, decide behind a
-// round of steps); the state lives in two slots, step s reads slot s&1 and leaves the state it ran with in the other one:
+// state and returns immediately once the pass is done.  One step = TWO launches up to 16 free cameras, three or four beyond (+ lin
+// in front of a pass, decide behind a round of steps); the state lives in two slots, step s reads slot s&1 and leaves the state it ran with in the other one:
 //   lin     (first trial of a pass only)  8 lanes per landmark: errors, Huber weights, Hll, bl, per-edge Hpl blocks;
 //                                          8 workgroups per free camera: Hpp, bp partials (deterministic tree reduction)
 //   schur   prologue in EVERY workgroup: apply the accept/reject decision of the previous trial (rho, flip current<->trial
@@ -26,15 +26,27 @@
 //           parallel instead of a one-workgroup launch.  Then 8 lanes per landmark: dx_l = D^-1 (b_l - Hpl^T dx_p), trial
 //           point, trial errors, partial chi2 / scale sums, and speculatively the linearisation AT THE TRIAL estimate into
 //           the trial half of the double-buffered Hll/bl/Hpl: accepting a trial flips estimate and linearisation together
-//   solve   stand-alone one-workgroup form of the solve for systems that need the HBM workspace (126 < n <= 384)
+//   solve   stand-alone one-workgroup form of the solve for systems beyond n = 126: on a packed triangle in LDS (22-32 free
+//           cameras) or in the HBM workspace (33-64)
+//   From 17 free cameras on the schur launch is the dense MFMA form (ba_schur_dense_kernel, from 33 ba_schur_dense_wide_kernel) with
+//   ba_schur_reduce_kernel behind it, which hands the solve the finished system: three or four launches per step.
 //   decide  stand-alone form of the decision, closes a round of enqueued steps (one wave)
 // (Folding solve and decide into the LAST-FINISHING workgroup of their producer launch — the threadfence-reduction pattern —
 // was measured and rejected: the agent-scope fences write back / invalidate the per-XCD L2s once per workgroup and cost
 // 15 us per step, five times the kernel boundary they save.  Redundant execution needs no fence.)
-// All reductions run in a fixed order, so results are run-to-run deterministic.  MFMA is not used: the only dense algebra is
-// 6x3·3x3·3x6 products per landmark pair (fp64) — far below any matrix-core tile; see DESIGN.md.
+// All reductions run in a fixed order, so results are run-to-run deterministic.  Up to 16 free cameras MFMA is not used: the only
+// dense algebra there is 6x3·3x3·3x6 products per landmark pair (fp64) — far below any matrix-core tile; the dense Schur kernels
+// from 17 free cameras on form the whole product in 16 x 16 fp64 MFMA tiles; see DESIGN.md.
+//
+// Host side (from struct StageLayout to the end of the file).  A problem runs in one of three forms: the persistent kernel
+// (ba_persist.hpp: 1-16 free cameras, two-row edges only, set through the pinned staging block by set_problem_fast), the launch chain
+// above, or the wide form (more than kMaxFree free cameras; "wide problems" below) — the latter two on host-built tables in one arena
+// (set_problem_tables: graph, wide lists, fp64 snapshot, carve + upload).  Which form, which Schur kernel and solve of the chain and
+// every size their launches take is decided once per set_problem by plan_ba(): a pure function of the problem's sizes, the UH_BA_*
+// knobs (BAKnobs, read at the top of each set_problem entry) and the device limits (BALimits, filled at create).  plan_problem() adds
+// the side effects (residency back-off, LDS grant); enqueue_steps() only reads the plan.  DESIGN.md section 4.3 has the table.
 #include <cfloat>
-#include <functional>
+#include <climits>
 #include <cstdio>
 #include <emmintrin.h>
 #include <immintrin.h>
@@ -2279,6 +2291,166 @@ struct StageLayout {
 // Result block (pinned host memory the kernel's tail writes): byte offsets
 struct ResLayout { size_t poses, state, points, chi2, bad, bytes, bytes_no_chi2; };   // chi2 last: it is handed over only on request
 
+// ------------------------------------------------------------------------------------------------ the plan of a problem
+// Every UH_BA_* variable a set_problem consults, read once at the top of the entry (tests flip them between two setParams of one
+// process).  Read elsewhere: UH_BA_SEQ0 at create, UH_BA_FAIL_RESIDENCY per optimize, UH_BA_RESIDENCY_TIMEOUT_MS and
+// UH_BA_INGEST_SPLIT once per process.
+constexpr int kKnobUnset = INT_MIN;
+struct BAKnobs {
+    bool legacy = false;           // UH_BA_FORM=legacy: no persistent form
+    bool wide = false;             // UH_BA_WIDE != 0: the wide form for any window with a free keyframe (tests compare the forms on the same inputs)
+    int nf = 0;                    // UH_BA_NF: 8 or 16 forces that persistent instantiation where the window fits it (A/B)
+    int lw = kKnobUnset;           // UH_BA_LW: landmarks per workgroup of the persistent form
+    int nsplit = kKnobUnset;       // UH_BA_NSPLIT: landmark chunks per camera pair of the pair Schur kernel (scripts/ba_chain_kernels.py)
+    bool hbm_solve = false;        // UH_BA_SOLVE=hbm: the HBM solve on systems of any size
+    bool prebuilt_off = false;     // UH_BA_PREBUILT=0: every solve assembles the system itself (A/B)
+    bool schur_dense_off = false;  // UH_BA_SCHUR_DENSE=0: the pair Schur kernel beyond 16 free keyframes too
+    int dense_g = kKnobUnset;      // UH_BA_DENSE_G: landmark groups of the dense Schur kernels at most (tuning)
+    bool spec = true;              // UH_BA_SPEC=0: the persistent kernel's three-hand-off trial (A/B)
+    bool obs24 = false;            // UH_BA_OBS24 != 0: never the 16-byte observation records
+    bool no_avx512 = false;        // UH_BA_NO_AVX512 (set at all): the SSE packer where the host has AVX-512
+};
+static BAKnobs read_knobs() {
+    BAKnobs k;
+    const char* e;
+    if ((e = getenv("UH_BA_FORM"))) k.legacy = std::string(e) == "legacy";
+    if ((e = getenv("UH_BA_WIDE"))) k.wide = atoi(e) != 0;
+    if ((e = getenv("UH_BA_NF"))) k.nf = atoi(e);
+    if ((e = getenv("UH_BA_LW"))) k.lw = atoi(e);
+    if ((e = getenv("UH_BA_NSPLIT"))) k.nsplit = atoi(e);
+    if ((e = getenv("UH_BA_SOLVE"))) k.hbm_solve = std::string(e) == "hbm";
+    if ((e = getenv("UH_BA_PREBUILT"))) k.prebuilt_off = atoi(e) == 0;
+    if ((e = getenv("UH_BA_SCHUR_DENSE"))) k.schur_dense_off = atoi(e) == 0;
+    if ((e = getenv("UH_BA_DENSE_G"))) k.dense_g = atoi(e);
+    if ((e = getenv("UH_BA_SPEC"))) k.spec = e[0] != '0';
+    if ((e = getenv("UH_BA_OBS24"))) k.obs24 = atoi(e) != 0;
+    k.no_avx512 = getenv("UH_BA_NO_AVX512") != nullptr;
+    return k;
+}
+
+// What the plan needs to know of the device: the context's compute units (its CU mask) and two LDS figures, queried once per
+// optimiser (uh_ba_create).
+struct BALimits { int cus, max_lds; size_t packed_static; };   // compute units, LDS a workgroup may have, static LDS of ba_solve_kernel<false, true>
+static void query_limits(const uh_ctx* ctx, BALimits& l) {
+    (void)hipSetDevice(ctx->device);
+    l.cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    int v = 0;
+    l.max_lds = (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) == hipSuccess && v > 0) ? v : 64 * 1024;
+    hipFuncAttributes fa{};   // (unknown: no packed solve)
+    l.packed_static = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&ba_solve_kernel<false, true>)) == hipSuccess ? fa.sharedSizeBytes : (size_t)1 << 30;
+    (void)hipGetLastError();   // (a failed query has chosen its fallback: no error is left pending)
+}
+
+struct PersistPlan { int NF, Lw, G, krows, nelem, SL, max_fix, kfix, lds, nb4, nblk, KS, off_cam; };   // NF: lanes per landmark = the instantiation (8 / 16)
+enum { kFormChain = 0, kFormPersist = 1, kFormWide = 2 };   // (the values uh_ba_form returns)
+enum { kSchurPair, kSchurDense, kSchurDenseWide };
+enum { kSolveFused, kSolvePacked, kSolveHbm };
+struct BAPlanIn {
+    int K, P, E, nfree;
+    bool stereo;       // the problem has three-row edges (the persistent form is monocular)
+    bool persist_ok;   // nothing outside the plan rules the persistent form out: the pinned report block is mapped, no residency back-off, no refused LDS grant
+};
+struct BAPlan {
+    int form;
+    bool persist_candidate;   // knobs and size class admit the persistent form — the problems the residency back-off counts — whether or not it fits the device
+    PersistPlan ps;           // kFormPersist
+    // launch chain (nsplit: the wide form's back-substitution launch takes it too)
+    int nsplit;               // landmark chunks per camera pair: what the pair Schur kernel and ba_assemble_pairs_kernel get
+    int schur; SchurDense sd; size_t lds_schur;
+    int solve; size_t lds_solve;   // fused into the back-substitution launch (system in LDS) / stand-alone on a packed triangle in LDS / in HBM
+    int pre_mode;             // ba_schur_reduce_kernel leaves the FINISHED system in p.S in the solve's layout (1: row stride n + 1, 2: packed); 0: partials in Spart
+    bool assemble_pairs;      // the HBM solve takes the finished system from ba_assemble_pairs_kernel instead of assembling alone
+    int ns_backsub, ns_solve; // the nsplit argument of ba_backsub_kernel / ba_solve_kernel (0: the system is finished)
+};
+
+// Does the window run as ONE persistent launch, and how?  One lane per (landmark, free-camera slot), so the lanes per landmark are the
+// number of free cameras rounded up to 8 or 16.  Beyond 16 the reduced system (6 nfree + 1)^2 doubles and the landmark panel no longer
+// share one workgroup's LDS, and 256 / 32 = 8 landmarks per workgroup would need more workgroups than the chip has compute units.
+// Limits come from the device, not from constants: every workgroup must be resident at once (one per compute unit — their LDS
+// blocks do not fit two to a CU), and its LDS block must fit what the device grants.
+static bool plan_persist(const BAPlanIn& in, const BAKnobs& kn, const BALimits& lim, PersistPlan& pl) {
+    const int nfree = in.nfree, P = in.P;
+    const int NF = ((kn.nf == 8 || kn.nf == 16) && nfree <= kn.nf) ? kn.nf : (nfree <= 8 ? 8 : (nfree <= 16 ? 16 : 0));
+    if (!NF) return false;
+    const int kLwMax = kPThreads / NF;
+    int Lw = std::max(std::min(8, kLwMax), std::min(kLwMax, uh_div_up(P, 64)));
+    if (kn.lw != kKnobUnset) Lw = std::max(1, std::min(kLwMax, kn.lw));
+    const int G = uh_div_up(P, Lw);
+    if (G > lim.cus) return false;
+    const int kfix = in.K - nfree;
+    if (kfix > 255) return false;
+    pl.NF = NF; pl.Lw = Lw; pl.G = G; pl.kfix = kfix;
+    pl.max_fix = Lw * kfix;   // bound: every landmark of the tile seen by every fixed frame (nothing is counted on the host)
+    pl.krows = (3 * Lw + 15) & ~15;
+    const int n = 6 * nfree;
+    pl.nb4 = (n + 3) / 4; pl.nblk = pl.nb4 * (pl.nb4 + 1) / 2;
+    pl.off_cam = pl.nblk * 16;   // the product part of a partial: the upper 4 x 4 blocks (vector FMA; the v_mfma_f64 form of rounds 2-4 was slower on gfx950 and is gone: docs/DESIGN_history_r1_r3.md, profiles/r03_mfma_f64.json)
+    pl.nelem = pl.off_cam + NF * 27 + 6 * NF + 4;
+    pl.SL = (uh_div_up(pl.nelem, G) + 1) & ~1;
+    // K-splits of the Schur product: work items = nblk * KS over 256 lanes, each krows / KS rows deep; the splits' partial blocks must
+    // fit the LDS region the reduced system occupies later ((n + 1)^2 doubles)
+    pl.KS = 1;
+    int best = 1 << 30;
+    for (int ks = 1; ks <= 6; ks++) {
+        if (ks > 1 && ks * pl.off_cam > (n + 1) * (n + 1) + 1452) break;
+        const int rounds = uh_div_up(pl.nblk * ks, kPThreads), depth = (uh_div_up(pl.krows, ks) + 3) & ~3;
+        if (rounds * depth < best) { best = rounds * depth; pl.KS = ks; }
+    }
+    pl.lds = NF == 8 ? persist_lds<8>(pl.krows, n, pl.max_fix, pl.kfix, pl.off_cam, pl.KS, pl.SL).total_bytes
+                     : persist_lds<16>(pl.krows, n, pl.max_fix, pl.kfix, pl.off_cam, pl.KS, pl.SL).total_bytes;
+    return pl.lds <= lim.max_lds;
+}
+
+// The form a problem runs in and everything its launches are sized by.  Arithmetic only: the knobs and the device limits come in, the
+// caller (plan_problem) owns the side effects.  DESIGN.md section 4.3 tabulates it.
+static BAPlan plan_ba(const BAPlanIn& in, const BAKnobs& kn, const BALimits& lim) {
+    BAPlan pl{};
+    const int nfree = in.nfree, n = 6 * nfree, P = in.P, npairs = nfree * (nfree + 1) / 2;
+    pl.persist_candidate = in.persist_ok && !in.stereo && !kn.legacy && !kn.wide && nfree >= 1 && P >= 1 && in.E < (1 << 20) - 1;
+    if (pl.persist_candidate && plan_persist(in, kn, lim, pl.ps)) { pl.form = kFormPersist; return pl; }
+    // wide form: sparse camera-pair lists + blocked dense LDL^T in HBM (see "wide problems" above)
+    pl.form = (nfree > kMaxFree || (kn.wide && nfree > 0)) ? kFormWide : kFormChain;
+    pl.nsplit = std::max(1, std::min(kMaxSplit, uh_div_up(P, kThreads)));
+    // every workgroup of the back-substitution launch assembles ALL npairs x nsplit partials itself: with many camera pairs fewer, fatter
+    // landmark chunks win (measured, 3000 landmarks: 17 / 20 / 32 free cameras 2.20 / 2.90 / 9.9 ms with 12 chunks, 1.77 / 2.14 / 7.3 with 2)
+    if (npairs > 32) pl.nsplit = std::max(1, std::min(pl.nsplit, uh_div_up(300, npairs)));   // (17 free cameras: 2 chunks, measured best — scripts/ba_chain_kernels.py with UH_BA_NSPLIT)
+    if (kn.nsplit != kKnobUnset) pl.nsplit = std::max(1, std::min(kMaxSplit, kn.nsplit));
+    if (pl.form == kFormWide) return pl;
+    // dense Schur form from 17 free keyframes on (17-32: 7..12 tile rows, one workgroup per landmark group; 33-64: the wide kernel)
+    if (nfree >= 17 && !kn.schur_dense_off) {
+        SchurDense& sd = pl.sd;
+        sd.ntt = uh_div_up(n, 16); sd.T = sd.ntt * (sd.ntt + 1) / 2;
+        sd.ys = 16 * sd.ntt + ((sd.ntt & 1) ? 0 : 16);   // row stride = 16 (mod 32) doubles: the four k-rows of an MFMA operand read fall on disjoint banks
+        const bool widek = nfree > 32;
+        const int chunks = std::max(uh_div_up(P, widek ? 8 : 16), 1);
+        const int gmax = kn.dense_g != kKnobUnset ? std::max(1, kn.dense_g) : (widek ? 96 : 224);
+        sd.cpw = uh_div_up(chunks, gmax); sd.G = uh_div_up(chunks, sd.cpw);
+        pl.schur = kSchurDense;
+        pl.lds_schur = (size_t)(48 * sd.ys + 48) * sizeof(double);
+        if (widek) {   // tile list cut over SP workgroups of at most 80 tiles, 4 waves x nown tiles each (kernel instantiations: 12, 16, 20)
+            sd.SP = uh_div_up(sd.T, 80);
+            const int need = uh_div_up(uh_div_up(sd.T, sd.SP), 4);
+            sd.nown = need <= 12 ? 12 : (need <= 16 ? 16 : 20);
+            pl.schur = kSchurDenseWide;
+            pl.lds_schur = (size_t)(24 * sd.ys + 24) * sizeof(double);
+        }
+        pl.nsplit = 1;   // (Spart then holds ONE chunk)
+    }
+    // which solve follows: fused into the back-substitution launch (system in LDS: n <= 126, 21 free cameras — 127 rows are the
+    // two-rows-per-lane factorisation's limit, 129 KB), stand-alone on a packed triangle in LDS (22-32 free cameras: 148 KB at 32,
+    // beside the kernel's static arrays, against the device's limit), else in HBM
+    const size_t packed = ((size_t)(n + 1) * (n + 2) / 2 + 2 + kLdltAux) * sizeof(double);   // rows 0 .. n (row n = right-hand side) + the solve's scratch
+    if (n <= 126 && !kn.hbm_solve) { pl.solve = kSolveFused; pl.lds_solve = (size_t)(n + 1) * (n + 1) * sizeof(double); }   // n rows of S + the right-hand-side row
+    else if (nfree <= kPackedFree && packed + lim.packed_static <= (size_t)std::max(lim.max_lds, 0) && !kn.hbm_solve) { pl.solve = kSolvePacked; pl.lds_solve = packed; }
+    else pl.solve = kSolveHbm;
+    // (the solve in HBM, 33-64 free cameras, factorises p.S in place: row stride n + 1 = mode 1, and nothing to copy)
+    if (pl.schur != kSchurPair && !kn.prebuilt_off) pl.pre_mode = pl.solve == kSolvePacked ? 2 : 1;
+    pl.assemble_pairs = pl.schur == kSchurPair && pl.solve == kSolveHbm && npairs > 0 && !kn.prebuilt_off;
+    pl.ns_backsub = pl.pre_mode ? 0 : pl.nsplit;
+    pl.ns_solve = pl.assemble_pairs ? 0 : pl.ns_backsub;
+    return pl;
+}
+
 struct uh_ba {
     uh_ctx* ctx = nullptr;
     bool have_problem = false;
@@ -2295,12 +2467,11 @@ struct uh_ba {
     double* d_pose0 = nullptr; double* d_pts0 = nullptr;
     unsigned char* h_stop = nullptr;      // pinned, device-visible force-stop flag
     int iters[2] = {0, 0};
-    int nsplit = 1;
-    bool dense = false; SchurDense sd{};   // 17-32 free keyframes of the launch chain: ba_schur_dense_kernel + ba_schur_reduce_kernel (Spart then holds ONE chunk)
-    bool wide = false;                    // more than kMaxFree free keyframes: sparse pair lists + blocked dense LDL^T in HBM
+    BAKnobs knobs;                        // as the set_problem entry of the current problem found them (the residency fallback of uh_ba_optimize reads them again)
+    BALimits lim{};
+    BAPlan plan{};                        // the form the current problem runs in (plan_ba): persistent — set through the staged path, results in the pinned block — launch chain or wide
     bool stereo = false; BAStereo sx{};   // the problem has three-row (stereo / RGB-D) edges: launch chain or wide form, STEREO instantiations
     std::vector<float> stage_depth, stage_bl;   // uh_ba_map_staging_stereo: per-observation depth / per-frame baseline beside the staging block
-    bool persist = false;                 // 1..8 free keyframes: the whole optimisation is ONE persistent launch (ba_persist.hpp)
     int persist_blocked = 0;              // > 0: the persistent form's workgroups did not all become resident lately (another spinning kernel shares the GPU): so many of the next problems take the launch chain
     BAPersist pq{};
     uh::DevBuf parena;                    // the persistent form's exchange buffers (tagged words only; [0, 64): the error word)
@@ -2325,17 +2496,12 @@ struct uh_ba {
     ResLayout rlay{};
     uh::DevBuf d_res;                     // the result block in HBM the kernel's tail fills first (same layout)
     bool want_chi2 = true;                // hand the per-observation chi2 (208 KB of the 270 KB of results at 26k observations) over to the host
-    bool fast = false;                    // the current problem was set through the staged path (persistent form)
-    int p_nf = 0;                         // lanes per landmark of the persistent instantiation in use
-    int p_lds_set[4] = {0, 0, 0, 0};      // dynamic LDS already granted to the instantiations (hipFuncSetAttribute once, not per problem)
-    int max_lds = 0;                      // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
+    int p_lds_set[2] = {0, 0};            // dynamic LDS already granted to the two instantiations (hipFuncSetAttribute once, not per problem)
     int job_kind = 0;                     // worker: 0 optimize, 1 setParams + optimize (uh_ba_solve_async)
-    bool knob_hbm_solve = false, knob_prebuilt_off = false;   // UH_BA_SOLVE=hbm / UH_BA_PREBUILT=0 as uh_ba_set_problem found them
     const uh_ba_problem* job_problem = nullptr; uh_ba_problem job_problem_copy{};
     int job_dims[3] = {0, 0, 0};
     uh_ba_params job_params{}; bool job_has_params = false;
     unsigned p_seq = 0;                   // launches of the persistent kernel by this optimizer: 20 bits of it tag the exchanged words
-    int p_lds = 0;
     BAWide wd{};
     int step = 0;                         // LM steps enqueued since uh_ba_optimize began: step s reads state slot s & 1
     bool optimized = false;
@@ -2363,25 +2529,6 @@ struct uh_ba {
 
 namespace {
 
-void quat_from_R_host(const double* R, double* q) {
-    double t = R[0] + R[4] + R[8];
-    if (t > 0) {
-        t = std::sqrt(t + 1.0); q[3] = 0.5 * t; t = 0.5 / t;
-        q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[i * 4]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-        q[i] = 0.5 * t; t = 0.5 / t;
-        q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t; q[j] = (R[j * 3 + i] + R[i * 3 + j]) * t; q[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-    }
-    if (q[3] < 0) for (int a = 0; a < 4; a++) q[a] = -q[a];
-    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int a = 0; a < 4; a++) q[a] /= n;
-}
-
 // Launch of a kernel that linearises: the monocular instantiation (same arguments as ever) or, on a problem with three-row edges, the
 // STEREO one with the BAStereo block behind them.  T0: a leading template argument of the kernel's own.
 #define UH_LAUNCH_BA(b, K, grid, block, shmem, ...)                                                            \
@@ -2395,17 +2542,16 @@ void quat_from_R_host(const double* R, double* q) {
         else UH_LAUNCH((b)->ctx, (K<T0, false>), grid, block, shmem, __VA_ARGS__);                                 \
     } while (0)
 
+// nsteps LM trials of the problem's plan (plan_ba decided everything; nothing is decided here) and the closing decision
 int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
     hipStream_t st = b->ctx->stream;
     const BADims& d = b->dims;
+    const BAPlan& pl = b->plan;
     const int npairs = d.nfree * (d.nfree + 1) / 2;
-    const bool hbm_forced = b->knob_hbm_solve;   // (tests: the HBM solve on systems of any size; read by uh_ba_set_problem on the caller's thread)
-    const int use_lds = (d.n <= 126 && !hbm_forced) ? 1 : 0;   // (21 free cameras: 127 rows = the two-rows-per-lane factorisation's limit; 129 KB of LDS)
-    const size_t lds = use_lds ? (size_t)(d.n + 1) * (d.n + 1) * sizeof(double) : 0;   // n rows of S + the right-hand-side row
     for (int s = 0; s < nsteps; s++) {
         const int slot = b->step & 1;   // state left by the previous step (or by begin_pass / the closing decide kernel)
         if (pass_start && s == 0) UH_LAUNCH_BA(b, ba_lin_kernel, dim3(d.nPointBlocks + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, slot);
-        if (b->wide) {
+        if (pl.form == kFormWide) {
             const BAWide& W = b->wd;
             const int run = slot ^ 1;   // the state this step runs with (published by the advance kernel)
             UH_LAUNCH(b->ctx, ba_advance_kernel, dim3(1), dim3(64), 0, b->ptrs, d, slot);
@@ -2425,49 +2571,29 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
                 UH_LAUNCH(b->ctx, ba_ldlw_back_kernel, dim3(std::max(uh_div_up(k0, 256), 1)), dim3(256), 0, b->ptrs, W, run, k0, nb);
             }
             UH_LAUNCH(b->ctx, ba_posew_kernel, dim3(uh_div_up(d.nfree, 256)), dim3(256), 0, b->ptrs, d, W, run);
-            UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, b->nsplit, run);
+            UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, pl.nsplit, run);
             b->step++;
             continue;
         }
-        // which solve follows: fused into the back-substitution launch (system in LDS, n <= 126), stand-alone on a packed triangle in LDS
-        // (22-32 free cameras: 148 KB at 32, beside the kernel's static arrays — both checked against the device's limit), else in HBM
-        const size_t packed = ((size_t)(d.n + 1) * (d.n + 2) / 2 + 2 + kLdltAux) * sizeof(double);   // rows 0 .. n (row n = right-hand side) + the solve's scratch
-        bool use_packed = false;
-        if (!use_lds) {
-            static const size_t packed_static = [] { hipFuncAttributes fa{}; return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&ba_solve_kernel<false, true>)) == hipSuccess ? fa.sharedSizeBytes : (size_t)1 << 30; }();
-            if (b->max_lds <= 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, b->ctx->device) == hipSuccess) b->max_lds = v; }
-            use_packed = d.nfree <= kPackedFree && packed + packed_static <= (size_t)std::max(b->max_lds, 0) && !hbm_forced;
-        }
-        // dense Schur form: the reduce launch leaves the FINISHED system in p.S in the following solve's layout (1: row stride n + 1,
-        // 2: packed) and the solve copies it (nsplit 0); the HBM solve keeps its own assembly from Spart (0)
-        const bool pre_off = b->knob_prebuilt_off;   // (A/B knob, read by uh_ba_set_problem on the caller's thread: getenv here would race a setenv elsewhere)
-        // (the solve in HBM, 33-64 free cameras, factorises p.S in place: row stride n + 1 = mode 1, and nothing to copy)
-        const int pre_mode = (b->dense && !pre_off) ? ((use_lds || !use_packed) ? 1 : 2) : 0;
-        const int ns = pre_mode ? 0 : b->nsplit;
-        if (b->dense) {
-            const SchurDense& sd = b->sd;
-            if (sd.SP > 0) {
-                const dim3 gridw(d.nfree * kCamChunks + sd.G * sd.SP);
-                const size_t ldsw = (size_t)(24 * sd.ys + 24) * sizeof(double);
-                if (sd.nown == 12) UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, 12, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
-                else if (sd.nown == 16) UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, 16, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
-                else UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, 20, gridw, dim3(kThreads), ldsw, b->ptrs, d, sd, slot);
-            } else
-                UH_LAUNCH_BA(b, ba_schur_dense_kernel, dim3(d.nfree * kCamChunks + sd.G), dim3(kThreads), (size_t)(48 * sd.ys + 48) * sizeof(double), b->ptrs, d, sd, slot);
-            UH_LAUNCH(b->ctx, ba_schur_reduce_kernel, dim3(sd.T + uh_div_up(d.n, kThreads)), dim3(kThreads * kReduceGroups), 0, b->ptrs, d, sd, slot ^ 1, pre_mode);
-        } else
-        UH_LAUNCH_BA(b, ba_schur_kernel, dim3(std::max(npairs, 1) * b->nsplit + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, b->nsplit, slot);
-        // the solve in HBM takes the finished system from a launch of its own (every pair's words in parallel) instead of assembling alone
-        const bool pre_hbm = !b->dense && !use_lds && !use_packed && npairs > 0 && !pre_off;
-        if (pre_hbm) UH_LAUNCH(b->ctx, ba_assemble_pairs_kernel, dim3(uh_div_up(npairs * 42, kThreads)), dim3(kThreads), 0, b->ptrs, d, b->nsplit, slot ^ 1);
-        if (use_lds) {
-            UH_LAUNCH_BA1(b, ba_backsub_kernel, true, dim3(d.nPointBlocks), dim3(kFusedThreads), lds, b->ptrs, d, ns, slot ^ 1);
+        const SchurDense& sd = pl.sd;
+        if (pl.schur == kSchurDenseWide) {
+#define UH_DENSE_WIDE(NOWN) UH_LAUNCH_BA1(b, ba_schur_dense_wide_kernel, NOWN, dim3(d.nfree * kCamChunks + sd.G * sd.SP), dim3(kThreads), pl.lds_schur, b->ptrs, d, sd, slot)
+            switch (sd.nown) { case 12: UH_DENSE_WIDE(12); break; case 16: UH_DENSE_WIDE(16); break; default: UH_DENSE_WIDE(20); }
+#undef UH_DENSE_WIDE
+        } else if (pl.schur == kSchurDense)
+            UH_LAUNCH_BA(b, ba_schur_dense_kernel, dim3(d.nfree * kCamChunks + sd.G), dim3(kThreads), pl.lds_schur, b->ptrs, d, sd, slot);
+        else
+            UH_LAUNCH_BA(b, ba_schur_kernel, dim3(std::max(npairs, 1) * pl.nsplit + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, pl.nsplit, slot);
+        if (pl.schur != kSchurPair) UH_LAUNCH(b->ctx, ba_schur_reduce_kernel, dim3(sd.T + uh_div_up(d.n, kThreads)), dim3(kThreads * kReduceGroups), 0, b->ptrs, d, sd, slot ^ 1, pl.pre_mode);
+        if (pl.assemble_pairs) UH_LAUNCH(b->ctx, ba_assemble_pairs_kernel, dim3(uh_div_up(npairs * 42, kThreads)), dim3(kThreads), 0, b->ptrs, d, pl.nsplit, slot ^ 1);
+        if (pl.solve == kSolveFused) {
+            UH_LAUNCH_BA1(b, ba_backsub_kernel, true, dim3(d.nPointBlocks), dim3(kFusedThreads), pl.lds_solve, b->ptrs, d, pl.ns_backsub, slot ^ 1);
         } else {
-            if (use_packed)
-                UH_LAUNCH(b->ctx, (ba_solve_kernel<false, true>), dim3(1), dim3(kPackedThreads), packed, b->ptrs, d, ns, slot ^ 1);
+            if (pl.solve == kSolvePacked)
+                UH_LAUNCH(b->ctx, (ba_solve_kernel<false, true>), dim3(1), dim3(kPackedThreads), pl.lds_solve, b->ptrs, d, pl.ns_solve, slot ^ 1);
             else
-                UH_LAUNCH(b->ctx,ba_solve_kernel<false>, dim3(1), dim3(kHbmThreads), 0, b->ptrs, d, pre_hbm ? 0 : ns, slot ^ 1);
-            UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, ns, slot ^ 1);
+                UH_LAUNCH(b->ctx,ba_solve_kernel<false>, dim3(1), dim3(kHbmThreads), 0, b->ptrs, d, pl.ns_solve, slot ^ 1);
+            UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, pl.ns_backsub, slot ^ 1);
         }
         b->step++;
     }
@@ -2498,6 +2624,15 @@ int wait_state(uh_ba* b, BAState* hs, const volatile uint8_t* stop_asap) {
     }
     UH_HIP_CHECK(hipStreamSynchronize(st));
     return UH_OK;
+}
+
+// The prologue of pass 2 and its steps: edges relabelled, the pass begun.  gated 1: enqueued behind pass 1 in one go — both kernels do
+// nothing unless ba_gate_kernel found pass 1 complete; 0: by the host, after a pass 1 that overran its budget.
+int enqueue_pass2(uh_ba* b, int n2, float mc, int gated, int nsteps) {
+    const BADims& d = b->dims;
+    if (d.E > 0) UH_LAUNCH_BA(b, ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, gated);
+    UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n2, mc, b->step & 1, gated);
+    return enqueue_steps(b, nsteps, true);
 }
 
 // rejected trials consumed steps of the budget: enqueue short rounds until the running pass is finished
@@ -2562,10 +2697,10 @@ int run_persistent(uh_ba* b, const volatile uint8_t* stop_asap, int n1, int n2, 
     volatile unsigned long long* h_done = reinterpret_cast<volatile unsigned long long*>(b->h_stop + 192);
     q.host_state = reinterpret_cast<BAState*>(static_cast<unsigned char*>(d_pin) + 64);
     q.host_done = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(d_pin) + 192);
-    switch (b->p_nf) {
-        case 8: UH_LAUNCH(b->ctx, ba_persist_kernel<8>, dim3(q.G), dim3(kPThreads), (size_t)b->p_lds, b->ptrs, b->dims, q); break;
-        case 16: UH_LAUNCH(b->ctx, ba_persist_kernel<16>, dim3(q.G), dim3(kPThreads), (size_t)b->p_lds, b->ptrs, b->dims, q); break;
-        default: uh::set_error("uh_ba_optimize: no persistent instantiation for %d lanes per landmark", b->p_nf); return UH_EINVAL;
+    switch (b->plan.ps.NF) {
+        case 8: UH_LAUNCH(b->ctx, ba_persist_kernel<8>, dim3(q.G), dim3(kPThreads), (size_t)b->plan.ps.lds, b->ptrs, b->dims, q); break;
+        case 16: UH_LAUNCH(b->ctx, ba_persist_kernel<16>, dim3(q.G), dim3(kPThreads), (size_t)b->plan.ps.lds, b->ptrs, b->dims, q); break;
+        default: uh::set_error("uh_ba_optimize: no persistent instantiation for %d lanes per landmark", b->plan.ps.NF); return UH_EINVAL;
     }
     UH_HIP_CHECK(hipGetLastError());
     bool err = false;
@@ -2594,7 +2729,7 @@ int run_persistent(uh_ba* b, const volatile uint8_t* stop_asap, int n1, int n2, 
         (void)hipStreamSynchronize(st);
         (void)hipMemsetAsync(b->dscratch.as<char>() + 768, 0, 4, st);   // the completion count of an aborted launch is meaningless
         b->done_base = 0;
-        if (b->persist_not_resident) uh::set_error("uh_ba_optimize: the persistent kernel's workgroups did not all become resident (%d workgroups, %d bytes of LDS each)", q.G, b->p_lds);
+        if (b->persist_not_resident) uh::set_error("uh_ba_optimize: the persistent kernel's workgroups did not all become resident (%d workgroups, %d bytes of LDS each)", q.G, b->plan.ps.lds);
         else {
             const hipError_t le = hipGetLastError();
             uh::set_error("uh_ba_optimize: the persistent launch ended without reporting (%s): a device fault or a 30 s stall, not a residency problem — not retried",
@@ -2640,6 +2775,7 @@ int uh_ba_create(uh_ctx* ctx, uh_ba** out) {
     // one pinned, device-visible block: [0] force-stop byte, [64..) the final BAState of a persistent launch, [192] its completion word
     if (hipHostMalloc(reinterpret_cast<void**>(&b->h_stop), 256, hipHostMallocMapped) != hipSuccess) b->h_stop = nullptr;
     if (b->h_stop) std::memset(b->h_stop, 0, 256);
+    query_limits(ctx, b->lim);
     if (const char* e = getenv("UH_BA_SEQ0")) b->p_seq = (unsigned)strtoul(e, nullptr, 0);   // tests: start next to the wrap of the exchange tags
     *out = b;
     return UH_OK;
@@ -2649,251 +2785,228 @@ void uh_ba_destroy(uh_ba* b) { delete b; }
 
 }  // extern "C"
 
-// setParams for the forms that keep host-built tables: the launch chain (more free keyframes than the persistent kernel is
-// instantiated for, or a window whose fixed frames do not fit its LDS) and the wide form (global BA).  Arrays anywhere in host memory.
-// (sin: the three-row edges of a stereo / RGB-D problem — NULL on the monocular route, whose tables and arena layout it leaves as they are)
-struct StereoIn { std::vector<double> ur, bf; std::vector<unsigned char> st; double delta3 = 0, chi2_th3 = 0; };
+// ------------------------------------------------------------------------------------------------ setParams with host-built tables
+// fp64 snapshot of one frame, toSE3Quat (globaloptimizer_g2o.cpp:80-90): float 4x4 -> double R, t -> normalised quaternion, plus the
+// widened intrinsics.  Rt12 (the staged path): R | t expanded from that quaternion, as ba_init_state_kernel does for the launch chain.
+static void snapshot_frame(const float* M, const float* intr_f, double* pose7, double* intr4, double* Rt12 = nullptr) {
+    const double R[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
+    quat_from_R(R, pose7);
+    quat_norm_pos(pose7);
+    pose7[4] = M[3]; pose7[5] = M[7]; pose7[6] = M[11];
+    for (int j = 0; j < 4; j++) intr4[j] = intr_f[j];
+    if (Rt12) { quat_to_R(pose7, Rt12); Rt12[9] = pose7[4]; Rt12[10] = pose7[5]; Rt12[11] = pose7[6]; }
+}
 
-static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const StereoIn* sin = nullptr) {
-    b->fast = false;
-    b->stereo = false;
-    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
-    std::vector<int> slot(K, -1), free_kf;
-    for (int k = 0; k < K; k++) if (!pr->fixed[k]) { slot[k] = (int)free_kf.size(); free_kf.push_back(k); }
-    const int nfree = (int)free_kf.size();
-    constexpr int kMaxFreeWide = 4096;
-    UH_REQUIRE(nfree <= kMaxFreeWide, "uh_ba_set_problem: %d free keyframes (supported: <= %d)", nfree, kMaxFreeWide);
-    // wide form: sparse camera-pair lists + blocked dense LDL^T in HBM (see "wide problems" above); UH_BA_WIDE=1 forces it for
-    // small problems (tests compare the two forms on the same inputs)
-    const bool wide = nfree > kMaxFree || (getenv("UH_BA_WIDE") && atoi(getenv("UH_BA_WIDE")) != 0 && nfree > 0);
-    b->wide = wide;
-    for (int e = 0; e < E; e++)
-        UH_REQUIRE(pr->obs_point[e] >= 0 && pr->obs_point[e] < P && pr->obs_frame[e] >= 0 && pr->obs_frame[e] < K,
-                   "uh_ba_set_problem: observation %d references point %d / frame %d out of range", e, pr->obs_point[e], pr->obs_frame[e]);
-    // host-side graph structure
-    std::vector<int> pt_ptr(P + 1, 0), pt_edges(E), cam_ptr(nfree + 1, 0), cam_edges, edge_of(wide ? 1 : (size_t)P * std::max(nfree, 1), -1);
-    for (int e = 0; e < E; e++) pt_ptr[pr->obs_point[e] + 1]++;
-    for (int p = 0; p < P; p++) pt_ptr[p + 1] += pt_ptr[p];
-    { std::vector<int> fill(pt_ptr.begin(), pt_ptr.end() - 1); for (int e = 0; e < E; e++) pt_edges[fill[pr->obs_point[e]]++] = e; }
-    for (int e = 0; e < E; e++) { const int s = slot[pr->obs_frame[e]]; if (s >= 0) cam_ptr[s + 1]++; }
-    for (int s = 0; s < nfree; s++) cam_ptr[s + 1] += cam_ptr[s];
-    cam_edges.resize(cam_ptr[nfree]);
-    { std::vector<int> fill(cam_ptr.begin(), cam_ptr.end() - 1);
-      for (int e = 0; e < E; e++) { const int s = slot[pr->obs_frame[e]]; if (s >= 0) { cam_edges[fill[s]++] = e;
-          if (!wide) {
-              UH_REQUIRE(edge_of[(size_t)pr->obs_point[e] * nfree + s] < 0, "uh_ba_set_problem: point %d observed twice by frame %d", pr->obs_point[e], pr->obs_frame[e]);
-              edge_of[(size_t)pr->obs_point[e] * nfree + s] = e; } } } }
-    // wide form: (s1 <= s2) camera pairs that share landmarks, their (landmark, edge1, edge2) triples in landmark order, <= 256 per item
-    std::vector<int> w_pair_s1, w_pair_s2, w_pair_item_ptr, w_item_pair, w_item_begin, w_item_count, w_tri_pt, w_tri_e1, w_tri_e2;
-    if (wide) {
-        // counting sort by pair key: pass 1 counts the triples of every (s1 <= s2), pass 2 drops them into place — landmarks
-        // are visited in ascending order both times, so a pair's triples end up in landmark order
-        std::vector<std::vector<std::pair<int, int>>> obs_of(P);
-        for (int pt = 0; pt < P; pt++) {
-            auto& obs = obs_of[pt];
-            for (int i = pt_ptr[pt]; i < pt_ptr[pt + 1]; i++) { const int e = pt_edges[i], s = slot[pr->obs_frame[e]]; if (s >= 0) obs.push_back({s, e}); }
-            std::sort(obs.begin(), obs.end());
-            for (size_t i = 1; i < obs.size(); i++)
-                UH_REQUIRE(obs[i].first != obs[i - 1].first, "uh_ba_set_problem: point %d observed twice by frame %d", pt, free_kf[obs[i].first]);
-        }
-        std::vector<size_t> key_count((size_t)nfree * nfree + 1, 0);
-        for (int pt = 0; pt < P; pt++) {
-            const auto& obs = obs_of[pt];
-            for (size_t i = 0; i < obs.size(); i++)
-                for (size_t j = i; j < obs.size(); j++) key_count[(size_t)obs[i].first * nfree + obs[j].first + 1]++;
-        }
-        for (size_t k = 0; k < (size_t)nfree * nfree; k++) key_count[k + 1] += key_count[k];
-        const size_t n_tri = key_count[(size_t)nfree * nfree];
-        UH_REQUIRE(n_tri < (size_t)1 << 31, "uh_ba_set_problem: %zu co-observation triples exceed the 32-bit index range", n_tri);
-        w_tri_pt.resize(n_tri); w_tri_e1.resize(n_tri); w_tri_e2.resize(n_tri);
-        {
-            std::vector<size_t> fill(key_count.begin(), key_count.end() - 1);
-            for (int pt = 0; pt < P; pt++) {
-                const auto& obs = obs_of[pt];
-                for (size_t i = 0; i < obs.size(); i++)
-                    for (size_t j = i; j < obs.size(); j++) {
-                        const size_t at = fill[(size_t)obs[i].first * nfree + obs[j].first]++;
-                        w_tri_pt[at] = pt; w_tri_e1[at] = obs[i].second; w_tri_e2[at] = obs[j].second;
-                    }
-            }
-        }
-        std::vector<char> have_diag(std::max(nfree, 1), 0);
-        auto add_pair = [&](int s1, int s2, int begin, int count) {
-            w_pair_s1.push_back(s1); w_pair_s2.push_back(s2); w_pair_item_ptr.push_back((int)w_item_pair.size());
-            for (int o = 0; o < count; o += kThreads) { w_item_pair.push_back((int)w_pair_s1.size() - 1); w_item_begin.push_back(begin + o); w_item_count.push_back(std::min(kThreads, count - o)); }
-            if (s1 == s2) have_diag[s1] = 1;
-        };
-        for (int s1 = 0; s1 < nfree; s1++)
-            for (int s2 = s1; s2 < nfree; s2++) {
-                const size_t k = (size_t)s1 * nfree + s2;
-                if (key_count[k + 1] > key_count[k]) add_pair(s1, s2, (int)key_count[k], (int)(key_count[k + 1] - key_count[k]));
-            }
-        for (int sfree = 0; sfree < nfree; sfree++) if (!have_diag[sfree]) add_pair(sfree, sfree, 0, 0);   // a camera without landmarks still owns its diagonal block
-        w_pair_item_ptr.push_back((int)w_item_pair.size());
-    }
-    std::vector<double> pose0(7 * (size_t)K), pts0(3 * (size_t)P), intr(4 * (size_t)K), uv(2 * (size_t)E), w(E);
-    for (int k = 0; k < K; k++) {   // toSE3Quat (globaloptimizer_g2o.cpp:80-90): float 4x4 -> double R,t -> quaternion
-        const float* M = pr->poses_f2g + 16 * k;
-        const double R[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
-        quat_from_R_host(R, &pose0[7 * k]);
-        pose0[7 * k + 4] = M[3]; pose0[7 * k + 5] = M[7]; pose0[7 * k + 6] = M[11];
-        for (int j = 0; j < 4; j++) intr[4 * k + j] = pr->intr[4 * k + j];
-    }
-    for (size_t i = 0; i < pts0.size(); i++) pts0[i] = pr->points[i];
-    for (int e = 0; e < E; e++) { uv[2 * e] = pr->obs_uv[2 * e]; uv[2 * e + 1] = pr->obs_uv[2 * e + 1]; w[e] = pr->obs_inv_sigma[e]; }
-    b->poses_in.assign(pr->poses_f2g, pr->poses_f2g + 16 * (size_t)K);
-    b->fixed.assign(pr->fixed, pr->fixed + K);
-
+static void fill_dims(uh_ba* b, int K, int P, int E, int nfree) {
     BADims& d = b->dims;
     d.K = K; d.P = P; d.E = E; d.nfree = nfree; d.n = 6 * nfree;
     d.nPointBlocks = std::max(uh_div_up(P, kPointsPerBlock), 1);
     d.delta = b->params.huber_delta; d.dsqr = d.delta * d.delta; d.chi2_th = b->params.chi2_threshold;
+}
 
-    // carve one arena
-    uh::Layout A;
-    const size_t o_pt_ptr = A.take<int>(P + 1), o_pt_edges = A.take<int>(E), o_cam_ptr = A.take<int>(nfree + 1), o_cam_edges = A.take<int>(cam_edges.size());
-    const size_t o_e_pt = A.take<int>(E), o_e_kf = A.take<int>(E), o_uv = A.take<double>(2 * (size_t)E), o_w = A.take<double>(E);
-    const size_t o_slot = A.take<int>(K), o_free = A.take<int>(std::max(nfree, 1)), o_intr = A.take<double>(4 * (size_t)K), o_edge_of = A.take<int>(edge_of.size());
-    const size_t o_ur = sin ? A.take<double>(E) : 0, o_bf = sin ? A.take<double>(E) : 0, o_est = sin ? A.take<unsigned char>(E) : 0;   // (inside the pinned prefix)
-    const size_t o_pose0 = A.take<double>(7 * (size_t)K), o_pts0 = A.take<double>(3 * (size_t)P);
-    size_t o_pose[2], o_poseR[2], o_pts[2];
-    for (int i = 0; i < 2; i++) { o_pose[i] = A.take<double>(7 * (size_t)K); o_poseR[i] = A.take<double>(12 * (size_t)K); o_pts[i] = A.take<double>(3 * (size_t)P); }
-    const size_t o_act = A.take<unsigned char>(E), o_rob = A.take<unsigned char>(E), o_err = A.take<double>(2 * (size_t)E), o_chi2 = A.take<double>(E);
-    size_t o_Hll[2], o_bl[2], o_Hpl[2];
-    for (int i = 0; i < 2; i++) { o_Hll[i] = A.take<double>(9 * (size_t)P); o_bl[i] = A.take<double>(3 * (size_t)P); o_Hpl[i] = A.take<double>(18 * (size_t)E); }
-    const size_t o_Hpp = A.take<double>(27 * (size_t)kCamChunks * std::max(nfree, 1)), o_bp = A.take<double>(std::max(d.n, 1));
-    const int npairs_h = nfree * (nfree + 1) / 2;
-    b->nsplit = std::max(1, std::min(kMaxSplit, uh_div_up(P, kThreads)));
-    // every workgroup of the back-substitution launch assembles ALL npairs x nsplit partials itself: with many camera pairs fewer, fatter
-    // landmark chunks win (measured, 3000 landmarks: 17 / 20 / 32 free cameras 2.20 / 2.90 / 9.9 ms with 12 chunks, 1.77 / 2.14 / 7.3 with 2)
-    if (npairs_h > 32) b->nsplit = std::max(1, std::min(b->nsplit, uh_div_up(300, npairs_h)));   // (17 free cameras: 2 chunks, measured best — scripts/ba_chain_kernels.py with UH_BA_NSPLIT)
-    if (const char* e = getenv("UH_BA_NSPLIT")) b->nsplit = std::max(1, std::min(kMaxSplit, atoi(e)));   // (measurement override: scripts/ba_chain_kernels.py)
-    // knobs the launch chain consults per step, possibly on the optimiser's worker thread: read ONCE here, on the caller's thread
-    { const char* e = getenv("UH_BA_SOLVE"); b->knob_hbm_solve = e && std::string(e) == "hbm"; }
-    { const char* e = getenv("UH_BA_PREBUILT"); b->knob_prebuilt_off = e && atoi(e) == 0; }
-    // dense Schur form: windows of 17-32 free keyframes (UH_BA_SCHUR_DENSE=0 keeps the pair form)
+// (sin: the three-row edges of a stereo / RGB-D problem — NULL on the monocular route, whose tables and arena layout it leaves as they are)
+struct StereoIn { std::vector<double> ur, bf; std::vector<unsigned char> st; double delta3 = 0, chi2_th3 = 0; };
+
+// Part 1, the graph: reduced-system slots, CSR of the edges per point and per free camera, (point, slot) -> edge (launch chain only)
+struct BAGraph { std::vector<int> slot, free_kf, pt_ptr, pt_edges, cam_ptr, cam_edges, edge_of; };
+static int build_graph(const uh_ba_problem* pr, bool wide, BAGraph& g) {
+    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
+    g.slot.assign(K, -1);
+    for (int k = 0; k < K; k++) if (!pr->fixed[k]) { g.slot[k] = (int)g.free_kf.size(); g.free_kf.push_back(k); }
+    const int nfree = (int)g.free_kf.size();
+    constexpr int kMaxFreeWide = 4096;
+    UH_REQUIRE(nfree <= kMaxFreeWide, "uh_ba_set_problem: %d free keyframes (supported: <= %d)", nfree, kMaxFreeWide);
+    for (int e = 0; e < E; e++)
+        UH_REQUIRE(pr->obs_point[e] >= 0 && pr->obs_point[e] < P && pr->obs_frame[e] >= 0 && pr->obs_frame[e] < K,
+                   "uh_ba_set_problem: observation %d references point %d / frame %d out of range", e, pr->obs_point[e], pr->obs_frame[e]);
+    g.pt_ptr.assign(P + 1, 0); g.pt_edges.resize(E); g.cam_ptr.assign(nfree + 1, 0); g.edge_of.assign(wide ? 1 : (size_t)P * std::max(nfree, 1), -1);
+    for (int e = 0; e < E; e++) g.pt_ptr[pr->obs_point[e] + 1]++;
+    for (int p = 0; p < P; p++) g.pt_ptr[p + 1] += g.pt_ptr[p];
+    { std::vector<int> fill(g.pt_ptr.begin(), g.pt_ptr.end() - 1); for (int e = 0; e < E; e++) g.pt_edges[fill[pr->obs_point[e]]++] = e; }
+    for (int e = 0; e < E; e++) { const int s = g.slot[pr->obs_frame[e]]; if (s >= 0) g.cam_ptr[s + 1]++; }
+    for (int s = 0; s < nfree; s++) g.cam_ptr[s + 1] += g.cam_ptr[s];
+    g.cam_edges.resize(g.cam_ptr[nfree]);
+    std::vector<int> fill(g.cam_ptr.begin(), g.cam_ptr.end() - 1);
+    for (int e = 0; e < E; e++) {
+        const int s = g.slot[pr->obs_frame[e]];
+        if (s < 0) continue;
+        g.cam_edges[fill[s]++] = e;
+        if (wide) continue;   // (the wide lists find a pair that occurs twice themselves)
+        int& cell = g.edge_of[(size_t)pr->obs_point[e] * nfree + s];
+        UH_REQUIRE(cell < 0, "uh_ba_set_problem: point %d observed twice by frame %d", pr->obs_point[e], pr->obs_frame[e]);
+        cell = e;
+    }
+    return UH_OK;
+}
+
+// Part 2, the wide form's lists: (s1 <= s2) camera pairs that share landmarks, their (landmark, edge1, edge2) triples in landmark
+// order, <= 256 per item
+struct WideLists { std::vector<int> pair_s1, pair_s2, pair_item_ptr, item_pair, item_begin, item_count, tri_pt, tri_e1, tri_e2; };
+static int build_wide_lists(const uh_ba_problem* pr, const BAGraph& g, WideLists& w) {
+    const int P = pr->n_points, nfree = (int)g.free_kf.size();
+    // counting sort by pair key: pass 1 counts the triples of every (s1 <= s2), pass 2 drops them into place — landmarks
+    // are visited in ascending order both times, so a pair's triples end up in landmark order
+    std::vector<std::vector<std::pair<int, int>>> obs_of(P);
+    for (int pt = 0; pt < P; pt++) {
+        auto& obs = obs_of[pt];
+        for (int i = g.pt_ptr[pt]; i < g.pt_ptr[pt + 1]; i++) { const int e = g.pt_edges[i], s = g.slot[pr->obs_frame[e]]; if (s >= 0) obs.push_back({s, e}); }
+        std::sort(obs.begin(), obs.end());
+        for (size_t i = 1; i < obs.size(); i++)
+            UH_REQUIRE(obs[i].first != obs[i - 1].first, "uh_ba_set_problem: point %d observed twice by frame %d", pt, g.free_kf[obs[i].first]);
+    }
+    std::vector<size_t> key_count((size_t)nfree * nfree + 1, 0);
+    for (int pt = 0; pt < P; pt++) {
+        const auto& obs = obs_of[pt];
+        for (size_t i = 0; i < obs.size(); i++)
+            for (size_t j = i; j < obs.size(); j++) key_count[(size_t)obs[i].first * nfree + obs[j].first + 1]++;
+    }
+    for (size_t k = 0; k < (size_t)nfree * nfree; k++) key_count[k + 1] += key_count[k];
+    const size_t n_tri = key_count[(size_t)nfree * nfree];
+    UH_REQUIRE(n_tri < (size_t)1 << 31, "uh_ba_set_problem: %zu co-observation triples exceed the 32-bit index range", n_tri);
+    w.tri_pt.resize(n_tri); w.tri_e1.resize(n_tri); w.tri_e2.resize(n_tri);
     {
-        const char* e = getenv("UH_BA_SCHUR_DENSE");
-        b->dense = !wide && nfree >= 17 && nfree <= kMaxFree && !(e && atoi(e) == 0);   // (17-32: 7..12 tile rows, one workgroup per landmark group; 33-64: the wide kernel)
-        if (b->dense) {
-            SchurDense& sd = b->sd;
-            sd.ntt = uh_div_up(d.n, 16); sd.T = sd.ntt * (sd.ntt + 1) / 2;
-            sd.ys = 16 * sd.ntt + ((sd.ntt & 1) ? 0 : 16);   // row stride = 16 (mod 32) doubles: the four k-rows of an MFMA operand read fall on disjoint banks
-            const bool widek = nfree > 32;
-            const int chunks = std::max(uh_div_up(P, widek ? 8 : 16), 1);
-            const int gmax = getenv("UH_BA_DENSE_G") ? std::max(1, atoi(getenv("UH_BA_DENSE_G"))) : (widek ? 96 : 224);   // (tuning knob: scripts/ba_chain_kernels.py)
-            sd.cpw = uh_div_up(chunks, gmax); sd.G = uh_div_up(chunks, sd.cpw);
-            sd.SP = 0; sd.nown = 0;
-            if (widek) {   // tile list cut over SP workgroups of at most 80 tiles, 4 waves x nown tiles each (kernel instantiations: 12, 16, 20)
-                sd.SP = uh_div_up(sd.T, 80);
-                const int need = uh_div_up(uh_div_up(sd.T, sd.SP), 4);
-                sd.nown = need <= 12 ? 12 : (need <= 16 ? 16 : 20);
-            }
-            b->nsplit = 1;
+        std::vector<size_t> fill(key_count.begin(), key_count.end() - 1);
+        for (int pt = 0; pt < P; pt++) {
+            const auto& obs = obs_of[pt];
+            for (size_t i = 0; i < obs.size(); i++)
+                for (size_t j = i; j < obs.size(); j++) {
+                    const size_t at = fill[(size_t)obs[i].first * nfree + obs[j].first]++;
+                    w.tri_pt[at] = pt; w.tri_e1[at] = obs[i].second; w.tri_e2[at] = obs[j].second;
+                }
         }
     }
-    const size_t o_dpart = A.take<double>(b->dense ? (size_t)b->sd.G * b->sd.T * 256 : 1), o_dbpart = A.take<double>(b->dense ? (size_t)b->sd.G * 16 * b->sd.ntt : 1);
-    const size_t o_S = A.take<double>((size_t)(d.n + 1) * (d.n + 1)), o_Sp = A.take<double>(wide ? 42 : (size_t)b->nsplit * std::max(npairs_h, 1) * 42), o_xp = A.take<double>(std::max(d.n, 1));
-    const size_t wn_pairs = w_pair_s1.size(), wn_items = w_item_pair.size(), wn_tri = w_tri_pt.size();
-    const size_t o_wps1 = A.take<int>(wn_pairs + 1), o_wps2 = A.take<int>(wn_pairs + 1), o_wpip = A.take<int>(wn_pairs + 2);
-    const size_t o_wip = A.take<int>(wn_items + 1), o_wib = A.take<int>(wn_items + 1), o_wic = A.take<int>(wn_items + 1);
-    const size_t o_wtp = A.take<int>(wn_tri + 1), o_wt1 = A.take<int>(wn_tri + 1), o_wt2 = A.take<int>(wn_tri + 1);
-    const size_t o_wpart = A.take<double>((wn_items + 1) * 42), o_wY = A.take<double>(wide ? (size_t)(d.n + 1) * kWNB : 1), o_wfail = A.take<int>(4);
-    const size_t o_plc = A.take<double>(d.nPointBlocks), o_pmd = A.take<double>(d.nPointBlocks), o_pc = A.take<double>(d.nPointBlocks), o_ps = A.take<double>(d.nPointBlocks);
-    const size_t o_st = A.take<BAState>(2), o_clk = A.take<long long>(64);
-    int rc = b->arena.reserve(A.off + 256);
-    if (rc) return rc;
-    UH_HIP_CHECK(hipSetDevice(b->ctx->device));
-    hipStream_t st = b->ctx->stream;
-    char* base = b->arena.as<char>();
-    // The constant arrays of the problem form one contiguous prefix of the arena ([o_pt_ptr, end of pts0)): they are gathered in a pinned
-    // mirror of that prefix and leave as ONE asynchronous copy (fourteen pageable copies were fourteen staged, synchronous transfers:
-    // 0.40 ms of setParams at 48 000 observations).  The wide form's pair / triple lists (up to hundreds of MB) keep their direct copies.
-    const size_t prefix_bytes = o_pts0 + 3 * (size_t)P * sizeof(double);
-    if (b->up_in_flight) { UH_HIP_CHECK(hipEventSynchronize(b->ev_up)); b->up_in_flight = false; }
-    if ((rc = b->up_pin.reserve(prefix_bytes + 256))) return rc;
-    if (!b->ev_up) UH_HIP_CHECK(hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming));
-    char* hp = b->up_pin.as<char>();
-    auto up = [&](size_t off, const void* src, size_t bytes) -> int {
-        if (!bytes) return UH_OK;
-        if (off + bytes <= prefix_bytes) std::memcpy(hp + off, src, bytes);
+    std::vector<char> have_diag(std::max(nfree, 1), 0);
+    auto add_pair = [&](int s1, int s2, int begin, int count) {
+        w.pair_s1.push_back(s1); w.pair_s2.push_back(s2); w.pair_item_ptr.push_back((int)w.item_pair.size());
+        for (int o = 0; o < count; o += kThreads) { w.item_pair.push_back((int)w.pair_s1.size() - 1); w.item_begin.push_back(begin + o); w.item_count.push_back(std::min(kThreads, count - o)); }
+        if (s1 == s2) have_diag[s1] = 1;
+    };
+    for (int s1 = 0; s1 < nfree; s1++)
+        for (int s2 = s1; s2 < nfree; s2++) {
+            const size_t k = (size_t)s1 * nfree + s2;
+            if (key_count[k + 1] > key_count[k]) add_pair(s1, s2, (int)key_count[k], (int)(key_count[k + 1] - key_count[k]));
+        }
+    for (int sfree = 0; sfree < nfree; sfree++) if (!have_diag[sfree]) add_pair(sfree, sfree, 0, 0);   // a camera without landmarks still owns its diagonal block
+    w.pair_item_ptr.push_back((int)w.item_pair.size());
+    return UH_OK;
+}
+
+// Part 3, the fp64 snapshot of the map (it may change after setParams)
+struct BASnapshot { std::vector<double> pose0, pts0, intr, uv, w; };
+static void build_snapshot(const uh_ba_problem* pr, BASnapshot& s) {
+    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
+    s.pose0.resize(7 * (size_t)K); s.intr.resize(4 * (size_t)K); s.pts0.resize(3 * (size_t)P); s.uv.resize(2 * (size_t)E); s.w.resize(E);
+    for (int k = 0; k < K; k++) snapshot_frame(pr->poses_f2g + 16 * k, pr->intr + 4 * k, &s.pose0[7 * k], &s.intr[4 * k]);
+    for (size_t i = 0; i < s.pts0.size(); i++) s.pts0[i] = pr->points[i];
+    for (int e = 0; e < E; e++) { s.uv[2 * e] = pr->obs_uv[2 * e]; s.uv[2 * e + 1] = pr->obs_uv[2 * e + 1]; s.w[e] = pr->obs_inv_sigma[e]; }
+}
+
+// Part 4, the arena.  carve_arena names every array once: the carver hands out its place (256-byte aligned, in the order asked for),
+// sets the device pointer and sends the host array there.  The constant arrays of the problem form one contiguous prefix of the arena
+// (everything up to end_prefix()): they are gathered in a pinned mirror of that prefix and leave as ONE asynchronous copy (fourteen
+// pageable copies were fourteen staged, synchronous transfers: 0.40 ms of setParams at 48 000 observations); an array behind the prefix
+// — the wide form's pair / triple lists, up to hundreds of MB — is copied directly.  The sequence runs twice: dry for the sizes (nothing
+// is written), then on the reserved arena.
+struct ArenaCarver {
+    bool dry = true;
+    char* base = nullptr; char* pin = nullptr; hipStream_t st = nullptr;
+    size_t prefix = 0;
+    uh::Layout A;
+    int rc = UH_OK;
+    int send(size_t off, const void* src, size_t bytes) {
+        if (off + bytes <= prefix) std::memcpy(pin + off, src, bytes);
         else UH_HIP_CHECK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, st));
         return UH_OK;
-    };
-    if ((rc = up(o_pt_ptr, pt_ptr.data(), pt_ptr.size() * 4))) return rc;
-    if ((rc = up(o_pt_edges, pt_edges.data(), pt_edges.size() * 4))) return rc;
-    if ((rc = up(o_cam_ptr, cam_ptr.data(), cam_ptr.size() * 4))) return rc;
-    if ((rc = up(o_cam_edges, cam_edges.data(), cam_edges.size() * 4))) return rc;
-    if ((rc = up(o_e_pt, pr->obs_point, (size_t)E * 4))) return rc;
-    if ((rc = up(o_e_kf, pr->obs_frame, (size_t)E * 4))) return rc;
-    if ((rc = up(o_uv, uv.data(), uv.size() * 8))) return rc;
-    if ((rc = up(o_w, w.data(), w.size() * 8))) return rc;
-    if ((rc = up(o_slot, slot.data(), slot.size() * 4))) return rc;
-    if ((rc = up(o_free, free_kf.data(), free_kf.size() * 4))) return rc;
-    if ((rc = up(o_intr, intr.data(), intr.size() * 8))) return rc;
-    if ((rc = up(o_edge_of, edge_of.data(), edge_of.size() * 4))) return rc;
-    if (wide) {
-        if ((rc = up(o_wps1, w_pair_s1.data(), wn_pairs * 4))) return rc;
-        if ((rc = up(o_wps2, w_pair_s2.data(), wn_pairs * 4))) return rc;
-        if ((rc = up(o_wpip, w_pair_item_ptr.data(), (wn_pairs + 1) * 4))) return rc;
-        if ((rc = up(o_wip, w_item_pair.data(), wn_items * 4))) return rc;
-        if ((rc = up(o_wib, w_item_begin.data(), wn_items * 4))) return rc;
-        if ((rc = up(o_wic, w_item_count.data(), wn_items * 4))) return rc;
-        if ((rc = up(o_wtp, w_tri_pt.data(), wn_tri * 4))) return rc;
-        if ((rc = up(o_wt1, w_tri_e1.data(), wn_tri * 4))) return rc;
-        if ((rc = up(o_wt2, w_tri_e2.data(), wn_tri * 4))) return rc;
     }
-    if (sin) {
-        if ((rc = up(o_ur, sin->ur.data(), (size_t)E * 8))) return rc;
-        if ((rc = up(o_bf, sin->bf.data(), (size_t)E * 8))) return rc;
-        if ((rc = up(o_est, sin->st.data(), (size_t)E))) return rc;
+    template <typename T, typename S = T> void arr(T*& dst, size_t count, const S* src = nullptr, size_t n_src = 0) {
+        static_assert(sizeof(S) == sizeof(T), "element size");
+        const size_t off = A.take<T>(count);
+        if (dry) return;
+        dst = reinterpret_cast<T*>(base + off);
+        if (src && n_src && rc == UH_OK) rc = send(off, src, n_src * sizeof(S));
     }
-    if ((rc = up(o_pose0, pose0.data(), pose0.size() * 8))) return rc;
-    if ((rc = up(o_pts0, pts0.data(), pts0.size() * 8))) return rc;
+    template <typename T, typename S> void arr(T*& dst, size_t count, const std::vector<S>& src) { arr(dst, count, src.data(), src.size()); }
+    void end_prefix() { if (dry) prefix = A.off; }
+};
+struct ArenaTables { BAPtrs p{}; BAWide W{}; BAStereo sx{}; double* pose0 = nullptr; double* pts0 = nullptr; };   // what the carve sets: handed to the optimiser once setParams has succeeded
+static void carve_arena(ArenaCarver& c, ArenaTables& t, const BADims& d, const BAPlan& pl, const uh_ba_problem* pr, const BAGraph& g, const WideLists& wl, const BASnapshot& s, const StereoIn* sin) {
+    const size_t K = d.K, P = d.P, E = d.E, nfree1 = std::max(d.nfree, 1), n1 = std::max(d.n, 1), npairs1 = std::max(d.nfree * (d.nfree + 1) / 2, 1);
+    const bool wide = pl.form == kFormWide, dense = pl.schur != kSchurPair;
+    BAPtrs& p = t.p;
+    BAWide& W = t.W;
+    c.arr(p.pt_ptr, P + 1, g.pt_ptr); c.arr(p.pt_edges, E, g.pt_edges); c.arr(p.cam_ptr, d.nfree + 1, g.cam_ptr); c.arr(p.cam_edges, g.cam_edges.size(), g.cam_edges);
+    c.arr(p.e_pt, E, pr->obs_point, E); c.arr(p.e_kf, E, pr->obs_frame, E); c.arr(p.e_uv, 2 * E, s.uv); c.arr(p.e_w, E, s.w);
+    c.arr(p.slot, K, g.slot); c.arr(p.free_kf, nfree1, g.free_kf); c.arr(p.intr, 4 * K, s.intr); c.arr(p.edge_of, g.edge_of.size(), g.edge_of);
+    if (sin) { c.arr(t.sx.e_ur, E, sin->ur); c.arr(t.sx.e_bf, E, sin->bf); c.arr(t.sx.e_st, E, sin->st); }
+    c.arr(t.pose0, 7 * K, s.pose0); c.arr(t.pts0, 3 * P, s.pts0);
+    c.end_prefix();
+    for (int i = 0; i < 2; i++) { c.arr(p.pose[i], 7 * K); c.arr(p.poseR[i], 12 * K); c.arr(p.pts[i], 3 * P); }
+    c.arr(p.e_active, E); c.arr(p.e_robust, E); c.arr(p.e_err, 2 * E); c.arr(p.e_chi2, E);
+    for (int i = 0; i < 2; i++) { c.arr(p.Hll[i], 9 * P); c.arr(p.bl[i], 3 * P); c.arr(p.Hpl[i], 18 * E); }
+    c.arr(p.HppPart, 27 * (size_t)kCamChunks * nfree1); c.arr(p.bp, n1);
+    c.arr(p.dpart, dense ? (size_t)pl.sd.G * pl.sd.T * 256 : 1); c.arr(p.dbpart, dense ? (size_t)pl.sd.G * 16 * pl.sd.ntt : 1);
+    c.arr(p.S, (size_t)(d.n + 1) * (d.n + 1)); c.arr(p.Spart, wide ? 42 : (size_t)pl.nsplit * npairs1 * 42); c.arr(p.xp, n1);
+    const size_t n_pairs = wl.pair_s1.size(), n_items = wl.item_pair.size(), n_tri = wl.tri_pt.size();
+    c.arr(W.pair_s1, n_pairs + 1, wl.pair_s1); c.arr(W.pair_s2, n_pairs + 1, wl.pair_s2); c.arr(W.pair_item_ptr, n_pairs + 2, wl.pair_item_ptr);
+    c.arr(W.item_pair, n_items + 1, wl.item_pair); c.arr(W.item_begin, n_items + 1, wl.item_begin); c.arr(W.item_count, n_items + 1, wl.item_count);
+    c.arr(W.tri_pt, n_tri + 1, wl.tri_pt); c.arr(W.tri_e1, n_tri + 1, wl.tri_e1); c.arr(W.tri_e2, n_tri + 1, wl.tri_e2);
+    c.arr(W.Wpart, (n_items + 1) * 42); c.arr(W.Y, wide ? (size_t)(d.n + 1) * kWNB : 1); c.arr(W.fail, 4);
+    c.arr(p.part_lin_chi, d.nPointBlocks); c.arr(p.part_maxdiag, d.nPointBlocks); c.arr(p.part_chi, d.nPointBlocks); c.arr(p.part_scale, d.nPointBlocks);
+    c.arr(p.st, 2); c.arr(p.clk, 64);
+    W.n_pairs = (int)n_pairs; W.n_items = (int)n_items; W.ld = d.n + 1; W.S = p.S;
+}
+
+// setParams for the forms that keep host-built tables: the launch chain (more free keyframes than the persistent kernel is
+// instantiated for, or a window whose fixed frames do not fit its LDS) and the wide form (global BA).  Arrays anywhere in host memory.
+// (Plan, pointers and tables of the optimiser change only when everything has succeeded: the residency fallback comes here with a
+// problem set, and one it cannot rebuild stays the persistent problem it was.)
+static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const BAPlan& pl, const StereoIn* sin = nullptr) {
+    b->stereo = false;
+    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
+    const bool wide = pl.form == kFormWide;
+    BAGraph g;
+    WideLists wl;
+    BASnapshot s;
+    int rc = build_graph(pr, wide, g);
+    if (rc) return rc;
+    if (wide && (rc = build_wide_lists(pr, g, wl))) return rc;
+    build_snapshot(pr, s);
+    b->poses_in.assign(pr->poses_f2g, pr->poses_f2g + 16 * (size_t)K);
+    b->fixed.assign(pr->fixed, pr->fixed + K);
+    fill_dims(b, K, P, E, (int)g.free_kf.size());
+    ArenaCarver sizes;
+    ArenaTables t;
+    carve_arena(sizes, t, b->dims, pl, pr, g, wl, s, sin);
+    if ((rc = b->arena.reserve(sizes.A.off + 256))) return rc;
+    UH_HIP_CHECK(hipSetDevice(b->ctx->device));
+    hipStream_t st = b->ctx->stream;
+    if (b->up_in_flight) { UH_HIP_CHECK(hipEventSynchronize(b->ev_up)); b->up_in_flight = false; }
+    if ((rc = b->up_pin.reserve(sizes.prefix + 256))) return rc;
+    if (!b->ev_up) UH_HIP_CHECK(hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming));
+    ArenaCarver c;
+    c.dry = false; c.base = b->arena.as<char>(); c.pin = b->up_pin.as<char>(); c.st = st; c.prefix = sizes.prefix;
+    carve_arena(c, t, b->dims, pl, pr, g, wl, s, sin);
+    if (c.rc) return c.rc;
     if ((rc = b->d_poses_in.reserve(16 * (size_t)K * 4))) return rc;
     if ((rc = b->d_poses_out.reserve(16 * (size_t)K * 4))) return rc;
     if ((rc = b->d_points_out.reserve(std::max<size_t>(3 * (size_t)P * 4, 16)))) return rc;
     if ((rc = b->d_bad.reserve(std::max<size_t>(E, 16)))) return rc;
-    UH_HIP_CHECK(hipMemcpyAsync(base, hp, prefix_bytes, hipMemcpyHostToDevice, st));
+    UH_HIP_CHECK(hipMemcpyAsync(c.base, c.pin, c.prefix, hipMemcpyHostToDevice, st));
     UH_HIP_CHECK(hipEventRecord(b->ev_up, st));
     b->up_in_flight = true;
     UH_HIP_CHECK(hipMemcpyAsync(b->d_poses_in.p, pr->poses_f2g, 16 * (size_t)K * 4, hipMemcpyHostToDevice, st));   // (640 bytes, pageable: staged at once)
-    b->persist = false;
     if (wide) UH_HIP_CHECK(hipStreamSynchronize(st));   // the wide form's host lists die here
-    BAPtrs& p = b->ptrs;
-    p.pt_ptr = (int*)(base + o_pt_ptr); p.pt_edges = (int*)(base + o_pt_edges); p.cam_ptr = (int*)(base + o_cam_ptr); p.cam_edges = (int*)(base + o_cam_edges);
-    p.e_pt = (int*)(base + o_e_pt); p.e_kf = (int*)(base + o_e_kf); p.e_uv = (double*)(base + o_uv); p.e_w = (double*)(base + o_w);
-    p.slot = (int*)(base + o_slot); p.free_kf = (int*)(base + o_free); p.intr = (double*)(base + o_intr); p.edge_of = (int*)(base + o_edge_of);
-    for (int i = 0; i < 2; i++) { p.pose[i] = (double*)(base + o_pose[i]); p.poseR[i] = (double*)(base + o_poseR[i]); p.pts[i] = (double*)(base + o_pts[i]); }
-    p.e_active = (unsigned char*)(base + o_act); p.e_robust = (unsigned char*)(base + o_rob); p.e_err = (double*)(base + o_err); p.e_chi2 = (double*)(base + o_chi2);
-    for (int i = 0; i < 2; i++) { p.Hll[i] = (double*)(base + o_Hll[i]); p.bl[i] = (double*)(base + o_bl[i]); p.Hpl[i] = (double*)(base + o_Hpl[i]); }
-    p.HppPart = (double*)(base + o_Hpp); p.bp = (double*)(base + o_bp);
-    p.S = (double*)(base + o_S); p.Spart = (double*)(base + o_Sp); p.xp = (double*)(base + o_xp);
-    p.dpart = (double*)(base + o_dpart); p.dbpart = (double*)(base + o_dbpart);
-    {
-        BAWide& W = b->wd;
-        W.n_pairs = (int)wn_pairs; W.n_items = (int)wn_items; W.ld = d.n + 1;
-        W.pair_s1 = (const int*)(base + o_wps1); W.pair_s2 = (const int*)(base + o_wps2); W.pair_item_ptr = (const int*)(base + o_wpip);
-        W.item_pair = (const int*)(base + o_wip); W.item_begin = (const int*)(base + o_wib); W.item_count = (const int*)(base + o_wic);
-        W.tri_pt = (const int*)(base + o_wtp); W.tri_e1 = (const int*)(base + o_wt1); W.tri_e2 = (const int*)(base + o_wt2);
-        W.Wpart = (double*)(base + o_wpart); W.S = p.S; W.Y = (double*)(base + o_wY); W.fail = (int*)(base + o_wfail);
-    }
-    p.part_lin_chi = (double*)(base + o_plc); p.part_maxdiag = (double*)(base + o_pmd); p.part_chi = (double*)(base + o_pc); p.part_scale = (double*)(base + o_ps);
-    p.st = (BAState*)(base + o_st);
-    p.clk = (long long*)(base + o_clk);
-    p.stop = nullptr;
     if (b->h_stop) {
         void* dflag = nullptr;
-        if (hipHostGetDevicePointer(&dflag, b->h_stop, 0) == hipSuccess) p.stop = (const volatile unsigned char*)dflag;
+        if (hipHostGetDevicePointer(&dflag, b->h_stop, 0) == hipSuccess) t.p.stop = (const volatile unsigned char*)dflag;
     }
-    b->d_pose0 = (double*)(base + o_pose0);
-    b->d_pts0 = (double*)(base + o_pts0);
+    b->ptrs = t.p; b->wd = t.W; b->d_pose0 = t.pose0; b->d_pts0 = t.pts0;
     if (sin) {
         b->stereo = true;
-        BAStereo& sx = b->sx;
-        sx.e_ur = (const double*)(base + o_ur); sx.e_bf = (const double*)(base + o_bf); sx.e_st = (const unsigned char*)(base + o_est);
-        sx.delta3 = sin->delta3; sx.dsqr3 = sin->delta3 * sin->delta3; sx.chi2_th3 = sin->chi2_th3;
+        b->sx = t.sx;
+        b->sx.delta3 = sin->delta3; b->sx.dsqr3 = sin->delta3 * sin->delta3; b->sx.chi2_th3 = sin->chi2_th3;
     }
+    b->plan = pl;
     b->have_problem = true;
     return UH_OK;
 }
@@ -2949,88 +3062,35 @@ static int ensure_staging(uh_ba* b, int K, int P, int E) {
     return UH_OK;
 }
 
-struct PersistPlan { bool ok; int NF, Lw, G, krows, nelem, SL, max_fix, kfix, lds, nb4, nblk, KS, off_cam; };
-
-template <int NF>
-static int persist_lds_bytes(const PersistPlan& pl, int n) { return persist_lds<NF>(pl.krows, n, pl.max_fix, pl.kfix, pl.off_cam, pl.KS, pl.SL).total_bytes; }
-
-// Which persistent instantiation runs a window of `nfree` free keyframes (0: none): one lane per (landmark, free-camera slot), so the
-// lanes per landmark are the number of free cameras rounded up to 8 or 16.  Beyond 16 the reduced system (6 nfree + 1)^2 doubles and
-// the landmark panel no longer share one workgroup's LDS, and 256 / 32 = 8 landmarks per workgroup would need more workgroups than the
-// chip has compute units: those windows run the launch chain.
-static int persist_lanes(int nfree) {
-    if (const char* e = getenv("UH_BA_NF")) { const int v = atoi(e); if ((v == 8 || v == 16) && nfree <= v) return v; }   // (A/B: force the wider instantiation)
-    return nfree <= 8 ? 8 : (nfree <= 16 ? 16 : 0);
-}
-
 template <int NF>
 static hipError_t persist_grant_lds(int bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_persist_kernel<NF>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-// Does the problem run as ONE persistent launch?  Limits come from the device, not from constants: every workgroup must be resident
-// at once (one per compute unit — their LDS blocks do not fit two to a CU), and its LDS block must fit what the device grants.
-static PersistPlan plan_persistent(uh_ba* b, int K, int P, int E, int nfree) {
-    PersistPlan pl{};
-    const char* form = getenv("UH_BA_FORM");
-    if (form && std::string(form) == "legacy") return pl;
-    if (getenv("UH_BA_WIDE") && atoi(getenv("UH_BA_WIDE")) != 0) return pl;
+// The plan of a problem with the side effects plan_ba leaves to its caller: the residency back-off counts down on every problem that
+// is a candidate for the persistent form, and the persistent kernel is granted its dynamic LDS (once per size class, not per
+// problem; a refusal selects the launch chain instead of failing setParams).
+static BAPlan plan_problem(uh_ba* b, int K, int P, int E, int nfree) {
     void* dflag = nullptr;
-    if (!b->h_stop || hipHostGetDevicePointer(&dflag, b->h_stop, 0) != hipSuccess) return pl;   // (the kernel reports through pinned memory)
-    if (nfree < 1 || P < 1 || E >= (1 << 20) - 1) return pl;
-    if (b->persist_blocked > 0) { --b->persist_blocked; return pl; }
-    const int NF = persist_lanes(nfree);
-    if (!NF) return pl;
-    const int kLwMax = kPThreads / NF;   // one lane per (landmark, free-camera slot)
-    int Lw = std::max(std::min(8, kLwMax), std::min(kLwMax, uh_div_up(P, 64)));
-    if (const char* e = getenv("UH_BA_LW")) Lw = std::max(1, std::min(kLwMax, atoi(e)));
-    const int G = uh_div_up(P, Lw);
-    const int cus = b->ctx->num_cus > 0 ? b->ctx->num_cus : 256;
-    if (G > cus) return pl;
-    const int kfix = K - nfree;
-    if (kfix > 255) return pl;
-    pl.NF = NF; pl.Lw = Lw; pl.G = G; pl.kfix = kfix;
-    pl.max_fix = Lw * kfix;   // bound: every landmark of the tile seen by every fixed frame (nothing is counted on the host)
-    pl.krows = (3 * Lw + 15) & ~15;
-    const int n = 6 * nfree;
-    pl.nb4 = (n + 3) / 4; pl.nblk = pl.nb4 * (pl.nb4 + 1) / 2;
-    pl.off_cam = pl.nblk * 16;   // the product part of a partial: the upper 4 x 4 blocks (vector FMA; the v_mfma_f64 form of rounds 2-4 was slower on gfx950 and is gone: docs/DESIGN_history_r1_r3.md, profiles/r03_mfma_f64.json)
-    pl.nelem = pl.off_cam + NF * 27 + 6 * NF + 4;
-    pl.SL = (uh_div_up(pl.nelem, G) + 1) & ~1;
-    // K-splits of the Schur product: work items = nblk * KS over 256 lanes, each krows / KS rows deep; the splits' partial blocks must
-    // fit the LDS region the reduced system occupies later ((n + 1)^2 doubles)
-    pl.KS = 1;
-    {
-        int best = 1 << 30;
-        for (int ks = 1; ks <= 6; ks++) {
-            if (ks > 1 && ks * pl.off_cam > (n + 1) * (n + 1) + 1452) break;
-            const int rounds = uh_div_up(pl.nblk * ks, kPThreads), depth = (uh_div_up(pl.krows, ks) + 3) & ~3;
-            if (rounds * depth < best) { best = rounds * depth; pl.KS = ks; }
+    BAPlanIn in{K, P, E, nfree, false, false};
+    in.persist_ok = b->h_stop && hipHostGetDevicePointer(&dflag, b->h_stop, 0) == hipSuccess;   // (the kernel reports through pinned memory)
+    BAPlan pl = plan_ba(in, b->knobs, b->lim);
+    if (pl.persist_candidate && b->persist_blocked > 0) { --b->persist_blocked; in.persist_ok = false; pl = plan_ba(in, b->knobs, b->lim); }
+    if (pl.form == kFormPersist) {
+        const int cls = pl.ps.NF == 8 ? 0 : 1;
+        if (pl.ps.lds > b->p_lds_set[cls]) {
+            if ((cls == 0 ? persist_grant_lds<8>(pl.ps.lds) : persist_grant_lds<16>(pl.ps.lds)) == hipSuccess) b->p_lds_set[cls] = pl.ps.lds;
+            else { (void)hipGetLastError(); in.persist_ok = false; pl = plan_ba(in, b->knobs, b->lim); }
         }
     }
-    pl.lds = NF == 8 ? persist_lds_bytes<8>(pl, n) : persist_lds_bytes<16>(pl, n);
-    if (b->max_lds <= 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, b->ctx->device) != hipSuccess || v <= 0) v = 64 * 1024;
-        b->max_lds = v;
-    }
-    if (pl.lds > b->max_lds) return pl;
-    const int cls = NF == 8 ? 0 : 1;
-    if (pl.lds > b->p_lds_set[cls]) {   // once per size class, not per problem; a refusal selects the launch chain instead of failing setParams
-        if ((NF == 8 ? persist_grant_lds<8>(pl.lds) : persist_grant_lds<16>(pl.lds)) != hipSuccess) { (void)hipGetLastError(); return pl; }
-        b->p_lds_set[cls] = pl.lds;
-    }
-    pl.ok = true;
     return pl;
 }
+// ... of a problem that keeps host-built tables whatever its size: three-row edges, or the residency fallback
+static BAPlan plan_tables(const uh_ba* b, int K, int P, int E, int nfree, bool stereo) { return plan_ba(BAPlanIn{K, P, E, nfree, stereo, false}, b->knobs, b->lim); }
 
-// setParams of the persistent form on a filled staging block: header on the host (K-sized), ONE H2D copy, the ingest kernel.
-// No host-built table, no stream synchronisation; every device buffer is kept across problems.
-// pack(e0, e1, as16, exact, oob): writes observation records [e0, e1) (e0 even) into the staging block in the 16- or 24-byte form; clears `exact`
-// when a scalar does not survive the 16-byte form, sets `oob` on an index out of range.  NULL: the records are in the block already (24-byte form
-// unless obs16).  With a packer the records leave in TWO ingest launches, the first running over the host link while the second half is packed.
-// The 16-byte observation records eight at a time where the host has AVX-512 (round 6; the SSE loop below packs two per step): same records,
-// same range test (sign bits of i and n - 1 - i OR-ed over the range), same exactness test of the information scalars.
+// The packers of uh_ba_set_problem: the caller's structure of arrays -> observation records in the staging block.
+// The 16-byte records eight at a time where the host has AVX-512 (round 6; the SSE loop packs two per step): same records, same range
+// test (sign bits of i and n - 1 - i OR-ed over the range), same exactness test of the information scalars.
 // Returns the number of observations packed (a multiple of eight, from e0).
 __attribute__((target("avx512f,avx512vl,avx512dq"))) static int pack_obs16_avx512(const int32_t* pt_, const int32_t* kf_, const float* uv_, const double* w_, int e0, int e1, int P, int K,
                                                                                  unsigned char* ob, bool& exact_out, unsigned& oob) {
@@ -3059,8 +3119,91 @@ __attribute__((target("avx512f,avx512vl,avx512dq"))) static int pack_obs16_avx51
     return i - e0;
 }
 
-using ObsPacker = std::function<void(int, int, bool, bool&, unsigned&)>;
-static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl, bool obs16 = false, const ObsPacker* pack = nullptr, unsigned* oob_out = nullptr) {
+static bool host_has_avx512() {
+    static const bool has = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl") && __builtin_cpu_supports("avx512dq");
+    return has;
+}
+
+// The SSE forms: two observations per step with 128-bit moves (this loop is most of setParams' host time: 26 000 observations, 31 us as
+// scalar code, a third of that this way); indices checked on the way: an index is in range iff neither i nor (n - 1 - i) is negative,
+// the sign bits are OR-ed over the range.  16-byte records {point | frame << 24, u, v, (float)inv_sigma}: clears exact_out when a
+// scalar does not survive the float.
+static void pack_obs16_sse(const int32_t* pt_, const int32_t* kf_, const float* uv_, const double* w_, int e0, int e1, int P, int K,
+                           unsigned char* ob, bool& exact_out, unsigned& oob) {
+    const __m128i pmax = _mm_set1_epi32(P - 1), kmax = _mm_set1_epi32(K - 1);
+    __m128i bad = _mm_setzero_si128();
+    __m128d exact = _mm_castsi128_pd(_mm_set1_epi32(-1));
+    int i = e0;
+    unsigned char* dst = ob + 16 * (size_t)i;
+    for (; i + 2 <= e1; i += 2, dst += 32) {
+        const __m128i pt = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(pt_ + i));
+        const __m128i kf = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(kf_ + i));
+        const __m128 uv = _mm_loadu_ps(uv_ + 2 * i);
+        const __m128d w = _mm_loadu_pd(w_ + i);
+        bad = _mm_or_si128(bad, _mm_or_si128(_mm_or_si128(pt, _mm_sub_epi32(pmax, pt)), _mm_or_si128(kf, _mm_sub_epi32(kmax, kf))));
+        const __m128 wf = _mm_cvtpd_ps(w);                                                  // w0f w1f 0 0
+        exact = _mm_and_pd(exact, _mm_cmpeq_pd(_mm_cvtps_pd(wf), w));
+        const __m128i pk = _mm_or_si128(pt, _mm_slli_epi32(kf, 24));                          // p0 p1 0 0
+        const __m128 a = _mm_castsi128_ps(_mm_unpacklo_epi32(pk, _mm_castps_si128(wf)));     // p0 w0 p1 w1
+        const __m128i r0 = _mm_shuffle_epi32(_mm_castps_si128(_mm_shuffle_ps(a, uv, _MM_SHUFFLE(1, 0, 1, 0))), _MM_SHUFFLE(1, 3, 2, 0));   // p0 u0 v0 w0
+        const __m128i r1 = _mm_shuffle_epi32(_mm_castps_si128(_mm_shuffle_ps(a, uv, _MM_SHUFFLE(3, 2, 3, 2))), _MM_SHUFFLE(1, 3, 2, 0));   // p1 u1 v1 w1
+        _mm_storeu_si128(reinterpret_cast<__m128i*>(dst), r0);
+        _mm_storeu_si128(reinterpret_cast<__m128i*>(dst + 16), r1);
+    }
+    bool ok = _mm_movemask_pd(exact) == 3;
+    oob |= (unsigned)_mm_movemask_ps(_mm_castsi128_ps(bad)) & 3u;
+    for (; i < e1; i++, dst += 16) {
+        const int pt = pt_[i], kf = kf_[i];
+        oob |= (unsigned)((unsigned)pt >= (unsigned)P) | (unsigned)((unsigned)kf >= (unsigned)K);
+        const float wf = (float)w_[i];
+        ok = ok && (double)wf == w_[i];
+        const unsigned pk = ((unsigned)pt & 0xFFFFFFu) | ((unsigned)kf << 24);
+        std::memcpy(dst, &pk, 4); std::memcpy(dst + 4, uv_ + 2 * i, 8); std::memcpy(dst + 12, &wf, 4);
+    }
+    if (!ok) exact_out = false;
+}
+static void pack_obs24_sse(const int32_t* pt_, const int32_t* kf_, const float* uv_, const double* w_, int e0, int e1, int P, int K, uh_ba_obs* ob, unsigned& oob) {
+    const __m128i pmax = _mm_set1_epi32(P - 1), kmax = _mm_set1_epi32(K - 1);
+    __m128i bad = _mm_setzero_si128();
+    int i = e0;
+    unsigned char* dst = reinterpret_cast<unsigned char*>(ob) + 24 * (size_t)e0;
+    for (; i + 2 <= e1; i += 2, dst += 48) {
+        const __m128i pt = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(pt_ + i));
+        const __m128i kf = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(kf_ + i));
+        const __m128i uv = _mm_loadu_si128(reinterpret_cast<const __m128i*>(uv_ + 2 * i));
+        const __m128i w = _mm_loadu_si128(reinterpret_cast<const __m128i*>(w_ + i));
+        bad = _mm_or_si128(bad, _mm_or_si128(_mm_or_si128(pt, _mm_sub_epi32(pmax, pt)), _mm_or_si128(kf, _mm_sub_epi32(kmax, kf))));
+        const __m128i pk = _mm_unpacklo_epi32(pt, kf);                                            // pt0 kf0 pt1 kf1
+        _mm_storeu_si128(reinterpret_cast<__m128i*>(dst), _mm_unpacklo_epi64(pk, uv));           // pt0 kf0 u0 v0
+        _mm_storel_epi64(reinterpret_cast<__m128i*>(dst + 16), w);                               // w0
+        _mm_storeu_si128(reinterpret_cast<__m128i*>(dst + 24), _mm_unpackhi_epi64(pk, uv));      // pt1 kf1 u1 v1
+        _mm_storel_epi64(reinterpret_cast<__m128i*>(dst + 40), _mm_unpackhi_epi64(w, w));        // w1
+    }
+    oob |= (unsigned)_mm_movemask_ps(_mm_castsi128_ps(bad)) & 3u;   // (lanes 0, 1 hold the two observations; 2, 3 were zero-filled loads)
+    for (; i < e1; i++) {
+        const int pt = pt_[i], kf = kf_[i];
+        oob |= (unsigned)((unsigned)pt >= (unsigned)P) | (unsigned)((unsigned)kf >= (unsigned)K);
+        ob[i].point = pt; ob[i].frame = kf; ob[i].u = uv_[2 * i]; ob[i].v = uv_[2 * i + 1]; ob[i].inv_sigma = w_[i];
+    }
+}
+// structure of arrays -> records [e0, e1) (e0 even) of the staging block, in the 16- or 24-byte form
+static void pack_obs(const uh_ba_problem* pr, int e0, int e1, bool as16, bool avx512, uh_ba_obs* ob, bool& exact, unsigned& oob) {
+    const int P = pr->n_points, K = pr->n_frames;
+    if (!as16) return pack_obs24_sse(pr->obs_point, pr->obs_frame, pr->obs_uv, pr->obs_inv_sigma, e0, e1, P, K, ob, oob);
+    unsigned char* ob16 = reinterpret_cast<unsigned char*>(ob);
+    if (avx512) e0 += pack_obs16_avx512(pr->obs_point, pr->obs_frame, pr->obs_uv, pr->obs_inv_sigma, e0, e1, P, K, ob16, exact, oob);
+    pack_obs16_sse(pr->obs_point, pr->obs_frame, pr->obs_uv, pr->obs_inv_sigma, e0, e1, P, K, ob16, exact, oob);
+}
+
+// setParams of the persistent form on a filled staging block: header on the host (K-sized), the ingest kernel (it fetches the block
+// over the host link itself).  No host-built table, no stream synchronisation, no heap allocation; every device buffer is kept across
+// problems.  src: the caller's arrays, whose observations are packed into the block here (16-byte records when try16 and every scalar
+// survives them; an index out of range sets *oob_out) — the records then leave in TWO ingest launches, the first running over the host
+// link while the second half is packed.  NULL: the records are in the block already, in the 24-byte form.
+static int set_problem_fast(uh_ba* b, int K, int P, int E, const BAPlan& plan, const uh_ba_problem* src = nullptr, bool try16 = false, unsigned* oob_out = nullptr) {
+    const PersistPlan& pl = plan.ps;
+    const BAKnobs& kn = b->knobs;
+    bool obs16 = try16;
     const StageLayout& L = b->slay;
     unsigned char* hs = b->h_stage;
     const float* poses = reinterpret_cast<const float*>(hs + L.poses_in);
@@ -3069,24 +3212,11 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
     double* pose0 = reinterpret_cast<double*>(hs + L.pose0); double* R0 = reinterpret_cast<double*>(hs + L.poseR0);
     double* intr = reinterpret_cast<double*>(hs + L.intr);
     int* slot = reinterpret_cast<int*>(hs + L.slot); int* free_kf = reinterpret_cast<int*>(hs + L.free_kf); int* fix_kf = reinterpret_cast<int*>(hs + L.fix_kf);
+    uh_ba_obs* ob = reinterpret_cast<uh_ba_obs*>(hs + L.obs);
     int nfree = 0, nfix = 0;
-    for (int k = 0; k < K; k++) {   // toSE3Quat (globaloptimizer_g2o.cpp:80-90): float 4x4 -> double R,t -> quaternion
+    for (int k = 0; k < K; k++) {
         if (!fixed[k]) { slot[k] = nfree; free_kf[nfree++] = k; } else { slot[k] = -1; fix_kf[nfix++] = k; }
-        const float* M = poses + 16 * k;
-        const double R[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
-        double* qq = pose0 + 7 * k;
-        quat_from_R_host(R, qq);
-        qq[4] = M[3]; qq[5] = M[7]; qq[6] = M[11];
-        for (int j = 0; j < 4; j++) intr[4 * k + j] = intr_f[4 * k + j];
-        double* Rk = R0 + 12 * k;   // R | t of the snapshot, from the normalised quaternion like the launch chain's init kernel
-        const double tx = 2 * qq[0], ty = 2 * qq[1], tz = 2 * qq[2];
-        const double twx = tx * qq[3], twy = ty * qq[3], twz = tz * qq[3];
-        const double txx = tx * qq[0], txy = ty * qq[0], txz = tz * qq[0];
-        const double tyy = ty * qq[1], tyz = tz * qq[1], tzz = tz * qq[2];
-        Rk[0] = 1 - (tyy + tzz); Rk[1] = txy - twz; Rk[2] = txz + twy;
-        Rk[3] = txy + twz; Rk[4] = 1 - (txx + tzz); Rk[5] = tyz - twx;
-        Rk[6] = txz - twy; Rk[7] = tyz + twx; Rk[8] = 1 - (txx + tyy);
-        Rk[9] = qq[4]; Rk[10] = qq[5]; Rk[11] = qq[6];
+        snapshot_frame(poses + 16 * k, intr_f + 4 * k, pose0 + 7 * k, intr + 4 * k, R0 + 12 * k);
     }
     UH_HIP_CHECK(hipSetDevice(b->ctx->device));
     hipStream_t st = b->ctx->stream;
@@ -3133,28 +3263,28 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
             UH_LAUNCH(b->ctx, ba_ingest_direct_kernel, dim3((head ? head_blocks : 0) + uh_div_up(std::max(e1 - e0, 1), 256)), dim3(256), 0, static_cast<const unsigned char*>(d_hs),
                       reinterpret_cast<unsigned char*>(db), L.obs, L.obs, e1, P, K, b->dT.as<unsigned>(), seq, d_err, head ? head_blocks : 0, as16 ? 1 : 0, e0);
         };
-        if (!pack) ingest(true, 0, E, obs16, tseq);
+        if (!src) ingest(true, 0, E, obs16, tseq);
         else {
             // two halves: the first half's records cross the host link (~25 GB/s: 10 us) while the host packs the second (round 5; one launch
             // behind the whole packing loop put its 21 us in front of the optimisation)
             static const int split_env = [] { const char* e = getenv("UH_BA_INGEST_SPLIT"); return e ? atoi(e) : -1; }();   // (A/B knob: 0 one launch, 1 two halves)
             // round 6: with the AVX-512 packer the whole loop is ~4 us — less than the second launch costs (two half transfers are latency-bound,
             // 13 us each; one is 20) — so the records go out in ONE launch there (step 0.4395 -> 0.4365 ms); the SSE packer keeps the halves
-            static const bool has_avx512 = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl") && __builtin_cpu_supports("avx512dq");
-            const bool split = split_env >= 0 ? split_env != 0 : !(has_avx512 && !getenv("UH_BA_NO_AVX512"));
+            const bool avx512 = host_has_avx512() && !kn.no_avx512;
+            const bool split = split_env >= 0 ? split_env != 0 : !avx512;
             const int mid = (split && E >= 4096) ? (E / 2) & ~1 : E;
             bool exact = true;
             unsigned oob = 0;
-            (*pack)(0, mid, obs16, exact, oob);
-            if (obs16 && !exact) { obs16 = false; exact = true; (*pack)(0, mid, false, exact, oob); }
+            pack_obs(src, 0, mid, obs16, avx512, ob, exact, oob);
+            if (obs16 && !exact) { obs16 = false; exact = true; pack_obs(src, 0, mid, false, avx512, ob, exact, oob); }
             if (!oob) ingest(true, 0, mid, obs16, tseq);
             if (mid < E && !oob) {
-                (*pack)(mid, E, obs16, exact, oob);
+                pack_obs(src, mid, E, obs16, avx512, ob, exact, oob);
                 if (obs16 && !exact) {   // the second half does not fit the 16-byte form: everything again as 24-byte records, under a new table sequence
                     obs16 = false; exact = true;
                     UH_HIP_CHECK(hipStreamSynchronize(st));   // (the first half's launch still reads the 16-byte records this pass overwrites; rare path)
                     h_err[0] = 0; h_err[1] = 0;
-                    (*pack)(0, E, false, exact, oob);
+                    pack_obs(src, 0, E, false, avx512, ob, exact, oob);
                     if ((b->tseq & 0xFFFu) == 0xFFFu) { UH_HIP_CHECK(hipMemsetAsync(b->dT.p, 0, b->dT.cap, st)); b->tseq = 0; }
                     ++b->tseq;
                     tseq = (b->tseq & 0xFFFu) << 20;
@@ -3169,10 +3299,7 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
     b->stage_in_flight = true;
     UH_HIP_CHECK(hipGetLastError());
     // ---- kernel arguments
-    BADims& d = b->dims;
-    d.K = K; d.P = P; d.E = E; d.nfree = nfree; d.n = 6 * nfree;
-    d.nPointBlocks = std::max(uh_div_up(P, kPointsPerBlock), 1);
-    d.delta = b->params.huber_delta; d.dsqr = d.delta * d.delta; d.chi2_th = b->params.chi2_threshold;
+    fill_dims(b, K, P, E, nfree);
     BAPtrs& p = b->ptrs;
     p = BAPtrs{};
     p.slot = reinterpret_cast<const int*>(db + L.slot); p.free_kf = reinterpret_cast<const int*>(db + L.free_kf); p.intr = reinterpret_cast<const double*>(db + L.intr);
@@ -3182,7 +3309,7 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
     BAPersist& q = b->pq;
     q = BAPersist{};
     q.G = pl.G; q.Lw = pl.Lw; q.krows = pl.krows; q.SL = pl.SL; q.nelem = pl.nelem; q.max_fix = pl.max_fix; q.kfix = pl.kfix;
-    { const char* e = getenv("UH_BA_SPEC"); q.speculate = e && e[0] == '0' ? 0 : 1; }   // (read per launch: the A/B scripts and a test switch it within one process)
+    q.speculate = kn.spec ? 1 : 0;
     q.nb4 = pl.nb4; q.nblk = pl.nblk; q.KS = pl.KS;
     q.T = b->dT.as<unsigned>(); q.tseq = tseq;
     q.obs16 = obs16 ? 1 : 0;
@@ -3203,8 +3330,7 @@ static int set_problem_fast(uh_ba* b, int K, int P, int E, const PersistPlan& pl
     q.r_poses = reinterpret_cast<float*>(rb + R.poses); q.r_state = reinterpret_cast<double*>(rb + R.state); q.r_points = reinterpret_cast<float*>(rb + R.points);
     q.r_chi2 = reinterpret_cast<double*>(rb + R.chi2); q.r_bad = rb + R.bad;
     q.done_ctr = reinterpret_cast<unsigned*>(b->dscratch.as<char>() + 768);
-    b->p_lds = pl.lds; b->p_nf = pl.NF;
-    b->persist = true; b->wide = false; b->fast = true;
+    b->plan = plan;
     b->have_problem = true;
     return UH_OK;
 }
@@ -3262,14 +3388,18 @@ static int staged_problem_to_tables(uh_ba* b, int K, int P, int E, bool obs16, c
     pr.poses_f2g = reinterpret_cast<const float*>(b->h_stage + L.poses_in); pr.fixed = b->h_stage + L.fixed; pr.intr = reinterpret_cast<const float*>(b->h_stage + L.intr_f);
     pr.points = reinterpret_cast<const float*>(b->h_stage + L.points);
     pr.obs_point = op.data(); pr.obs_frame = of.data(); pr.obs_uv = uv.data(); pr.obs_inv_sigma = w.data();
-    if (!obs_depth) return set_problem_tables(b, &pr);
+    int nfree = 0;
+    for (int k = 0; k < K; k++) nfree += pr.fixed[k] ? 0 : 1;
+    const BAPlan pl = plan_tables(b, K, P, E, nfree, obs_depth != nullptr);
+    if (!obs_depth) return set_problem_tables(b, &pr, pl);
     StereoIn sin;
     const int rc = stereo_edges(&pr, obs_depth, frame_bl, huber_delta_3d, chi2_threshold_3d, "uh_ba_set_problem_staged_stereo", sin);
     if (rc) return rc;
-    return set_problem_tables(b, &pr, &sin);
+    return set_problem_tables(b, &pr, pl, &sin);
 }
 
 static void set_problem_begin(uh_ba* b, const uh_ba_params* params) {
+    b->knobs = read_knobs();
     b->have_problem = false;
     b->optimized = false;
     b->stereo = false;
@@ -3305,8 +3435,8 @@ int uh_ba_set_problem(uh_ba* b, const uh_ba_problem* pr, const uh_ba_params* par
     if (rc) return rc;
     int nfree = 0;
     for (int k = 0; k < K; k++) nfree += pr->fixed[k] ? 0 : 1;
-    const PersistPlan pl = plan_persistent(b, K, P, E, nfree);
-    if (!pl.ok) return set_problem_tables(b, pr);
+    const BAPlan pl = plan_problem(b, K, P, E, nfree);
+    if (pl.form != kFormPersist) return set_problem_tables(b, pr, pl);
     rc = ensure_staging(b, K, P, E);
     if (rc) return rc;
     const StageLayout& L = b->slay;
@@ -3314,74 +3444,12 @@ int uh_ba_set_problem(uh_ba* b, const uh_ba_problem* pr, const uh_ba_params* par
     std::memcpy(b->h_stage + L.fixed, pr->fixed, K);
     std::memcpy(b->h_stage + L.intr_f, pr->intr, 4 * (size_t)K * sizeof(float));
     if (P) std::memcpy(b->h_stage + L.points, pr->points, 3 * (size_t)P * sizeof(float));
-    uh_ba_obs* ob = reinterpret_cast<uh_ba_obs*>(b->h_stage + L.obs);
     // The ingest kernel's time is the bytes it fetches over the host link (~25 GB/s): when every information scalar is float-exact — the
     // reference's always are, (double)(float)(1. / scaleFactor) — and the indices fit 24 + 8 bits, the records go out as 16 bytes
     // {point | frame << 24, u, v, (float)inv_sigma} instead of 24.  Tried first; an inexact scalar falls through to the 24-byte form.
-    const bool try16 = K <= 256 && P < (1 << 24) && !(getenv("UH_BA_OBS24") && atoi(getenv("UH_BA_OBS24")));
-    // structure of arrays -> records [e0, e1) (e0 even), two observations per step with 128-bit moves (this loop is most of setParams' host
-    // time: 26 000 observations, 31 us as scalar code, a third of that this way); indices checked on the way: an index is in range
-    // iff neither i nor (n - 1 - i) is negative, the sign bits are OR-ed over the range
-    const ObsPacker pack = [&](int e0, int e1, bool as16, bool& exact_out, unsigned& oob) {
-        const __m128i pmax = _mm_set1_epi32(P - 1), kmax = _mm_set1_epi32(K - 1);
-        __m128i bad = _mm_setzero_si128();
-        int i = e0;
-        if (as16) {
-            static const bool has_avx512 = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl") && __builtin_cpu_supports("avx512dq");
-            if (has_avx512 && !getenv("UH_BA_NO_AVX512"))   // (read per call: a test switches it within one process)
-                i += pack_obs16_avx512(pr->obs_point, pr->obs_frame, pr->obs_uv, pr->obs_inv_sigma, e0, e1, P, K, reinterpret_cast<unsigned char*>(ob), exact_out, oob);
-            __m128d exact = _mm_castsi128_pd(_mm_set1_epi32(-1));
-            unsigned char* dst = reinterpret_cast<unsigned char*>(ob) + 16 * (size_t)i;
-            for (; i + 2 <= e1; i += 2, dst += 32) {
-                const __m128i pt = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(pr->obs_point + i));
-                const __m128i kf = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(pr->obs_frame + i));
-                const __m128 uv = _mm_loadu_ps(pr->obs_uv + 2 * i);
-                const __m128d w = _mm_loadu_pd(pr->obs_inv_sigma + i);
-                bad = _mm_or_si128(bad, _mm_or_si128(_mm_or_si128(pt, _mm_sub_epi32(pmax, pt)), _mm_or_si128(kf, _mm_sub_epi32(kmax, kf))));
-                const __m128 wf = _mm_cvtpd_ps(w);                                                  // w0f w1f 0 0
-                exact = _mm_and_pd(exact, _mm_cmpeq_pd(_mm_cvtps_pd(wf), w));
-                const __m128i pk = _mm_or_si128(pt, _mm_slli_epi32(kf, 24));                          // p0 p1 0 0
-                const __m128 a = _mm_castsi128_ps(_mm_unpacklo_epi32(pk, _mm_castps_si128(wf)));     // p0 w0 p1 w1
-                const __m128i r0 = _mm_shuffle_epi32(_mm_castps_si128(_mm_shuffle_ps(a, uv, _MM_SHUFFLE(1, 0, 1, 0))), _MM_SHUFFLE(1, 3, 2, 0));   // p0 u0 v0 w0
-                const __m128i r1 = _mm_shuffle_epi32(_mm_castps_si128(_mm_shuffle_ps(a, uv, _MM_SHUFFLE(3, 2, 3, 2))), _MM_SHUFFLE(1, 3, 2, 0));   // p1 u1 v1 w1
-                _mm_storeu_si128(reinterpret_cast<__m128i*>(dst), r0);
-                _mm_storeu_si128(reinterpret_cast<__m128i*>(dst + 16), r1);
-            }
-            bool ok = _mm_movemask_pd(exact) == 3;
-            oob |= (unsigned)_mm_movemask_ps(_mm_castsi128_ps(bad)) & 3u;
-            for (; i < e1; i++, dst += 16) {
-                const int pt = pr->obs_point[i], kf = pr->obs_frame[i];
-                oob |= (unsigned)((unsigned)pt >= (unsigned)P) | (unsigned)((unsigned)kf >= (unsigned)K);
-                const float wf = (float)pr->obs_inv_sigma[i];
-                ok = ok && (double)wf == pr->obs_inv_sigma[i];
-                const unsigned pk = ((unsigned)pt & 0xFFFFFFu) | ((unsigned)kf << 24);
-                std::memcpy(dst, &pk, 4); std::memcpy(dst + 4, pr->obs_uv + 2 * i, 8); std::memcpy(dst + 12, &wf, 4);
-            }
-            if (!ok) exact_out = false;
-            return;
-        }
-        unsigned char* dst = reinterpret_cast<unsigned char*>(ob) + 24 * (size_t)e0;
-        for (; i + 2 <= e1; i += 2, dst += 48) {
-            const __m128i pt = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(pr->obs_point + i));
-            const __m128i kf = _mm_loadl_epi64(reinterpret_cast<const __m128i*>(pr->obs_frame + i));
-            const __m128i uv = _mm_loadu_si128(reinterpret_cast<const __m128i*>(pr->obs_uv + 2 * i));
-            const __m128i w = _mm_loadu_si128(reinterpret_cast<const __m128i*>(pr->obs_inv_sigma + i));
-            bad = _mm_or_si128(bad, _mm_or_si128(_mm_or_si128(pt, _mm_sub_epi32(pmax, pt)), _mm_or_si128(kf, _mm_sub_epi32(kmax, kf))));
-            const __m128i pk = _mm_unpacklo_epi32(pt, kf);                                            // pt0 kf0 pt1 kf1
-            _mm_storeu_si128(reinterpret_cast<__m128i*>(dst), _mm_unpacklo_epi64(pk, uv));           // pt0 kf0 u0 v0
-            _mm_storel_epi64(reinterpret_cast<__m128i*>(dst + 16), w);                               // w0
-            _mm_storeu_si128(reinterpret_cast<__m128i*>(dst + 24), _mm_unpackhi_epi64(pk, uv));      // pt1 kf1 u1 v1
-            _mm_storel_epi64(reinterpret_cast<__m128i*>(dst + 40), _mm_unpackhi_epi64(w, w));        // w1
-        }
-        oob |= (unsigned)_mm_movemask_ps(_mm_castsi128_ps(bad)) & 3u;   // (lanes 0, 1 hold the two observations; 2, 3 were zero-filled loads)
-        for (; i < e1; i++) {
-            const int pt = pr->obs_point[i], kf = pr->obs_frame[i];
-            oob |= (unsigned)((unsigned)pt >= (unsigned)P) | (unsigned)((unsigned)kf >= (unsigned)K);
-            ob[i].point = pt; ob[i].frame = kf; ob[i].u = pr->obs_uv[2 * i]; ob[i].v = pr->obs_uv[2 * i + 1]; ob[i].inv_sigma = pr->obs_inv_sigma[i];
-        }
-    };
+    const bool try16 = K <= 256 && P < (1 << 24) && !b->knobs.obs24;
     unsigned oob = 0;
-    rc = set_problem_fast(b, K, P, E, pl, try16, &pack, &oob);
+    rc = set_problem_fast(b, K, P, E, pl, pr, try16, &oob);
     if (oob)   // (an index out of range may not survive the 24 + 8 bit packing: found by the packer, named here)
         for (int e = 0; e < E; e++)
             UH_REQUIRE(pr->obs_point[e] >= 0 && pr->obs_point[e] < P && pr->obs_frame[e] >= 0 && pr->obs_frame[e] < K,
@@ -3420,8 +3488,8 @@ int uh_ba_set_problem_staged(uh_ba* b, int K, int P, int E, const uh_ba_params* 
                        "uh_ba_set_problem: observation %d references point %d / frame %d out of range", e, ob[e].point, ob[e].frame);
     int nfree = 0;
     for (int k = 0; k < K; k++) nfree += fixed[k] ? 0 : 1;
-    const PersistPlan pl = plan_persistent(b, K, P, E, nfree);
-    if (pl.ok) return set_problem_fast(b, K, P, E, pl);
+    const BAPlan pl = plan_problem(b, K, P, E, nfree);
+    if (pl.form == kFormPersist) return set_problem_fast(b, K, P, E, pl);
     // a window the persistent form does not take: hand the launch chain / wide form the arrays it wants
     return staged_problem_to_tables(b, K, P, E, false);
 }
@@ -3443,7 +3511,9 @@ int uh_ba_set_problem_stereo(uh_ba* b, const uh_ba_problem* pr, const uh_ba_ster
         if (rc) return rc;
     }
     if (n_st == 0) return uh_ba_set_problem(b, pr, params);
-    return set_problem_tables(b, pr, &sin);
+    int nfree = 0;
+    for (int k = 0; k < K; k++) nfree += pr->fixed[k] ? 0 : 1;
+    return set_problem_tables(b, pr, plan_tables(b, K, P, E, nfree, true), &sin);
 }
 
 int uh_ba_map_staging_stereo(uh_ba* b, int n_frames, int n_points, int max_obs, uh_ba_staging_stereo* out) {
@@ -3485,8 +3555,8 @@ int uh_ba_want_chi2(uh_ba* b, int on) {
 
 int uh_ba_form(uh_ba* b, int* lanes_out) {
     UH_REQUIRE(b && b->have_problem, "uh_ba_form: no problem set");
-    if (lanes_out) *lanes_out = b->persist ? b->p_nf : 0;
-    return b->wide ? 2 : (b->persist ? 1 : 0);
+    if (lanes_out) *lanes_out = b->plan.form == kFormPersist ? b->plan.ps.NF : 0;
+    return b->plan.form;
 }
 
 // GlobalOptimizer::optimize(bool* stopASAP).  The caller may flip *stop_asap asynchronously; it is sampled into a pinned,
@@ -3501,7 +3571,7 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
     const float mc = b->params.min_chi2_between_iter;
     b->iters[0] = b->iters[1] = 0;
     b->step = 0;
-    if (b->persist) {
+    if (b->plan.form == kFormPersist) {
         const int rcp = run_persistent(b, stop_asap, n1, n2, mc);
         if (rcp != UH_ENODEVICE || !b->h_stage || !b->persist_not_resident) return rcp;
         if (b->problem_stage_gen != b->stage_gen) {   // uh_ba_map_staging was called since set_problem: the block may hold the NEXT keyframe's problem
@@ -3513,7 +3583,8 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
         // kernel holds CUs: INTEGRATION.md section 8).  The problem is still in the staging block: this optimisation and the next 64
         // problems of this object take the launch chain, which needs no co-residency; then the persistent form is tried again.
         const std::string why = uh_last_error();
-        const int rc2 = staged_problem_to_tables(b, d.K, d.P, d.E, b->pq.obs16 != 0);   // (clears b->persist; the parameters stay)
+        b->knobs = read_knobs();   // (the fallback is a setParams of its own, possibly on the worker thread: it reads the knobs when it runs, as ever)
+        const int rc2 = staged_problem_to_tables(b, d.K, d.P, d.E, b->pq.obs16 != 0);   // (plans the chain or the wide form; the parameters stay)
         b->persist_blocked = 64;
         if (rc2 != UH_OK) { uh::set_error("%s; falling back to the launch chain failed too", why.c_str()); return UH_ENODEVICE; }
         return uh_ba_optimize(b, stop_asap);
@@ -3528,9 +3599,7 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
     UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n1, mc, b->step & 1, 0);
     if ((rc = enqueue_steps(b, n1, true))) return rc;
     UH_LAUNCH(b->ctx,ba_gate_kernel, dim3(1), dim3(64), 0, b->ptrs, b->step & 1);
-    if (d.E > 0) UH_LAUNCH_BA(b, ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, 1);
-    UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n2, mc, b->step & 1, 1);
-    if ((rc = enqueue_steps(b, n2, true))) return rc;
+    if ((rc = enqueue_pass2(b, n2, mc, 1, n2))) return rc;
     BAState hs;
     if ((rc = wait_state(b, &hs, stop_asap))) return rc;
     if (hs.gate) {                       // the common case: pass 2 is under way or done
@@ -3544,9 +3613,7 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
         if (stop_asap && *stop_asap) cont = false;
         if (b->h_stop && *b->h_stop) cont = false;
         if (cont) {
-            if (d.E > 0) UH_LAUNCH_BA(b, ba_relabel_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->step & 1, 0);
-            UH_LAUNCH(b->ctx,ba_begin_pass_kernel, dim3(1), dim3(64), 0, b->ptrs, n2, mc, b->step & 1, 0);
-            if ((rc = enqueue_steps(b, n2 + 1, true))) return rc;
+            if ((rc = enqueue_pass2(b, n2, mc, 0, n2 + 1))) return rc;
             if ((rc = wait_state(b, &hs, stop_asap))) return rc;
             if ((rc = finish_pass(b, &hs, stop_asap))) return rc;
             b->iters[1] = hs.iters_done;
@@ -3647,7 +3714,7 @@ uint8_t* uh_ba_stop_flag(uh_ba* b) { return b ? b->h_stop : nullptr; }
 
 int uh_ba_get_results(uh_ba* b, float* poses_out, float* points_out, double* chi2_out, uint8_t* bad_out, int32_t* iters_out) {
     UH_REQUIRE(b && b->have_problem && b->optimized, "uh_ba_get_results: optimize() has not run");
-    if (b->fast) {   // the optimisation kernel's tail has already written everything into the pinned result block
+    if (b->plan.form == kFormPersist) {   // the optimisation kernel's tail has already written everything into the pinned result block
         const BADims& d = b->dims;
         const ResLayout& R = b->rlay;
         if (poses_out) std::memcpy(poses_out, b->h_res + R.poses, 16 * (size_t)d.K * sizeof(float));
@@ -3689,7 +3756,7 @@ int uh_ba_get_results(uh_ba* b, float* poses_out, float* points_out, double* chi
 // final pose state (qx qy qz qw tx ty tz per frame, fp64) — used by the parity tests to state the tolerance on se3
 int uh_ba_get_pose_state(uh_ba* b, double* pose7_out) {
     UH_REQUIRE(b && b->have_problem && b->optimized && pose7_out, "uh_ba_get_pose_state: not ready");
-    if (b->fast) { std::memcpy(pose7_out, b->h_res + b->rlay.state, 7 * (size_t)b->dims.K * sizeof(double)); return UH_OK; }
+    if (b->plan.form == kFormPersist) { std::memcpy(pose7_out, b->h_res + b->rlay.state, 7 * (size_t)b->dims.K * sizeof(double)); return UH_OK; }
     BAState hs;
     UH_HIP_CHECK(hipMemcpyAsync(&hs, b->ptrs.st + (b->step & 1), sizeof(BAState), hipMemcpyDeviceToHost, b->ctx->stream));
     UH_HIP_CHECK(hipStreamSynchronize(b->ctx->stream));
@@ -3702,7 +3769,7 @@ int uh_ba_get_pose_state(uh_ba* b, double* pose7_out) {
 int uh_ba_results_view_get(uh_ba* b, uh_ba_results_view* out) {
     UH_REQUIRE(b && out, "uh_ba_results_view_get: NULL argument");
     UH_REQUIRE(b->have_problem && b->optimized, "uh_ba_results_view_get: optimize() has not run");
-    UH_REQUIRE(b->fast, "uh_ba_results_view_get: the current problem runs in a form that keeps its results in HBM (use uh_ba_get_results)");
+    UH_REQUIRE(b->plan.form == kFormPersist, "uh_ba_results_view_get: the current problem runs in a form that keeps its results in HBM (use uh_ba_get_results)");
     const ResLayout& R = b->rlay;
     out->poses = reinterpret_cast<const float*>(b->h_res + R.poses); out->points = reinterpret_cast<const float*>(b->h_res + R.points);
     out->chi2 = b->pq.want_chi2 ? reinterpret_cast<const double*>(b->h_res + R.chi2) : nullptr; out->bad = b->h_res + R.bad;

@@ -1,7 +1,8 @@
-// Quaternion <-> rotation helpers shared by the solvers (ba.hip, ba_persist.hpp, pnp.hip): fp64, q = (x, y, z, w), R row-major 3x3.
+// Quaternion <-> rotation helpers shared by the solvers (ba.hip, ba_persist.hpp, pnp.hip), kernels and host code alike: fp64, q = (x, y, z, w),
+// R row-major 3x3.
 #pragma once
 
-__device__ __forceinline__ void quat_to_R(const double* q, double* R) {
+__host__ __device__ __forceinline__ void quat_to_R(const double* q, double* R) {
     const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
     const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
     const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
@@ -10,7 +11,7 @@ __device__ __forceinline__ void quat_to_R(const double* q, double* R) {
     R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
 }
-__device__ __forceinline__ void quat_from_R(const double* R, double* q) {   // Eigen::Quaternion(Matrix3)
+__host__ __device__ __forceinline__ void quat_from_R(const double* R, double* q) {   // Eigen::Quaternion(Matrix3)
     double t = R[0] + R[4] + R[8];
     if (t > 0) {
         t = sqrt(t + 1.0);
@@ -31,7 +32,7 @@ __device__ __forceinline__ void quat_from_R(const double* R, double* q) {   // E
         q[3] = (R[3] - R[1]) * t; q[0] = (R[2] + R[6]) * t; q[1] = (R[5] + R[7]) * t;
     }
 }
-__device__ __forceinline__ void quat_norm_pos(double* q) {
+__host__ __device__ __forceinline__ void quat_norm_pos(double* q) {
     if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
     const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
