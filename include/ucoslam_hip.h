@@ -487,6 +487,36 @@ int  uh_ba_map_staging_stereo(uh_ba* ba, int n_frames, int n_points, int max_obs
 int  uh_ba_set_problem_staged_stereo(uh_ba* ba, int n_frames, int n_points, int n_obs, const uh_ba_params* params,
                                      double huber_delta_3d, double chi2_threshold_3d);
 
+/* ---- squared planar markers with free poses (globaloptimizer_g2o.cpp:156-171, 277-352, 451-455, 526-527; MarkerEdge, typesg2o.h:108-167).
+ * Every marker is a free SE3 vertex of the pose part (six parameters, exp(update) * estimate), linked by one eight-row edge to every
+ * frame that sees it: error = und_corners - the projection of the four corners (-+size/2, +-size/2, 0) through c2g * g2m rounded to
+ * float, g2o's numeric central differences (delta = (double)1e-4f) on both vertices, information edge_weight * I8 (the frame's
+ * frame_MarkerWeight, :281-299 — flatten_for_ba_markers computes it), NO robust kernel; the edges are never excluded or flagged and
+ * are the same in both passes; their chi2 is part of the Levenberg decision, the chi2 stop and the lambda initialisation.  A fixed
+ * frame's edge contributes the marker's diagonal block and right-hand side only.
+ * markers == NULL or n_edges == 0: exactly uh_ba_set_problem / uh_ba_set_problem_stereo (stereo != NULL).  Otherwise the problem runs
+ * in the wide form whatever its size (uh_ba_form reports 2), n_points = n_obs = 0 included; optimize / optimize_async / wait /
+ * get_results / get_pose_state / stop flag / want_chi2 work unchanged, uh_ba_results_view_get refuses as for every wide problem.
+ * Refused with UH_EINVAL, nothing launched: a NULL array, edge_marker / edge_frame out of range, a (marker, frame) pair that occurs
+ * twice, a weight or a size that is not finite and > 0, a non-finite pose or corner, more than 4096 free keyframes + markers.
+ * Not covered: the planar constraint between markers (ParamSet::InPlaneMarkers, :355-398), the staged and solve_async routes. */
+typedef struct uh_ba_markers {
+    int32_t n_markers;
+    const float*   pose_g2m;        /* n_markers x 16, row-major 4x4 (Marker::pose_g2m) */
+    const float*   size;            /* n_markers (Marker::size) */
+    int32_t n_edges;
+    const int32_t* edge_marker;     /* n_edges */
+    const int32_t* edge_frame;      /* n_edges: index into the problem's frames */
+    const float*   und_corners;     /* n_edges x 8: x0 y0 .. x3 y3 (MarkerObservation::und_corners) */
+    const double*  edge_weight;     /* n_edges: information = w * I8 */
+} uh_ba_markers;
+int  uh_ba_set_problem_markers(uh_ba* ba, const uh_ba_problem* problem, const uh_ba_stereo* stereo /* or NULL */, const uh_ba_markers* markers,
+                               const uh_ba_params* params);
+/* after optimize: the marker poses as float 4x4 (getResults, :526-527), their fp64 state (qx qy qz qw tx ty tz; may be NULL) and the
+ * chi2 of every marker edge at the final estimate (may be NULL) */
+int  uh_ba_get_marker_results(uh_ba* ba, float* pose_g2m_out /* n_markers x 16 */, double* pose7_out /* n_markers x 7 or NULL */,
+                              double* edge_chi2_out /* n_edges or NULL */);
+
 /* ------------------------------------------------------------------------
  * Bag of words — replaces fbow::Vocabulary::transform / fBow::score:
  *   3rdparty/fbow/fbow/fbow.h:54-116 (class surface), fbow.cpp:51-90 (transform with level), :92-143 (normalised

@@ -222,6 +222,37 @@ class GlobalOptimizer {
         staged_ = true;
         obs_keep_.assign(sink.st.obs, sink.st.obs + index_.n_obs);
     }
+    // setParams on a map with markers (globaloptimizer_g2o.cpp:156-171, 277-352; any mix of monocular and stereo / RGB-D observations):
+    // flatten_for_ba_markers into plain vectors, then uh_ba_set_problem_markers — the wide form; the staging block has no marker form.  The
+    // MapView also needs the marker members listed in flatten_ba.hpp.  A map without markers ends on the marker-free route.
+    template <class MapView>
+    void setParamsMarkers(const MapView& map, const ParamSet& p) {
+        StereoVectorSink flat;
+        MarkerVectorSink mk;
+        index_ = flatten_for_ba_markers(map, p, flat, mk, mindex_);
+        const int E = index_.n_obs;
+        std::vector<int32_t> op(E), of(E);
+        std::vector<float> uv(2 * (size_t)E);
+        std::vector<double> w(E);
+        for (int e = 0; e < E; e++) { op[e] = flat.obs[e].point; of[e] = flat.obs[e].frame; uv[2 * e] = flat.obs[e].u; uv[2 * e + 1] = flat.obs[e].v; w[e] = flat.obs[e].inv_sigma; }
+        const uh_ba_problem pr{(int32_t)index_.frame_of.size(), (int32_t)index_.point_of.size(), E, flat.poses.data(), flat.fixed.data(), flat.intr.data(),
+                               flat.points.data(), op.data(), of.data(), uv.data(), w.data()};
+        const uh_ba_stereo sx{flat.depth.data(), flat.bl.data(), 0.0, 0.0};
+        const uh_ba_markers m = mk.view();
+        uh_ba_params bp{p.nIters, 0.0, 0.0, 1.0f};
+        check(uh_ba_set_problem_markers(b_, &pr, &sx, &m, &bp));
+        staged_ = true;
+        obs_keep_ = flat.obs;
+    }
+    // getResults' marker part (:526-527), after getResults(map): Marker::pose_g2m of the markers setParamsMarkers took
+    template <class MapView>
+    void getMarkerResults(MapView& map) {
+        if (mindex_.marker_of.empty()) return;
+        std::vector<float> poses(16 * mindex_.marker_of.size());
+        check(uh_ba_get_marker_results(b_, poses.data(), nullptr, nullptr));
+        apply_marker_results(map, mindex_, poses.data());
+    }
+    const FlatBAMarkerIndex& marker_index() const { return mindex_; }
     // ... and on flattened arrays with the stereo block beside them
     void setParams(const uh_ba_problem& problem, const uh_ba_stereo& stereo, const ParamSet& p) {
         uh_ba_params bp{p.nIters, 0.0, 0.0, 1.0f};
@@ -276,6 +307,7 @@ class GlobalOptimizer {
     int K_ = 0, P_ = 0;
     bool staged_ = false;
     FlatBAIndex index_;
+    FlatBAMarkerIndex mindex_;
     std::vector<uh_ba_obs> obs_keep_;
     std::vector<std::pair<uint32_t, uint32_t>> bad_;
 };

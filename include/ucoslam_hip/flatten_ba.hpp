@@ -21,10 +21,20 @@
 //             optimiser sees (double)(float)(1. / f).  depth > 0 (stereo / RGB-D observation, :250-) is refused by flatten_for_ba
 //             (the monocular entry) and taken by flatten_for_ba_stereo, which writes the depth per observation and the baseline
 //             (Frame::imageParams.bl) per frame beside the records: the optimiser forms mbf and kp_ur from them (:253-254).
-//   markers (:158-171, :300-398) are refused: marker-less maps only.
+//   markers (:158-171, :300-398) are refused by flatten_for_ba and flatten_for_ba_stereo and taken by flatten_for_ba_markers:
+//   :158-171  a frame that contributes points also contributes its markers, in the order of Frame::markers: a marker not taken yet
+//             whose map pose is valid is taken, and every frame of Marker::frames that is not used yet joins as FIXED_WITHOUTPOINTS
+//   :281-299  frame_MarkerWeight of every used frame: 1, or, when the frame's keypoint weight sum kpw is > 40 and it has markers,
+//             markersOptWeight * min(1, n / minMarkersForMaxWeight) * kpw / (n * 8) with n = frame.markers.size() — which counts the
+//             markers WITHOUT a valid pose too.  kpw adds, per edge of the frame and in edge order, the FLOAT product 2 * f (two rows)
+//             or 3 * f (three rows) of the vector<float> _InvScaleFactors to a double (:248, :271)
+//   :307-352  the taken markers in ascending id (marker_info is a std::map), one edge per frame of Marker::frames in ascending frame
+//             index (a std::set): measurement = that frame's und_corners of the marker, information = frame_MarkerWeight * I8
+//   :355-398  the planar constraint (ParamSet::InPlaneMarkers with at least two valid markers in the map) is refused
 // getResults (:466-537) is apply_results below: poses of the non-fixed used frames, coordinates of the taken points, and the bad
 // associations as (map point id, frame id) pairs.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <set>
 #include <stdexcept>
@@ -44,6 +54,9 @@ struct BAParamSet {
     bool fixFirstFrame = true;
     int nIters = 100;
     bool verbose = false;
+    float markersOptWeight = 0.5f;              // importance of the markers in the final error (flatten_for_ba_markers)
+    int minMarkersForMaxWeight = 5;
+    bool InPlaneMarkers = false;                // refused by flatten_for_ba_markers when the map has at least two valid markers
 };
 
 /* MapView — what flatten_for_ba needs from a map (all const):
@@ -66,6 +79,16 @@ struct BAParamSet {
  *   void     point_coordinates(p, float out[3])
  * and, for apply_results, non-const:
  *   void set_frame_pose_f2g(f, const float m[16]); void set_point_coordinates(p, const float xyz[3]); void update_point_normal_and_distances(p)
+ * flatten_for_ba_markers needs, in addition:
+ *   size_t   frame_n_markers(f)                     Frame::markers.size() (markers without a valid pose included)
+ *   uint32_t frame_marker_id(f, i)                  Frame::markers[i].id
+ *   const float* frame_marker_corners(f, id)        8 floats x0 y0 .. x3 y3: Frame::getMarker(id).und_corners
+ *   template <class F> void for_each_marker(F)      F(uint32_t id) for every marker of map->map_markers
+ *   bool     marker_valid(id)                       Marker::pose_g2m.isValid()
+ *   const float* marker_pose_g2m(id)                16 floats, row-major 4x4
+ *   float    marker_size(id)
+ *   template <class F> void for_each_marker_frame(id, F)   F(uint32_t frame) over Marker::frames in ascending index
+ * and, for apply_marker_results:  void set_marker_pose_g2m(id, const float m[16])
  */
 
 struct FlatBAIndex {                       // what getResults needs to write back
@@ -73,6 +96,14 @@ struct FlatBAIndex {                       // what getResults needs to write bac
     std::vector<uint8_t>  frame_fixed;     // 0 free, 1 FIXED_WITHPOINTS, 2 FIXED_WITHOUTPOINTS
     std::vector<uint32_t> point_of;        // flattened point -> map point id (= usedMapPoints)
     int n_obs = 0;
+};
+
+struct FlatBAMarkerIndex {                 // ... and for the markers
+    std::vector<uint32_t> marker_of;       // flattened marker -> map marker id (ascending)
+    int n_edges = 0;
+};
+struct FlatMarkerArrays {                  // where the walk writes the marker part (MarkerVectorSink::begin)
+    float* pose_g2m; float* size; int32_t* edge_marker; int32_t* edge_frame; float* und_corners; double* edge_weight;
 };
 
 constexpr uint32_t kInvalidIdx = 0xFFFFFFFFu;
@@ -83,9 +114,12 @@ inline float* stereo_depth(uh_ba_staging_stereo& st) { return st.obs_depth; }
 inline float* stereo_bl(uh_ba_staging&) { return nullptr; }
 inline float* stereo_bl(uh_ba_staging_stereo& st) { return st.frame_bl; }
 
-// the walk of both entries; STEREO: the sink's block has obs_depth / frame_bl and observations with depth are taken
-template <bool STEREO, class MapView, class Sink>
-FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
+struct NoMarkerSink {};
+
+// the walk of all entries; STEREO: the sink's block has obs_depth / frame_bl and observations with depth are taken; MARKERS: markers
+// with a valid pose are taken instead of refused, and written to msink with their edges
+template <bool STEREO, bool MARKERS, class MapView, class Sink, class MSink>
+FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink, MSink& msink, FlatBAMarkerIndex* mix) {
     enum : uint8_t { UNFIXED = 0, FIXED_WITHPOINTS = 1, FIXED_WITHOUTPOINTS = 2 };
     const uint32_t FC = map.frame_capacity(), PC = map.point_capacity();
     std::vector<uint8_t> used(FC, 0), fixed(FC, UNFIXED);
@@ -99,6 +133,13 @@ FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
     if (ps.fixFirstFrame) { const uint32_t f0 = map.front_keyframe(); if (f0 < FC && used[f0]) fixed[f0] = FIXED_WITHPOINTS; }
     for (uint32_t f : ps.fixed_frames) if (f < FC && used[f]) fixed[f] = FIXED_WITHPOINTS;
 
+    std::set<uint32_t> taken_markers;      // marker_info's keys: ascending id
+    if constexpr (MARKERS) {
+        int n_valid = 0;
+        map.for_each_marker([&](uint32_t id) { n_valid += map.marker_valid(id) ? 1 : 0; });
+        if (ps.InPlaneMarkers && n_valid >= 2)
+            throw std::runtime_error("flatten_for_ba_markers: the planar constraint between markers (InPlaneMarkers) is not supported by the HIP optimiser");
+    }
     FlatBAIndex ix;
     for (uint32_t f = 0; f < FC; f++) {   // ascending index: frames that join below with a larger index are reached, and skipped
         if (!used[f] || fixed[f] == FIXED_WITHOUTPOINTS) continue;
@@ -116,8 +157,19 @@ FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
                 if (!used[of]) { used[of] = 1; fixed[of] = FIXED_WITHOUTPOINTS; }
             });
         }
-        if (map.frame_has_valid_markers(f))
-            throw std::runtime_error("flatten_for_ba: frame " + std::to_string(f) + " sees markers with a valid pose; the HIP optimiser takes marker-less maps only");
+        if constexpr (MARKERS) {
+            const size_t nm = map.frame_n_markers(f);
+            for (size_t i = 0; i < nm; i++) {
+                const uint32_t id = map.frame_marker_id(f, i);
+                if (taken_markers.count(id) || !map.marker_valid(id)) continue;
+                taken_markers.insert(id);
+                map.for_each_marker_frame(id, [&](uint32_t mf) {
+                    if (mf >= FC || !map.frame_valid(mf)) throw std::runtime_error("flatten_for_ba_markers: marker " + std::to_string(id) + " is seen by a frame that is not in the map");
+                    if (!used[mf]) { used[mf] = 1; fixed[mf] = FIXED_WITHOUTPOINTS; }
+                });
+            }
+        } else if (map.frame_has_valid_markers(f))
+            throw std::runtime_error("flatten_for_ba: frame " + std::to_string(f) + " sees markers with a valid pose; use flatten_for_ba_markers");
     }
     std::vector<int32_t> flat_of(FC, -1);
     for (uint32_t f = 0; f < FC; f++)
@@ -141,6 +193,7 @@ FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
     const std::vector<float>& sf = map.scale_factors();
     std::vector<float> inv_sf(sf.size());
     for (size_t i = 0; i < sf.size(); i++) inv_sf[i] = (float)(1. / sf[i]);
+    std::vector<double> kpw(FC, 0.0);   // frame_kpOptWeight
     int e = 0;
     for (int pi = 0; pi < P; pi++) {
         const uint32_t p = ix.point_of[pi];
@@ -157,7 +210,39 @@ FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
             if (octave < 0 || (size_t)octave >= inv_sf.size()) throw std::runtime_error("flatten_for_ba: keypoint octave outside the scale-factor table");
             uh_ba_obs& o = st.obs[e++];
             o.point = pi; o.frame = flat_of[of]; o.u = x; o.v = y; o.inv_sigma = (double)inv_sf[octave];
+            if constexpr (MARKERS) kpw[of] += (double)((depth > 0 ? 3 : 2) * inv_sf[octave]);   // (:248, :271: int * float, a float product)
         });
+    }
+    if constexpr (MARKERS) {
+        mix->marker_of.assign(taken_markers.begin(), taken_markers.end());
+        int EM = 0;
+        for (uint32_t id : mix->marker_of) map.for_each_marker_frame(id, [&](uint32_t) { ++EM; });
+        mix->n_edges = EM;
+        const int M = (int)mix->marker_of.size();
+        FlatMarkerArrays ma = msink.begin(M, EM);
+        // :281-299, for the frames the edges below hang on
+        auto frame_weight = [&](uint32_t f) {
+            const size_t n = map.frame_n_markers(f);
+            double weight_per_error = 1;
+            if (kpw[f] > 40 && n > 0) {
+                const double marker_perct = ps.markersOptWeight * std::min(1., double(n) / ps.minMarkersForMaxWeight);
+                weight_per_error = (marker_perct * kpw[f]) / double(n * 8);
+            }
+            return weight_per_error;
+        };
+        int me = 0;
+        for (int m = 0; m < M; m++) {
+            const uint32_t id = mix->marker_of[m];
+            const float* G = map.marker_pose_g2m(id);
+            for (int j = 0; j < 16; j++) ma.pose_g2m[16 * m + j] = G[j];
+            ma.size[m] = map.marker_size(id);
+            map.for_each_marker_frame(id, [&](uint32_t mf) {
+                const float* c = map.frame_marker_corners(mf, id);
+                for (int j = 0; j < 8; j++) ma.und_corners[8 * me + j] = c[j];
+                ma.edge_marker[me] = m; ma.edge_frame[me] = flat_of[mf]; ma.edge_weight[me] = frame_weight(mf);
+                ++me;
+            });
+        }
     }
     return ix;
 }
@@ -167,14 +252,31 @@ FlatBAIndex flatten_walk(const MapView& map, const BAParamSet& ps, Sink& sink) {
 // pinned block; tests pass a vector-backed one and run without a GPU.
 template <class MapView, class Sink>
 FlatBAIndex flatten_for_ba(const MapView& map, const BAParamSet& ps, Sink& sink) {
-    return detail::flatten_walk<false>(map, ps, sink);
+    detail::NoMarkerSink none;
+    return detail::flatten_walk<false, false>(map, ps, sink, none, nullptr);
 }
 
 // The same selection for maps with stereo / RGB-D observations: Sink::begin returns a uh_ba_staging_stereo (StereoStagingSink /
 // StereoVectorSink below); then uh_ba_set_problem_staged_stereo, or uh_ba_set_problem_stereo on the vectors.
 template <class MapView, class Sink>
 FlatBAIndex flatten_for_ba_stereo(const MapView& map, const BAParamSet& ps, Sink& sink) {
-    return detail::flatten_walk<true>(map, ps, sink);
+    detail::NoMarkerSink none;
+    return detail::flatten_walk<true, false>(map, ps, sink, none, nullptr);
+}
+
+// The selection for maps with markers (and any mix of monocular and stereo / RGB-D observations): the frame / point / observation part
+// goes to `sink` as flatten_for_ba_stereo writes it (StereoVectorSink), the markers with a valid pose that the walk reaches and their
+// edges to `msink` (MarkerVectorSink); then uh_ba_set_problem_markers on sink.problem-style arrays, msink.view() and, where an
+// observation has depth, the stereo block.  A map without markers gives what flatten_for_ba_stereo gives and no marker edge.
+template <class MapView, class Sink, class MSink>
+FlatBAIndex flatten_for_ba_markers(const MapView& map, const BAParamSet& ps, Sink& sink, MSink& msink, FlatBAMarkerIndex& mix) {
+    return detail::flatten_walk<true, true>(map, ps, sink, msink, &mix);
+}
+
+// getResults' marker part (:526-527): the poses of the taken markers
+template <class MapView>
+void apply_marker_results(MapView& map, const FlatBAMarkerIndex& mix, const float* marker_poses /*M x 16*/) {
+    for (size_t m = 0; m < mix.marker_of.size(); m++) map.set_marker_pose_g2m(mix.marker_of[m], marker_poses + 16 * m);
 }
 
 // getResults (:466-537) onto the map: poses of the free used frames, coordinates of every taken point, then
@@ -233,6 +335,22 @@ struct StereoVectorSink {
         poses.assign(16 * (size_t)K, 0.f); intr.assign(4 * (size_t)K, 0.f); points.assign(3 * (size_t)P, 0.f); fixed.assign(K, 0); obs.assign(E, uh_ba_obs{});
         depth.assign(E, 0.f); bl.assign(K, 0.f);
         return uh_ba_staging_stereo{poses.data(), fixed.data(), intr.data(), points.data(), obs.data(), depth.data(), bl.data(), K, P, E};
+    }
+};
+
+// Plain vectors as the marker sink; view() is the block uh_ba_set_problem_markers takes
+struct MarkerVectorSink {
+    std::vector<float> pose_g2m, size, und_corners;
+    std::vector<int32_t> edge_marker, edge_frame;
+    std::vector<double> edge_weight;
+    FlatMarkerArrays begin(int M, int EM) {
+        pose_g2m.assign(16 * (size_t)M, 0.f); size.assign(M, 0.f); und_corners.assign(8 * (size_t)EM, 0.f);
+        edge_marker.assign(EM, 0); edge_frame.assign(EM, 0); edge_weight.assign(EM, 0.0);
+        return FlatMarkerArrays{pose_g2m.data(), size.data(), edge_marker.data(), edge_frame.data(), und_corners.data(), edge_weight.data()};
+    }
+    uh_ba_markers view() const {
+        return uh_ba_markers{(int32_t)size.size(), pose_g2m.data(), size.data(), (int32_t)edge_marker.size(), edge_marker.data(), edge_frame.data(),
+                             und_corners.data(), edge_weight.data()};
     }
 };
 

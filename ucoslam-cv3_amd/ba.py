@@ -42,6 +42,11 @@ class _StagingStereo(C.Structure):   # uh_ba_staging_stereo
                 ("cap_frames", C.c_int32), ("cap_points", C.c_int32), ("cap_obs", C.c_int32)]
 
 
+class _Markers(C.Structure):   # uh_ba_markers
+    _fields_ = [("n_markers", C.c_int32), ("pose_g2m", VP), ("size", VP), ("n_edges", C.c_int32), ("edge_marker", VP), ("edge_frame", VP),
+                ("und_corners", VP), ("edge_weight", VP)]
+
+
 class _ResultsView(C.Structure):
     _fields_ = [("poses", VP), ("points", VP), ("chi2", VP), ("bad", VP), ("pose_state", VP), ("iters", C.c_int32 * 2),
                 ("n_frames", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32)]
@@ -69,6 +74,8 @@ def _declare(L, sig):
     sig("uh_ba_set_problem_stereo", I, VP, C.POINTER(_Problem), C.POINTER(_Stereo), C.POINTER(ParamSet))
     sig("uh_ba_map_staging_stereo", I, VP, I, I, I, C.POINTER(_StagingStereo))
     sig("uh_ba_set_problem_staged_stereo", I, VP, I, I, I, C.POINTER(ParamSet), C.c_double, C.c_double)
+    sig("uh_ba_set_problem_markers", I, VP, C.POINTER(_Problem), C.POINTER(_Stereo), C.POINTER(_Markers), C.POINTER(ParamSet))
+    sig("uh_ba_get_marker_results", I, VP, VP, VP, VP)
 
 
 _lib._EXTRA_DECLS.append(_declare)
@@ -101,19 +108,39 @@ class GlobalOptimizer:
                       np_ptr(a["obs_kf"]), np_ptr(a["obs_uv"]), np_ptr(a["obs_w"]))
         return pr, a, (K, P, E)
 
-    def setParams(self, problem, params: ParamSet | None = None, stereo=None):
+    @staticmethod
+    def _markers_struct(markers: dict):
+        m = dict(pose_g2m=np.ascontiguousarray(markers["pose_g2m"], np.float32).reshape(-1, 16), size=np.ascontiguousarray(markers["size"], np.float32),
+                 edge_marker=np.ascontiguousarray(markers["edge_marker"], np.int32), edge_frame=np.ascontiguousarray(markers["edge_frame"], np.int32),
+                 und_corners=np.ascontiguousarray(markers["und_corners"], np.float32).reshape(-1, 8),
+                 edge_weight=np.ascontiguousarray(markers["edge_weight"], np.float64))
+        M, EM = len(m["size"]), len(m["edge_marker"])
+        assert len(m["pose_g2m"]) == M and len(m["edge_frame"]) == EM and len(m["und_corners"]) == EM and len(m["edge_weight"]) == EM
+        return _Markers(M, np_ptr(m["pose_g2m"]), np_ptr(m["size"]), EM, np_ptr(m["edge_marker"]), np_ptr(m["edge_frame"]), np_ptr(m["und_corners"]),
+                        np_ptr(m["edge_weight"])), m, (M, EM)
+
+    def setParams(self, problem, params: ParamSet | None = None, stereo=None, markers=None):
         """stereo: None (monocular edges only, uh_ba_set_problem), True (the problem dict's "obs_depth" [E] f32 and "frame_bl" [K] f32:
-        an observation with depth > 0 is a three-row stereo / RGB-D edge) or a dict(huber_delta_3d=, chi2_threshold_3d=) with that meaning."""
+        an observation with depth > 0 is a three-row stereo / RGB-D edge) or a dict(huber_delta_3d=, chi2_threshold_3d=) with that meaning.
+        markers: None, or a dict(pose_g2m [M,16] f32, size [M] f32, edge_marker [EM] i32, edge_frame [EM] i32, und_corners [EM,8] f32,
+        edge_weight [EM] f64): squared planar markers with free poses (uh_ba_set_problem_markers); getMarkerResults() returns them."""
         pr, a, dims = problem if isinstance(problem, tuple) else self._problem_struct(problem)
         pp = C.byref(params) if params is not None else None
-        if stereo is None or stereo is False:
-            check(lib().uh_ba_set_problem(self._h, C.byref(pr), pp))
-        else:
+        sx = None
+        if not (stereo is None or stereo is False):
             opts = stereo if isinstance(stereo, dict) else {}
             depth = np.ascontiguousarray(problem["obs_depth"], np.float32)
             bl = np.ascontiguousarray(problem["frame_bl"], np.float32)
             assert len(depth) == dims[2] and len(bl) == dims[0]
             sx = _Stereo(np_ptr(depth), np_ptr(bl), float(opts.get("huber_delta_3d", 0.0)), float(opts.get("chi2_threshold_3d", 0.0)))
+        self._mdims = None
+        if markers is not None:
+            mk, keep, mdims = self._markers_struct(markers)
+            check(lib().uh_ba_set_problem_markers(self._h, C.byref(pr), C.byref(sx) if sx is not None else None, C.byref(mk), pp))
+            self._mdims = mdims if mdims[1] > 0 else None
+        elif sx is None:
+            check(lib().uh_ba_set_problem(self._h, C.byref(pr), pp))
+        else:
             check(lib().uh_ba_set_problem_stereo(self._h, C.byref(pr), C.byref(sx), pp))
         self._dims = dims
         self._obs = (a["obs_pt"], a["obs_kf"])
@@ -245,6 +272,16 @@ class GlobalOptimizer:
         check(lib().uh_ba_get_pose_state(self._h, np_ptr(out["state"])))
         self._bad_flags = out["bad"]
         self._bad = None
+        return out
+
+    def getMarkerResults(self):
+        """After optimize() on a problem set with markers: dict(poses [M,16] f32 — Marker::pose_g2m as getResults writes it back —,
+        state [M,7] f64 (qx qy qz qw tx ty tz), chi2 [EM] f64 of the marker edges at the final estimate)."""
+        if getattr(self, "_mdims", None) is None:
+            raise RuntimeError("GlobalOptimizer::getMarkerResults: the current problem has no markers")
+        M, EM = self._mdims
+        out = dict(poses=np.zeros((M, 16), np.float32), state=np.zeros((M, 7), np.float64), chi2=np.zeros(EM, np.float64))
+        check(lib().uh_ba_get_marker_results(self._h, np_ptr(out["poses"]), np_ptr(out["state"]), np_ptr(out["chi2"])))
         return out
 
     def getBadAssociations(self):

@@ -152,6 +152,7 @@ __device__ __forceinline__ void uh_latency_critical() { __builtin_amdgcn_s_setpr
 
 // ------------------------------------------------------------------------------------------------ small fp64 helpers
 #include "se3.hpp"   // quat_to_R, quat_from_R, quat_norm_pos
+#include "marker_edge.hpp"   // the marker edge of the "markers with free poses" kernels below
 __device__ __forceinline__ void inv3(const double* M, double* I) {
     const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
     const double id = 1.0 / (M[0] * c00 + M[1] * c01 + M[2] * c02);
@@ -2278,6 +2279,141 @@ __global__ __launch_bounds__(256) void ba_ingest_direct_kernel(const unsigned ch
     }
 }
 
+// ------------------------------------------------------------------------------------------------ markers with free poses
+// MarkerEdge in bundle adjustment (globaloptimizer_g2o.cpp:300-352; the edge itself: marker_edge.hpp).  A problem with marker edges
+// runs in the wide form, and the host hands it over with every marker appended as one more FREE FRAME without observations: frame
+// index K0 + m (K0 = the caller's frames), the last reduced-system slots, entries of the two pose state buffers like any keyframe.
+// ba_posew_kernel, ba_results_kernel, the pair lists (a diagonal pair per slot) and the factorisation then serve the markers as they
+// are, the landmark kernels see cameras nobody observes, and none of the kernels above takes a new argument.  What is new sits in
+// three kernels of its own:
+//   ba_mk_lin_kernel       one wave per marker edge: the 25 evaluations at the state of buffer `buf` (100 (evaluation, corner)
+//                          lanes over two rounds), the edge's five blocks (marker_edge.hpp: kMkBlock doubles) into blk[buf] and its
+//                          chi2; launched beside ba_lin_kernel at the start of a pass (buf = current) and behind ba_posew_kernel
+//                          in every trial (buf = trial): like Hll / bl / Hpl the blocks are double-buffered, so an accepted trial
+//                          flips the estimate and its marker linearisation together and a rejected one keeps both
+//   ba_mk_assemble_kernel  behind ba_assemblew_kernel, one workgroup per slot: adds the slot's edges, in edge order, into its
+//                          diagonal block, b_p and the border row of S, and drops each edge's off-diagonal block into the lower
+//                          triangle (marker row, frame column; S is zeroed per trial and a (marker, frame) pair occurs once)
+//   ba_mk_advance_kernel   ba_advance_kernel for these problems: the lambda initialisation takes the maximum over the SUMMED
+//                          diagonal of every vertex (keypoint part + marker edges), as computeLambdaInit sees it
+// The marker chi2 enters the decision through the partial-sum arrays the decision already adds up: entry nPointBlocks + e of
+// part_lin_chi (pass start) / part_chi (trial) is edge e's chi2 (part_scale: 0 — the markers' share of computeScale is in x_p, b_p),
+// and the kernels that take the decision are handed dims whose nPointBlocks counts those entries too (mk_decide_dims).  BAState,
+// BAPtrs and BADims keep their layout.
+struct BAMarkers {
+    int n_edges;
+    const int* e_mk; const int* e_kf;        // [n_edges] pose index of the marker (K0 + m) and of the frame
+    const double* e_uv;                      // [n_edges][8] und_corners, widened
+    const double* e_w; const double* e_half; // [n_edges] information scalar, half the marker's side (marker_half)
+    const int* slot_ptr; const int* slot_edge;   // CSR per reduced-system slot: edge * 2 + side (0: the slot is the edge's marker, 1: its frame), in edge order
+    double* blk[2];                          // [n_edges][kMkBlock], per state buffer
+    double* chi[2];                          // [n_edges] chi2 at the estimate of that buffer
+};
+__host__ __device__ inline BADims mk_decide_dims(BADims d, int n_edges) { d.nPointBlocks += n_edges; return d; }
+
+// grid = n_edges, one wave.  at_trial 0: the pass's first linearisation (only while st.first_trial), 1: at the trial estimate.
+__global__ __launch_bounds__(64) void ba_mk_lin_kernel(BAPtrs p, BADims d, BAMarkers mk, int slot, int at_trial) {
+    const BAState st = p.st[slot];
+    if (st.phase == 2 || (!at_trial && !st.first_trial)) return;
+    const int buf = at_trial ? st.cur ^ 1 : st.cur;
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const int km = mk.e_mk[e], kf = mk.e_kf[e];
+    const bool cam_free = p.slot[kf] >= 0;
+    __shared__ double s_err[25][8];
+    double g2m[7], c2g[7], intr[4];
+#pragma unroll
+    for (int i = 0; i < 7; i++) { g2m[i] = p.pose[buf][7 * (size_t)km + i]; c2g[i] = p.pose[buf][7 * (size_t)kf + i]; }
+#pragma unroll
+    for (int i = 0; i < 4; i++) intr[i] = p.intr[4 * (size_t)kf + i];
+    const double half = mk.e_half[e], w = mk.e_w[e];
+#pragma unroll 1
+    for (int round = 0; round < 2; round++) {
+        const int item = lane + 64 * round;   // (evaluation, corner)
+        if (item < 100) {
+            const int k = item >> 2, c = item & 3;
+            double ex = 0, ey = 0;
+            if (k < 13 || cam_free) {   // (a fixed frame is never perturbed)
+                double T[7];
+                mk_edge_transform(k, g2m, c2g, T);
+                mk_corner_error(T, c, half, intr, mk.e_uv[8 * (size_t)e + 2 * c], mk.e_uv[8 * (size_t)e + 2 * c + 1], ex, ey);
+            }
+            s_err[k][2 * c] = ex; s_err[k][2 * c + 1] = ey;
+        }
+    }
+    __syncthreads();
+    double* out = mk.blk[buf] + (size_t)kMkBlock * e;
+    for (int q = lane; q < kMkBlock; q += 64) out[q] = mk_block_entry(s_err, w, cam_free, q);
+    if (lane == 0) {
+        const double chi = mk_chi2(s_err, w);
+        mk.chi[buf][e] = chi;
+        if (at_trial) { p.part_chi[d.nPointBlocks + e] = chi; p.part_scale[d.nPointBlocks + e] = 0.0; }
+        else p.part_lin_chi[d.nPointBlocks + e] = chi;
+    }
+}
+
+// entry q (0..41: the 6 x 6 row-major, then the 6 of b) of what the marker edges add to slot s's diagonal block, in edge order
+__device__ __forceinline__ double mk_slot_sum(const BAMarkers& mk, int cur, int s, int q) {
+    double v = 0;
+    for (int i = mk.slot_ptr[s]; i < mk.slot_ptr[s + 1]; i++) {
+        const int code = mk.slot_edge[i];
+        v += mk.blk[cur][(size_t)kMkBlock * (code >> 1) + ((code & 1) ? 42 : 0) + q];
+    }
+    return v;
+}
+
+// grid = nfree (frames and markers), 64 threads; runs behind ba_assemblew_kernel on the state the step runs with
+__global__ __launch_bounds__(64) void ba_mk_assemble_kernel(BAPtrs p, BADims d, BAWide w, BAMarkers mk, int slot) {
+    const BAState st = p.st[slot];
+    if (st.phase == 2) return;
+    const int s = blockIdx.x, q = threadIdx.x;
+    const int i0 = mk.slot_ptr[s], i1 = mk.slot_ptr[s + 1];
+    if (i0 == i1) return;
+    const size_t ld = w.ld;
+    if (q < 42) {
+        const double v = mk_slot_sum(mk, st.cur, s, q);
+        if (q >= 36) { p.bp[6 * s + (q - 36)] += v; w.S[(size_t)d.n * ld + 6 * s + (q - 36)] += v; }
+        else { const int a = q / 6, c = q - 6 * a; if (c <= a) w.S[(size_t)(6 * s + a) * ld + 6 * s + c] += v; }
+    }
+    if (q < 36) {   // the off-diagonal blocks of a marker slot: row = marker dimension a, column = frame dimension c
+        const int a = q / 6, c = q - 6 * a;
+        for (int i = i0; i < i1; i++) {
+            const int code = mk.slot_edge[i];
+            if (code & 1) continue;
+            const int e = code >> 1, sf = p.slot[mk.e_kf[e]];
+            if (sf < 0) continue;
+            w.S[(size_t)(6 * s + a) * ld + 6 * sf + c] += mk.blk[st.cur][(size_t)kMkBlock * e + 84 + q];
+        }
+    }
+}
+
+// ba_advance_kernel with marker edges in the sums and in the maximum of computeLambdaInit
+__global__ __launch_bounds__(64) void ba_mk_advance_kernel(BAPtrs p, BADims d, BAMarkers mk, int slot) {
+    const int lane = threadIdx.x;
+    const BAState st0 = p.st[slot];
+    const DecideSums sm = decide_sums(p, mk_decide_dims(d, mk.n_edges), lane, st0.lambda);
+    BAState st = (st0.phase != 2 && st0.pending) ? apply_decision(st0, sm, st0.stop_seen != 0) : st0;
+    if (st.phase == 2) {
+        if (lane == 0) { st.pending = 0; p.st[slot ^ 1] = st; }
+        return;
+    }
+    if (st.iteration == 0 && st.qmax == 0) {   // computeLambdaInit: tau * max |H_jj| over the vertices' summed diagonals
+        double m = 0;
+        for (int i = lane; i < d.nPointBlocks; i += 64) m = fmax(m, p.part_maxdiag[i]);
+        for (int i = lane; i < d.nfree * 6; i += 64) {
+            const int s = i / 6, a = i - 6 * s;
+            const int q = a * 6 - a * (a - 1) / 2;
+            double v = 0;
+            for (int c = 0; c < kCamChunks; c++) v += p.HppPart[((size_t)s * kCamChunks + c) * 27 + q];
+            v += mk_slot_sum(mk, st.cur, s, 7 * a);
+            m = fmax(m, fabs(v));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+        st.lambda = 1e-5 * m; st.ni = 2;
+    }
+    if (lane == 0) { BAState pub = st; pub.pending = 1; pub.stop_seen = 0; p.st[slot ^ 1] = pub; }
+}
+
 #include "ba_persist.hpp"
 
 }  // namespace
@@ -2349,6 +2485,7 @@ struct BAPlanIn {
     int K, P, E, nfree;
     bool stereo;       // the problem has three-row edges (the persistent form is monocular)
     bool persist_ok;   // nothing outside the plan rules the persistent form out: the pinned report block is mapped, no residency back-off, no refused LDS grant
+    bool markers;      // the problem has marker edges: the wide form whatever its size (K and nfree count the markers, appended as free frames)
 };
 struct BAPlan {
     int form;
@@ -2406,10 +2543,10 @@ static bool plan_persist(const BAPlanIn& in, const BAKnobs& kn, const BALimits& 
 static BAPlan plan_ba(const BAPlanIn& in, const BAKnobs& kn, const BALimits& lim) {
     BAPlan pl{};
     const int nfree = in.nfree, n = 6 * nfree, P = in.P, npairs = nfree * (nfree + 1) / 2;
-    pl.persist_candidate = in.persist_ok && !in.stereo && !kn.legacy && !kn.wide && nfree >= 1 && P >= 1 && in.E < (1 << 20) - 1;
+    pl.persist_candidate = in.persist_ok && !in.stereo && !in.markers && !kn.legacy && !kn.wide && nfree >= 1 && P >= 1 && in.E < (1 << 20) - 1;
     if (pl.persist_candidate && plan_persist(in, kn, lim, pl.ps)) { pl.form = kFormPersist; return pl; }
     // wide form: sparse camera-pair lists + blocked dense LDL^T in HBM (see "wide problems" above)
-    pl.form = (nfree > kMaxFree || (kn.wide && nfree > 0)) ? kFormWide : kFormChain;
+    pl.form = (nfree > kMaxFree || in.markers || (kn.wide && nfree > 0)) ? kFormWide : kFormChain;
     pl.nsplit = std::max(1, std::min(kMaxSplit, uh_div_up(P, kThreads)));
     // every workgroup of the back-substitution launch assembles ALL npairs x nsplit partials itself: with many camera pairs fewer, fatter
     // landmark chunks win (measured, 3000 landmarks: 17 / 20 / 32 free cameras 2.20 / 2.90 / 9.9 ms with 12 chunks, 1.77 / 2.14 / 7.3 with 2)
@@ -2503,6 +2640,8 @@ struct uh_ba {
     uh_ba_params job_params{}; bool job_has_params = false;
     unsigned p_seq = 0;                   // launches of the persistent kernel by this optimizer: 20 bits of it tag the exchanged words
     BAWide wd{};
+    int n_mk = 0;                         // markers of the current problem: the last n_mk frames (and reduced-system slots) of dims are theirs, not the caller's
+    BAMarkers mk{};                       // ... and their edges (n_mk > 0: the wide form with the marker kernels)
     int step = 0;                         // LM steps enqueued since uh_ba_optimize began: step s reads state slot s & 1
     bool optimized = false;
     // uh_ba_optimize_async: a persistent worker thread (the reference's mapper thread, mapmanager.cpp:150) runs uh_ba_optimize
@@ -2551,14 +2690,17 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
     for (int s = 0; s < nsteps; s++) {
         const int slot = b->step & 1;   // state left by the previous step (or by begin_pass / the closing decide kernel)
         if (pass_start && s == 0) UH_LAUNCH_BA(b, ba_lin_kernel, dim3(d.nPointBlocks + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, slot);
+        if (pass_start && s == 0 && b->n_mk) UH_LAUNCH(b->ctx, ba_mk_lin_kernel, dim3(b->mk.n_edges), dim3(64), 0, b->ptrs, d, b->mk, slot, 0);
         if (pl.form == kFormWide) {
             const BAWide& W = b->wd;
             const int run = slot ^ 1;   // the state this step runs with (published by the advance kernel)
-            UH_LAUNCH(b->ctx, ba_advance_kernel, dim3(1), dim3(64), 0, b->ptrs, d, slot);
+            if (b->n_mk) UH_LAUNCH(b->ctx, ba_mk_advance_kernel, dim3(1), dim3(64), 0, b->ptrs, d, b->mk, slot);
+            else UH_LAUNCH(b->ctx, ba_advance_kernel, dim3(1), dim3(64), 0, b->ptrs, d, slot);
             UH_HIP_CHECK(hipMemsetAsync(W.S, 0, sizeof(double) * (size_t)W.ld * W.ld, st));
             UH_HIP_CHECK(hipMemsetAsync(W.fail, 0, sizeof(int), st));
             UH_LAUNCH_BA(b, ba_schurw_kernel, dim3(W.n_items + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, W, run);
             UH_LAUNCH(b->ctx, ba_assemblew_kernel, dim3(W.n_pairs), dim3(64), 0, b->ptrs, d, W, run);
+            if (b->n_mk) UH_LAUNCH(b->ctx, ba_mk_assemble_kernel, dim3(d.nfree), dim3(64), 0, b->ptrs, d, W, b->mk, run);
             for (int k0 = 0; k0 < d.n; k0 += kWNB) {
                 const int nb = std::min(kWNB, d.n - k0), rows = d.n + 1 - (k0 + nb);   // rows behind the panel, border row included
                 UH_LAUNCH(b->ctx, ba_ldlw_diag_kernel, dim3(1), dim3(256), 0, b->ptrs, W, run, k0, nb);
@@ -2571,6 +2713,7 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
                 UH_LAUNCH(b->ctx, ba_ldlw_back_kernel, dim3(std::max(uh_div_up(k0, 256), 1)), dim3(256), 0, b->ptrs, W, run, k0, nb);
             }
             UH_LAUNCH(b->ctx, ba_posew_kernel, dim3(uh_div_up(d.nfree, 256)), dim3(256), 0, b->ptrs, d, W, run);
+            if (b->n_mk) UH_LAUNCH(b->ctx, ba_mk_lin_kernel, dim3(b->mk.n_edges), dim3(64), 0, b->ptrs, d, b->mk, run, 1);
             UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, pl.nsplit, run);
             b->step++;
             continue;
@@ -2598,7 +2741,7 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
         b->step++;
     }
     // the last trial's decision (every other one is taken by the following step's schur kernel)
-    UH_LAUNCH(b->ctx,ba_decide_kernel, dim3(1), dim3(64), 0, b->ptrs, d, b->step & 1);
+    UH_LAUNCH(b->ctx,ba_decide_kernel, dim3(1), dim3(64), 0, b->ptrs, b->n_mk ? mk_decide_dims(d, b->mk.n_edges) : d, b->step & 1);   // (marker problems: the edges' chi2 entries behind the landmark blocks' count too)
     UH_HIP_CHECK(hipGetLastError());
     return UH_OK;
 }
@@ -2901,6 +3044,10 @@ static void build_snapshot(const uh_ba_problem* pr, BASnapshot& s) {
     for (int e = 0; e < E; e++) { s.uv[2 * e] = pr->obs_uv[2 * e]; s.uv[2 * e + 1] = pr->obs_uv[2 * e + 1]; s.w[e] = pr->obs_inv_sigma[e]; }
 }
 
+// (min: the marker edges of a problem whose markers are appended to pr as free frames — NULL on every other route, whose tables and
+// arena layout it leaves as they are.  slot_ptr / slot_edge: the CSR BAMarkers describes.)
+struct MarkerIn { int n_markers = 0; std::vector<int> e_mk, e_kf, slot_ptr, slot_edge; std::vector<double> uv, w, half; };
+
 // Part 4, the arena.  carve_arena names every array once: the carver hands out its place (256-byte aligned, in the order asked for),
 // sets the device pointer and sends the host array there.  The constant arrays of the problem form one contiguous prefix of the arena
 // (everything up to end_prefix()): they are gathered in a pinned mirror of that prefix and leave as ONE asynchronous copy (fourteen
@@ -2928,8 +3075,8 @@ struct ArenaCarver {
     template <typename T, typename S> void arr(T*& dst, size_t count, const std::vector<S>& src) { arr(dst, count, src.data(), src.size()); }
     void end_prefix() { if (dry) prefix = A.off; }
 };
-struct ArenaTables { BAPtrs p{}; BAWide W{}; BAStereo sx{}; double* pose0 = nullptr; double* pts0 = nullptr; };   // what the carve sets: handed to the optimiser once setParams has succeeded
-static void carve_arena(ArenaCarver& c, ArenaTables& t, const BADims& d, const BAPlan& pl, const uh_ba_problem* pr, const BAGraph& g, const WideLists& wl, const BASnapshot& s, const StereoIn* sin) {
+struct ArenaTables { BAPtrs p{}; BAWide W{}; BAStereo sx{}; BAMarkers mk{}; double* pose0 = nullptr; double* pts0 = nullptr; };   // what the carve sets: handed to the optimiser once setParams has succeeded
+static void carve_arena(ArenaCarver& c, ArenaTables& t, const BADims& d, const BAPlan& pl, const uh_ba_problem* pr, const BAGraph& g, const WideLists& wl, const BASnapshot& s, const StereoIn* sin, const MarkerIn* min) {
     const size_t K = d.K, P = d.P, E = d.E, nfree1 = std::max(d.nfree, 1), n1 = std::max(d.n, 1), npairs1 = std::max(d.nfree * (d.nfree + 1) / 2, 1);
     const bool wide = pl.form == kFormWide, dense = pl.schur != kSchurPair;
     BAPtrs& p = t.p;
@@ -2938,6 +3085,11 @@ static void carve_arena(ArenaCarver& c, ArenaTables& t, const BADims& d, const B
     c.arr(p.e_pt, E, pr->obs_point, E); c.arr(p.e_kf, E, pr->obs_frame, E); c.arr(p.e_uv, 2 * E, s.uv); c.arr(p.e_w, E, s.w);
     c.arr(p.slot, K, g.slot); c.arr(p.free_kf, nfree1, g.free_kf); c.arr(p.intr, 4 * K, s.intr); c.arr(p.edge_of, g.edge_of.size(), g.edge_of);
     if (sin) { c.arr(t.sx.e_ur, E, sin->ur); c.arr(t.sx.e_bf, E, sin->bf); c.arr(t.sx.e_st, E, sin->st); }
+    const size_t EM = min ? min->e_mk.size() : 0;
+    if (min) {
+        c.arr(t.mk.e_mk, EM, min->e_mk); c.arr(t.mk.e_kf, EM, min->e_kf); c.arr(t.mk.e_uv, 8 * EM, min->uv); c.arr(t.mk.e_w, EM, min->w); c.arr(t.mk.e_half, EM, min->half);
+        c.arr(t.mk.slot_ptr, d.nfree + 1, min->slot_ptr); c.arr(t.mk.slot_edge, min->slot_edge.size(), min->slot_edge);
+    }
     c.arr(t.pose0, 7 * K, s.pose0); c.arr(t.pts0, 3 * P, s.pts0);
     c.end_prefix();
     for (int i = 0; i < 2; i++) { c.arr(p.pose[i], 7 * K); c.arr(p.poseR[i], 12 * K); c.arr(p.pts[i], 3 * P); }
@@ -2951,7 +3103,8 @@ static void carve_arena(ArenaCarver& c, ArenaTables& t, const BADims& d, const B
     c.arr(W.item_pair, n_items + 1, wl.item_pair); c.arr(W.item_begin, n_items + 1, wl.item_begin); c.arr(W.item_count, n_items + 1, wl.item_count);
     c.arr(W.tri_pt, n_tri + 1, wl.tri_pt); c.arr(W.tri_e1, n_tri + 1, wl.tri_e1); c.arr(W.tri_e2, n_tri + 1, wl.tri_e2);
     c.arr(W.Wpart, (n_items + 1) * 42); c.arr(W.Y, wide ? (size_t)(d.n + 1) * kWNB : 1); c.arr(W.fail, 4);
-    c.arr(p.part_lin_chi, d.nPointBlocks); c.arr(p.part_maxdiag, d.nPointBlocks); c.arr(p.part_chi, d.nPointBlocks); c.arr(p.part_scale, d.nPointBlocks);
+    c.arr(p.part_lin_chi, d.nPointBlocks + EM); c.arr(p.part_maxdiag, d.nPointBlocks); c.arr(p.part_chi, d.nPointBlocks + EM); c.arr(p.part_scale, d.nPointBlocks + EM);   // (+ one entry per marker edge)
+    if (min) { for (int i = 0; i < 2; i++) { c.arr(t.mk.blk[i], (size_t)kMkBlock * EM); c.arr(t.mk.chi[i], EM); } t.mk.n_edges = (int)EM; }
     c.arr(p.st, 2); c.arr(p.clk, 64);
     W.n_pairs = (int)n_pairs; W.n_items = (int)n_items; W.ld = d.n + 1; W.S = p.S;
 }
@@ -2960,7 +3113,7 @@ static void carve_arena(ArenaCarver& c, ArenaTables& t, const BADims& d, const B
 // instantiated for, or a window whose fixed frames do not fit its LDS) and the wide form (global BA).  Arrays anywhere in host memory.
 // (Plan, pointers and tables of the optimiser change only when everything has succeeded: the residency fallback comes here with a
 // problem set, and one it cannot rebuild stays the persistent problem it was.)
-static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const BAPlan& pl, const StereoIn* sin = nullptr) {
+static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const BAPlan& pl, const StereoIn* sin = nullptr, const MarkerIn* min = nullptr) {
     b->stereo = false;
     const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs;
     const bool wide = pl.form == kFormWide;
@@ -2976,7 +3129,7 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const BAPlan& p
     fill_dims(b, K, P, E, (int)g.free_kf.size());
     ArenaCarver sizes;
     ArenaTables t;
-    carve_arena(sizes, t, b->dims, pl, pr, g, wl, s, sin);
+    carve_arena(sizes, t, b->dims, pl, pr, g, wl, s, sin, min);
     if ((rc = b->arena.reserve(sizes.A.off + 256))) return rc;
     UH_HIP_CHECK(hipSetDevice(b->ctx->device));
     hipStream_t st = b->ctx->stream;
@@ -2985,7 +3138,7 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const BAPlan& p
     if (!b->ev_up) UH_HIP_CHECK(hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming));
     ArenaCarver c;
     c.dry = false; c.base = b->arena.as<char>(); c.pin = b->up_pin.as<char>(); c.st = st; c.prefix = sizes.prefix;
-    carve_arena(c, t, b->dims, pl, pr, g, wl, s, sin);
+    carve_arena(c, t, b->dims, pl, pr, g, wl, s, sin, min);
     if (c.rc) return c.rc;
     if ((rc = b->d_poses_in.reserve(16 * (size_t)K * 4))) return rc;
     if ((rc = b->d_poses_out.reserve(16 * (size_t)K * 4))) return rc;
@@ -3006,6 +3159,8 @@ static int set_problem_tables(uh_ba* b, const uh_ba_problem* pr, const BAPlan& p
         b->sx = t.sx;
         b->sx.delta3 = sin->delta3; b->sx.dsqr3 = sin->delta3 * sin->delta3; b->sx.chi2_th3 = sin->chi2_th3;
     }
+    b->n_mk = min ? min->n_markers : 0;
+    if (min) b->mk = t.mk;
     b->plan = pl;
     b->have_problem = true;
     return UH_OK;
@@ -3403,6 +3558,7 @@ static void set_problem_begin(uh_ba* b, const uh_ba_params* params) {
     b->have_problem = false;
     b->optimized = false;
     b->stereo = false;
+    b->n_mk = 0;
     if (params) b->params = *params;
     if (b->params.huber_delta <= 0) b->params.huber_delta = std::sqrt(5.99);
     if (b->params.chi2_threshold <= 0) b->params.chi2_threshold = 5.99;
@@ -3545,6 +3701,104 @@ int uh_ba_set_problem_staged_stereo(uh_ba* b, int K, int P, int E, const uh_ba_p
     return staged_problem_to_tables(b, K, P, E, false, b->stage_depth.data(), b->stage_bl.data(), huber_delta_3d, chi2_threshold_3d);
 }
 
+// setParams with marker observations and free marker poses.  Without marker edges: exactly uh_ba_set_problem / _stereo.  Otherwise the
+// markers are appended to the frames as free ones nobody observes (pose = pose_g2m through the same toSE3Quat snapshot, a neutral
+// intrinsics row) and the problem is planned as the wide form; see "markers with free poses" above.
+int uh_ba_set_problem_markers(uh_ba* b, const uh_ba_problem* pr, const uh_ba_stereo* stereo, const uh_ba_markers* mkr, const uh_ba_params* params) {
+    const char* who = "uh_ba_set_problem_markers";
+    UH_REQUIRE(b && pr, "%s: NULL argument", who);
+    if (!mkr || mkr->n_edges == 0) return stereo ? uh_ba_set_problem_stereo(b, pr, stereo, params) : uh_ba_set_problem(b, pr, params);
+    UH_REQUIRE(b->job.load() == 0, "%s: an optimisation is in flight (call uh_ba_wait)", who);
+    const int K = pr->n_frames, P = pr->n_points, E = pr->n_obs, M = mkr->n_markers, EM = mkr->n_edges;
+    set_problem_begin(b, params);   // (ahead of the checks, as in uh_ba_set_problem: a refused problem leaves none set)
+    int rc = check_problem_args(who, b, pr, K, P, E);
+    if (rc) return rc;
+    UH_REQUIRE(M >= 1 && EM >= 1, "%s: bad sizes n_markers=%d n_edges=%d", who, M, EM);
+    UH_REQUIRE(mkr->pose_g2m && mkr->size && mkr->edge_marker && mkr->edge_frame && mkr->und_corners && mkr->edge_weight, "%s: NULL marker arrays", who);
+    for (int m = 0; m < M; m++) {
+        UH_REQUIRE(std::isfinite(mkr->size[m]) && mkr->size[m] > 0, "%s: marker %d has size %g (must be finite and > 0)", who, m, (double)mkr->size[m]);
+        for (int j = 0; j < 16; j++) UH_REQUIRE(std::isfinite(mkr->pose_g2m[16 * (size_t)m + j]), "%s: marker %d has a non-finite pose", who, m);
+    }
+    int nfree = 0;
+    for (int k = 0; k < K; k++) nfree += pr->fixed[k] ? 0 : 1;
+    MarkerIn min;
+    min.n_markers = M;
+    min.e_mk.resize(EM); min.e_kf.resize(EM); min.uv.resize(8 * (size_t)EM); min.w.resize(EM); min.half.resize(EM);
+    std::vector<std::pair<int, int>> seen(EM);
+    for (int e = 0; e < EM; e++) {
+        const int m = mkr->edge_marker[e], k = mkr->edge_frame[e];
+        UH_REQUIRE(m >= 0 && m < M && k >= 0 && k < K, "%s: marker edge %d references marker %d / frame %d out of range", who, e, m, k);
+        const double w = mkr->edge_weight[e];
+        UH_REQUIRE(std::isfinite(w) && w > 0, "%s: marker edge %d has weight %g (must be finite and > 0)", who, e, w);
+        for (int j = 0; j < 8; j++) {
+            UH_REQUIRE(std::isfinite(mkr->und_corners[8 * (size_t)e + j]), "%s: marker edge %d has a non-finite corner", who, e);
+            min.uv[8 * (size_t)e + j] = mkr->und_corners[8 * (size_t)e + j];
+        }
+        min.e_mk[e] = K + m; min.e_kf[e] = k; min.w[e] = w; min.half[e] = marker_half(mkr->size[m]);
+        seen[e] = {m, k};
+    }
+    std::sort(seen.begin(), seen.end());
+    for (int e = 1; e < EM; e++)
+        UH_REQUIRE(seen[e] != seen[e - 1], "%s: marker %d is linked to frame %d twice", who, seen[e].first, seen[e].second);
+    // the problem with the markers appended as free frames; the reduced-system slots follow the frame order, so the markers' are the last
+    const int KA = K + M;
+    std::vector<float> poses(16 * (size_t)KA), intr(4 * (size_t)KA);
+    std::vector<uint8_t> fixed(KA, 0);
+    std::memcpy(poses.data(), pr->poses_f2g, 16 * (size_t)K * sizeof(float));
+    std::memcpy(poses.data() + 16 * (size_t)K, mkr->pose_g2m, 16 * (size_t)M * sizeof(float));
+    std::memcpy(intr.data(), pr->intr, 4 * (size_t)K * sizeof(float));
+    for (int m = 0; m < M; m++) { float* I = &intr[4 * (size_t)(K + m)]; I[0] = I[1] = 1.f; I[2] = I[3] = 0.f; }
+    std::memcpy(fixed.data(), pr->fixed, K);
+    uh_ba_problem aug = *pr;
+    aug.n_frames = KA; aug.poses_f2g = poses.data(); aug.fixed = fixed.data(); aug.intr = intr.data();
+    // per slot, in edge order: the marker edges it takes part in
+    std::vector<int> slot(KA, -1);
+    { int sfree = 0; for (int k = 0; k < KA; k++) if (!fixed[k]) slot[k] = sfree++; }
+    const int nfa = nfree + M;
+    min.slot_ptr.assign(nfa + 1, 0);
+    for (int e = 0; e < EM; e++) { min.slot_ptr[slot[min.e_mk[e]] + 1]++; if (slot[min.e_kf[e]] >= 0) min.slot_ptr[slot[min.e_kf[e]] + 1]++; }
+    for (int sl = 0; sl < nfa; sl++) min.slot_ptr[sl + 1] += min.slot_ptr[sl];
+    min.slot_edge.resize(min.slot_ptr[nfa]);
+    {
+        std::vector<int> fill(min.slot_ptr.begin(), min.slot_ptr.end() - 1);
+        for (int e = 0; e < EM; e++) {
+            min.slot_edge[fill[slot[min.e_mk[e]]]++] = 2 * e;
+            if (slot[min.e_kf[e]] >= 0) min.slot_edge[fill[slot[min.e_kf[e]]]++] = 2 * e + 1;
+        }
+    }
+    StereoIn sin;
+    int n_st = 0;
+    if (stereo && E > 0) {
+        UH_REQUIRE(stereo->obs_depth && stereo->frame_bl, "%s: NULL obs_depth / frame_bl", who);
+        rc = stereo_edges(pr, stereo->obs_depth, stereo->frame_bl, stereo->huber_delta_3d, stereo->chi2_threshold_3d, who, sin, &n_st);
+        if (rc) return rc;
+    }
+    const BAPlan pl = plan_ba(BAPlanIn{KA, P, E, nfa, n_st > 0, false, true}, b->knobs, b->lim);
+    return set_problem_tables(b, &aug, pl, n_st > 0 ? &sin : nullptr, &min);
+}
+
+// getResults for the markers (:526-527): float 4x4 poses through the kernel that writes the frames', the fp64 state, the edges' chi2
+int uh_ba_get_marker_results(uh_ba* b, float* pose_g2m_out, double* pose7_out, double* edge_chi2_out) {
+    UH_REQUIRE(b && b->have_problem && b->optimized, "uh_ba_get_marker_results: optimize() has not run");
+    UH_REQUIRE(b->n_mk > 0, "uh_ba_get_marker_results: the current problem has no markers");
+    UH_HIP_CHECK(hipSetDevice(b->ctx->device));
+    hipStream_t st = b->ctx->stream;
+    const BADims& d = b->dims;
+    const size_t K0 = (size_t)(d.K - b->n_mk), M = (size_t)b->n_mk, EM = (size_t)b->mk.n_edges;
+    BAState hs;
+    UH_HIP_CHECK(hipMemcpyAsync(&hs, b->ptrs.st + (b->step & 1), sizeof(BAState), hipMemcpyDeviceToHost, st));
+    if (pose_g2m_out) {
+        UH_LAUNCH_BA(b, ba_results_kernel, dim3(uh_div_up(std::max(std::max(d.K, 3 * d.P), 1), 256)), dim3(256), 0, b->ptrs, d, b->d_poses_in.as<float>(),
+                     b->d_poses_out.as<float>(), b->d_points_out.as<float>(), b->d_bad.as<unsigned char>(), 0, b->step & 1);
+        UH_HIP_CHECK(hipMemcpyAsync(pose_g2m_out, b->d_poses_out.as<float>() + 16 * K0, 16 * M * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    UH_HIP_CHECK(hipStreamSynchronize(st));
+    if (pose7_out) UH_HIP_CHECK(hipMemcpyAsync(pose7_out, b->ptrs.pose[hs.cur] + 7 * K0, 7 * M * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (edge_chi2_out) UH_HIP_CHECK(hipMemcpyAsync(edge_chi2_out, b->mk.chi[hs.cur], EM * sizeof(double), hipMemcpyDeviceToHost, st));
+    UH_HIP_CHECK(hipStreamSynchronize(st));
+    return UH_OK;
+}
+
 // the per-observation chi2 is an extra of this ABI (the reference's getResults does not return it): a host that never asks for it saves
 // the kernel three quarters of its result hand-over.  Takes effect with the next set_problem.
 int uh_ba_want_chi2(uh_ba* b, int on) {
@@ -3590,6 +3844,7 @@ int uh_ba_optimize(uh_ba* b, const volatile uint8_t* stop_asap) {
         return uh_ba_optimize(b, stop_asap);
     }
     UH_LAUNCH(b->ctx,ba_init_state_kernel, dim3(uh_div_up(nmax, 256)), dim3(256), 0, b->ptrs, d, b->d_pose0, b->d_pts0);
+    if (b->n_mk) for (int i = 0; i < 2; i++) UH_HIP_CHECK(hipMemsetAsync(b->mk.chi[i], 0, sizeof(double) * (size_t)b->mk.n_edges, b->ctx->stream));   // (a run stopped before its first linearisation reports 0, as e_chi2 does)
     // Both passes are enqueued in one go, one step per outer iteration: enough when no trial is rejected — a rejected trial is rare,
     // and a spare step whose pass is already finished would still cost its two launches (~10 us per pass); finish_pass() adds steps
     // when a pass needs them.  Between them the
@@ -3735,17 +3990,18 @@ int uh_ba_get_results(uh_ba* b, float* poses_out, float* points_out, double* chi
         UH_LAUNCH_BA(b, ba_results_kernel, dim3(uh_div_up(d.E, 256)), dim3(256), 0, b->ptrs, d, b->d_poses_in.as<float>(),
                            b->d_poses_out.as<float>(), b->d_points_out.as<float>(), b->d_bad.as<unsigned char>(), 1, b->step & 1);
     // through ONE pinned block: asynchronous DMA + one synchronisation (four pageable copies each staged and synchronised on their own: 0.16 ms)
+    const size_t K0 = (size_t)(d.K - b->n_mk);   // the caller's frames (markers sit behind them: uh_ba_get_marker_results)
     const size_t o_po = 0, o_pt = o_po + ((16 * (size_t)d.K * 4 + 255) & ~(size_t)255), o_bad = o_pt + ((3 * (size_t)d.P * 4 + 255) & ~(size_t)255);
     const size_t o_chi = o_bad + (((size_t)d.E + 255) & ~(size_t)255), total = o_chi + (chi2_out ? (size_t)d.E * 8 : 0) + 256;
     int rc = b->res_pin.reserve(total);
     if (rc) return rc;
     unsigned char* hp = b->res_pin.as<unsigned char>();
-    if (poses_out) UH_HIP_CHECK(hipMemcpyAsync(hp + o_po, b->d_poses_out.p, 16 * (size_t)d.K * 4, hipMemcpyDeviceToHost, st));
+    if (poses_out) UH_HIP_CHECK(hipMemcpyAsync(hp + o_po, b->d_poses_out.p, 16 * K0 * 4, hipMemcpyDeviceToHost, st));
     if (points_out && d.P) UH_HIP_CHECK(hipMemcpyAsync(hp + o_pt, b->d_points_out.p, 3 * (size_t)d.P * 4, hipMemcpyDeviceToHost, st));
     if (chi2_out && d.E) UH_HIP_CHECK(hipMemcpyAsync(hp + o_chi, b->ptrs.e_chi2, (size_t)d.E * 8, hipMemcpyDeviceToHost, st));
     if (bad_out && d.E) UH_HIP_CHECK(hipMemcpyAsync(hp + o_bad, b->d_bad.p, (size_t)d.E, hipMemcpyDeviceToHost, st));
     UH_HIP_CHECK(hipStreamSynchronize(st));
-    if (poses_out) std::memcpy(poses_out, hp + o_po, 16 * (size_t)d.K * 4);
+    if (poses_out) std::memcpy(poses_out, hp + o_po, 16 * K0 * 4);
     if (points_out && d.P) std::memcpy(points_out, hp + o_pt, 3 * (size_t)d.P * 4);
     if (chi2_out && d.E) std::memcpy(chi2_out, hp + o_chi, (size_t)d.E * 8);
     if (bad_out && d.E) std::memcpy(bad_out, hp + o_bad, (size_t)d.E);
@@ -3760,7 +4016,7 @@ int uh_ba_get_pose_state(uh_ba* b, double* pose7_out) {
     BAState hs;
     UH_HIP_CHECK(hipMemcpyAsync(&hs, b->ptrs.st + (b->step & 1), sizeof(BAState), hipMemcpyDeviceToHost, b->ctx->stream));
     UH_HIP_CHECK(hipStreamSynchronize(b->ctx->stream));
-    UH_HIP_CHECK(hipMemcpyAsync(pose7_out, b->ptrs.pose[hs.cur], 7 * (size_t)b->dims.K * 8, hipMemcpyDeviceToHost, b->ctx->stream));
+    UH_HIP_CHECK(hipMemcpyAsync(pose7_out, b->ptrs.pose[hs.cur], 7 * (size_t)(b->dims.K - b->n_mk) * 8, hipMemcpyDeviceToHost, b->ctx->stream));
     UH_HIP_CHECK(hipStreamSynchronize(b->ctx->stream));
     return UH_OK;
 }
