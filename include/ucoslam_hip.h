@@ -665,6 +665,10 @@ int    uh_fstream_finish_dev(uh_fstream* fs, uh_keypoint* d_kps, uint8_t* d_desc
  * inv_sigma[i] = 1/scaleFactors[octave] (float, :230), weight[i] = 1 or 0.5 for unstable points (:215-216).
  * Outputs: pose (row-major 4x4 float), bad[i] (1 = outlier: the reference marks DMatch::imgIdx = -1), outer iterations of the
  * four rounds.  Returns the inlier count (>= 0, solvePnp's return value) or a negative UH_E* code.
+ * Degenerate matches are not refused, they are solved as the reference solves them (tests/golden/pnp_hard_golden.npz): zero
+ * information everywhere fails every factorisation (one iteration of ten trials per round, the pose comes back as it went in);
+ * a map point on the camera plane of the input pose makes the sums and lambda non-finite (one trial per round, no match is
+ * relabelled, the pose comes back as it went in).
  * ------------------------------------------------------------------------ */
 typedef struct uh_pnp uh_pnp;
 int  uh_pnp_create(uh_ctx* ctx, uh_pnp** out);

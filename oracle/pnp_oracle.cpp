@@ -11,11 +11,25 @@
 // oracle_pnp_solve_stereo adds  typesg2o.h:521-588  EdgeStereoSE3ProjectXYZOnlyPose (cam_project rounds 1/z to float, the Jacobian uses
 // the double 1/z) for matches with depth > 0, built as pnpsolver.cpp:205-276 does (kp_ur = x - mbf / depth in float, weight doubled,
 // Huber sqrt(7.815), relabelling at 7.815); pinned against tests/golden/pnp_stereo_golden.npz (real g2o) by tests/test_track_oracle.py.
+// oracle_pnp_trace is oracle_pnp_solve_stereo with a record of the control flow (OraclePnpTrace below) and one test hook; the arithmetic
+// is that of the other entries.  Pinned against tests/golden/pnp_hard_golden.npz (real g2o, rarely taken branches) by tests/test_pnp_hard.py.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <limits>
 #include <vector>
+
+// What oracle_pnp_trace reports, per round r and outer iteration i at [10 * r + i] (tests/oracle_lib.py mirrors the layout).
+struct OraclePnpTrace {
+    int32_t trials[40];         // Levenberg trials the iteration took (g2o: G2OBatchStatistics::levenbergIterations)
+    int32_t accepted[40];       // the number of the trial that was accepted, counted from 1 (always the iteration's last), or -1
+    int32_t fails[40];          // trials whose 6x6 factorisation failed
+    int32_t lam_nonfinite[40];  // 1: lambda went non-finite and the loop was left before its increment
+    int32_t reason[40];         // why nothing followed the iteration, bits: 1 ten trials, 2 rho == 0, 4 non-finite lambda (Levenberg's
+                                // Terminate), 8 the float chi2 did not decrease, 16 the budget of ten iterations is spent; 0: another follows
+    double w2_applied[40];      // max |omega|^2 over the steps the iteration applied (accepted or not)
+    double w2_accepted[40];     // |omega|^2 of the accepted step, 0 without one
+};
 
 namespace {
 
@@ -43,14 +57,15 @@ void quat_to_R(const double* q, double R[9]) {
     R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy; R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
-void pose_oplus(Pose& T, const double d[6]) {   // T <- exp(d) * T, se3quat.h:276-311
+// small_angle_only (test hook of oracle_pnp_trace): the constants of the theta < 1e-5 branch at every theta >= 0.5 as well
+void pose_oplus(Pose& T, const double d[6], bool small_angle_only = false) {   // T <- exp(d) * T, se3quat.h:276-311
     const double w[3] = {d[0], d[1], d[2]}, u[3] = {d[3], d[4], d[5]};
     const double theta = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
     const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
     double O2[9];
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) O2[r * 3 + c] = O[r * 3] * O[c] + O[r * 3 + 1] * O[3 + c] + O[r * 3 + 2] * O[6 + c];
     double a, b, c1, c2;
-    if (theta < 0.00001) { a = 1; b = 0.5; c1 = 0.5; c2 = 1.0 / 6.0; }
+    if (theta < 0.00001 || (small_angle_only && theta >= 0.5)) { a = 1; b = 0.5; c1 = 0.5; c2 = 1.0 / 6.0; }
     else { a = std::sin(theta) / theta; b = (1 - std::cos(theta)) / (theta * theta); c1 = b; c2 = (theta - std::sin(theta)) / std::pow(theta, 3); }
     double R[9], V[9];
     for (int i = 0; i < 9; i++) { const double I = (i % 4 == 0) ? 1.0 : 0.0; R[i] = I + a * O[i] + b * O2[i]; V[i] = I + c1 * O[i] + c2 * O2[i]; }
@@ -81,7 +96,10 @@ struct PnP {
     Pose T;
     std::vector<char> active, robust;
     std::vector<double> err, chi2;
-    double H[36], b[6], x[6], lambda = -1, ni = 2;
+    double H[36], b[6], x[6] = {0, 0, 0, 0, 0, 0}, lambda = -1, ni = 2;   // (g2o's solution vector starts as zeros, solver.cpp:57)
+    OraclePnpTrace* tr = nullptr;   // oracle_pnp_trace only
+    int tr_at = 0;                  // 10 * round + iteration
+    bool small_angle_only = false;  // test hook, see pose_oplus
 
     void edge_error(int e, const double R[9], double& ex, double& ey, double pc[3]) const {
         const float* X = p3d + 3 * e;
@@ -162,14 +180,16 @@ struct PnP {
             }
         }
     }
-    bool solve(double lam) {   // 6x6 LDL^T
+    // 6x6 LDL^T.  Fails as Eigen's SimplicialLDLT does (g2o's LinearSolverEigen): on a pivot that is exactly zero, and on nothing else — a
+    // non-finite pivot goes through and leaves a non-finite step.  x is left as it was on failure (so is g2o's solution vector).
+    bool solve(double lam) {
         double M[36], L[36] = {0}, d[6];
         for (int i = 0; i < 36; i++) M[i] = H[i] + ((i % 7 == 0) ? lam : 0.0);
         for (int j = 0; j < 6; j++) {
             double dj = M[j * 6 + j];
             for (int k = 0; k < j; k++) dj -= L[j * 6 + k] * L[j * 6 + k] * d[k];
             d[j] = dj;
-            if (dj == 0.0 || !std::isfinite(dj)) return false;
+            if (dj == 0.0) return false;
             for (int i = j + 1; i < 6; i++) { double v = M[i * 6 + j]; for (int k = 0; k < j; k++) v -= L[i * 6 + k] * L[j * 6 + k] * d[k]; L[i * 6 + j] = v / dj; }
         }
         for (int i = 0; i < 6; i++) { double v = b[i]; for (int k = 0; k < i; k++) v -= L[i * 6 + k] * x[k]; x[i] = v; }
@@ -187,7 +207,16 @@ struct PnP {
         do {
             const Pose bak = T;
             const bool ok2 = solve(lambda);
-            if (ok2) pose_oplus(T, x);
+            // (also after a failed factorisation, with the step left over: optimization_algorithm_levenberg.cpp:104-109.  pnp.hip evaluates
+            // the unchanged pose there instead: the same up to rounding while the step left over is zero, as it is when the first factorisation
+            // of a round fails — a zero pivot after an accepted step has not been seen)
+            pose_oplus(T, x, small_angle_only);
+            const double w2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+            if (tr) {
+                tr->trials[tr_at]++;
+                if (!ok2) tr->fails[tr_at]++;
+                else if (w2 > tr->w2_applied[tr_at]) tr->w2_applied[tr_at] = w2;
+            }
             compute_errors();
             tempChi = robust_chi2();
             if (!ok2) tempChi = std::numeric_limits<double>::max();
@@ -202,24 +231,28 @@ struct PnP {
                 lambda *= std::max(1. / 3., alpha);
                 ni = 2;
                 currentChi = tempChi;
+                if (tr) { tr->accepted[tr_at] = qmax + 1; tr->w2_accepted[tr_at] = w2; }
             } else {
                 lambda *= ni; ni *= 2; T = bak;
-                if (!std::isfinite(lambda)) break;
+                if (!std::isfinite(lambda)) { if (tr) tr->lam_nonfinite[tr_at] = 1; break; }
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
+        if (tr) tr->reason[tr_at] = (qmax == 10 ? 1 : 0) | (rho == 0 ? 2 : 0) | (!std::isfinite(lambda) ? 4 : 0);
         return !(qmax == 10 || rho == 0 || !std::isfinite(lambda));
     }
-    int optimize(int iterations) {
+    int optimize(int iterations, int round) {
         float prev = std::numeric_limits<float>::max(), cur = prev, diff = prev;
         bool ok = true;
         int done = 0;
         for (int i = 0; i < iterations && ok && diff > 0.f; i++) {
             std::swap(prev, cur);
+            tr_at = 10 * round + i;
             ok = lm_solve(i);
             cur = (float)robust_chi2();
             diff = prev - cur;
             ++done;
+            if (tr) tr->reason[tr_at] |= (!(diff > 0.f) ? 8 : 0) | (i + 1 >= iterations ? 16 : 0);
         }
         return done;
     }
@@ -242,7 +275,7 @@ static int pnp_run(PnP& s, const float* pose_f2g, int n, float* pose_out, uint8_
     if (n > 0)
         for (int it = 0; it < 4; it++) {
             s.T = T0;                                   // every round restarts from the input pose (:354)
-            iters_out[it] = s.optimize(10);
+            iters_out[it] = s.optimize(10, it);
             int nGood = 0;
             double R[9]; quat_to_R(s.T.q, R);
             for (int e = 0; e < n; e++) {
@@ -272,11 +305,9 @@ extern "C" int oracle_pnp_solve(const float* pose_f2g, const float* intr4, int n
     return pnp_run(s, pose_f2g, n, pose_out, bad_out, iters_out, state_out);
 }
 
-// depth: n floats (Frame::getDepth(queryIdx); <= 0 = monocular edge) or NULL (= oracle_pnp_solve); bl = imageParams.bl
-extern "C" int oracle_pnp_solve_stereo(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
-                                       const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out,
-                                       int32_t* iters_out /*4*/, double* state_out /*7*/) {
-    PnP s;
+// the edges of oracle_pnp_solve_stereo: depth NULL or <= 0 = the monocular edge
+static void pnp_prepare(PnP& s, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma, const float* weight,
+                        const float* depth, float bl) {
     s.n = n; s.p3d = p3d; s.kp = kp; s.invsig = invsigma; s.weight = weight;
     s.fx = intr4[0]; s.fy = intr4[1]; s.cx = intr4[2]; s.cy = intr4[3];
     s.delta = (double)(float)std::sqrt(5.99);    // thHuber2D
@@ -294,5 +325,28 @@ extern "C" int oracle_pnp_solve_stereo(const float* pose_f2g, const float* intr4
             s.w3[e] = w;
         }
     }
+}
+
+// depth: n floats (Frame::getDepth(queryIdx); <= 0 = monocular edge) or NULL (= oracle_pnp_solve); bl = imageParams.bl
+extern "C" int oracle_pnp_solve_stereo(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
+                                       const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out,
+                                       int32_t* iters_out /*4*/, double* state_out /*7*/) {
+    PnP s;
+    pnp_prepare(s, intr4, n, p3d, kp, invsigma, weight, depth, bl);
+    return pnp_run(s, pose_f2g, n, pose_out, bad_out, iters_out, state_out);
+}
+
+// oracle_pnp_solve_stereo with its control flow recorded in *trace (zeroed here; accepted = -1 where no trial was accepted).
+// small_angle_only != 0 is a test hook: SE3's exp keeps its small-angle constants at |omega| >= 0.5, i.e. the step of a solver whose
+// large-rotation branch is wrong (tests/test_pnp_hard.py looks at what of the fixture such a solver misses).
+extern "C" int oracle_pnp_trace(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
+                                const float* weight, const float* depth, float bl, int small_angle_only, float* pose_out, uint8_t* bad_out,
+                                int32_t* iters_out /*4*/, double* state_out /*7*/, OraclePnpTrace* trace) {
+    PnP s;
+    std::memset(trace, 0, sizeof(*trace));
+    for (int i = 0; i < 40; i++) trace->accepted[i] = -1;
+    s.tr = trace;
+    s.small_angle_only = small_angle_only != 0;
+    pnp_prepare(s, intr4, n, p3d, kp, invsigma, weight, depth, bl);
     return pnp_run(s, pose_f2g, n, pose_out, bad_out, iters_out, state_out);
 }

@@ -458,12 +458,15 @@ pnp = PnPSolver(ctx)
 
 def pnp_case(seed):
     r = np.random.default_rng(seed)
-    n = int(r.integers(8, 3500))
-    pr = synth.pnp_problem(n, seed % 100000, outlier_frac=float(r.choice([0.0, 0.15, 0.4])), pose_noise=float(r.choice([0.01, 0.03, 0.08])))
+    n = int(r.integers(1, 3500))
+    pr = synth.pnp_problem(n, seed % 100000, outlier_frac=float(r.choice([0.0, 0.15, 0.4])), pose_noise=float(r.choice([0.01, 0.03, 0.08, 0.5, 0.7])))
     g = pnp.solvePnp(pr["pose"], pr["intr"], pr["p3d"], pr["kp"], pr["invsig"], pr["weight"])
     o = oracle_lib.pnp_solve(L, pr)
-    err = float(np.abs(g["state"] - o["state"]).max())
-    return g["ngood"] == o["ngood"] and (g["bad"] == o["bad"]).all() and g["iters"].tolist() == o["iters"].tolist() and err < 1e-6, (n, g["ngood"], o["ngood"], err)
+    fg, fo = np.isfinite(g["state"]), np.isfinite(o["state"])   # non-finite states: the same values in the same places
+    same_nonfinite = bool((fg == fo).all()) and np.array_equal(g["state"][~fg], o["state"][~fo], equal_nan=True)
+    err = float(np.abs(g["state"][fg & fo] - o["state"][fg & fo]).max()) if (fg & fo).any() else 0.0
+    return (g["ngood"] == o["ngood"] and (g["bad"] == o["bad"]).all() and g["iters"].tolist() == o["iters"].tolist() and same_nonfinite and err < 1e-6,
+            (n, g["ngood"], o["ngood"], err))
 
 run("pnp", pnp_case)
 tot = sum(len(b) for _, b in report.values())

@@ -7,6 +7,9 @@
 // by depth (:205-276: kp_ur = x - mbf / depth in float, robust weight doubled, Huber sqrt(7.815)), four rounds of optimize(10) from the
 // input pose, relabelling against each edge's own MaxChi (5.99 / 7.815), robust kernels dropped from the third round, early stop below
 // 10 inliers.  The solver stack (Levenberg, block solver, Eigen LDLT, SE3 exp, robustification) is g2o's own code.
+//
+// Two entry points on the one graph: pnp_stereo_ref_solve (tests/golden/pnp_stereo_golden.npz) and pnp_hard_ref_solve
+// (tests/golden/pnp_hard_golden.npz), which also reports the Levenberg trials of every iteration and can jitter the map points.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -15,7 +18,9 @@
 
 #include "g2o/core/base_unary_edge.h"
 #include "g2o/core/base_vertex.h"
+#include "g2o/core/batch_stats.h"
 #include "g2o/core/block_solver.h"
+#include "g2o/core/hyper_graph_action.h"
 #include "g2o/core/optimization_algorithm_levenberg.h"
 #include "g2o/core/robust_kernel.h"
 #include "g2o/core/sparse_optimizer.h"
@@ -121,15 +126,65 @@ class WeightedHuber : public g2o::RobustKernel {   // WeightedHubberRobustKernel
     }
 };
 
+// The Levenberg trials of every iteration, as g2o counts them itself (G2OBatchStatistics::levenbergIterations, incremented by
+// OptimizationAlgorithmLevenberg::solve at the head of every trial through G2OBatchStatistics::globalStats()).  The optimiser's own
+// setComputeBatchStatistics(true) would also recompute the active errors after every iteration, at the pose Levenberg RESTORED after a
+// rejected last trial — the solver under test relabels with the errors of the last trial g2o evaluated (pnpsolver.cpp:358-371 reads
+// e->chi2()), so that switch changes the outcome.  This action only points the global statistics at the iteration's own record.
+class TrialCounter : public g2o::HyperGraphAction {
+   public:
+    g2o::G2OBatchStatistics stat[10];
+    void reset() { for (auto& s : stat) s = g2o::G2OBatchStatistics(); g2o::G2OBatchStatistics::setGlobalStats(0); }
+    g2o::HyperGraphAction* operator()(const g2o::HyperGraph*, Parameters* p = 0) override {
+        auto* it = dynamic_cast<ParametersIteration*>(p);
+        if (it && it->iteration >= 0 && it->iteration < 10) g2o::G2OBatchStatistics::setGlobalStats(&stat[it->iteration]);
+        return this;
+    }
+};
+
+// jitter > 0: a seeded relative perturbation of the map points in the graph's doubles, |rel| <= 1e-12 (the screen of
+// tests/golden/make_pnp_hard_golden.py: a case whose outcome hangs on rounding noise cannot pin a solver)
+struct Jitter {
+    uint64_t s;
+    explicit Jitter(int seed) : s(0x9E3779B97F4A7C15ull * (uint64_t)(seed + 1)) {}
+    double next() {   // splitmix64 -> [-1, 1)
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+    }
+};
+
+// trials_out: NULL, or 4 x 10 ints (the Levenberg trials of every iteration of every round); jitter: 0 = none
+int solve_impl(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma, const float* weight,
+               const float* depth, float bl, float* pose_out, uint8_t* bad_out, int32_t* iters_out, double* state_out, int32_t* trials_out, int jitter);
+
 }  // namespace
 
 // depth: n floats (<= 0 = monocular match) or NULL; bl = the stereo baseline.  Returns the inlier count.
 extern "C" int pnp_stereo_ref_solve(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
                                     const float* weight, const float* depth, float bl, float* pose_out, uint8_t* bad_out, int32_t* iters_out,
                                     double* state_out) {
+    return solve_impl(pose_f2g, intr4, n, p3d, kp, invsigma, weight, depth, bl, pose_out, bad_out, iters_out, state_out, nullptr, 0);
+}
+
+// the same solve; trials_out [4][10]: Levenberg trials per round and iteration (0 where none ran); jitter: 0, or the seed of a relative
+// 1e-12 perturbation of the map points
+extern "C" int pnp_hard_ref_solve(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma,
+                                  const float* weight, const float* depth, float bl, int jitter, float* pose_out, uint8_t* bad_out,
+                                  int32_t* iters_out, double* state_out, int32_t* trials_out) {
+    return solve_impl(pose_f2g, intr4, n, p3d, kp, invsigma, weight, depth, bl, pose_out, bad_out, iters_out, state_out, trials_out, jitter);
+}
+
+namespace {
+int solve_impl(const float* pose_f2g, const float* intr4, int n, const float* p3d, const float* kp, const float* invsigma, const float* weight,
+               const float* depth, float bl, float* pose_out, uint8_t* bad_out, int32_t* iters_out, double* state_out, int32_t* trials_out, int jitter) {
     g2o::SparseOptimizer opt;
     auto linearSolver = g2o::make_unique<g2o::LinearSolverEigen<g2o::BlockSolver_6_3::PoseMatrixType>>();
-    opt.setAlgorithm(new g2o::OptimizationAlgorithmLevenberg(g2o::make_unique<g2o::BlockSolver_6_3>(std::move(linearSolver))));
+    auto* lm = new g2o::OptimizationAlgorithmLevenberg(g2o::make_unique<g2o::BlockSolver_6_3>(std::move(linearSolver)));
+    lm->setWriteDebug(false);   // (a failed factorisation would leave a debug.txt in the working directory; the arithmetic is the same)
+    opt.setAlgorithm(lm);
     auto toSE3 = [&]() {
         Eigen::Matrix3d R;
         R << pose_f2g[0], pose_f2g[1], pose_f2g[2], pose_f2g[4], pose_f2g[5], pose_f2g[6], pose_f2g[8], pose_f2g[9], pose_f2g[10];
@@ -140,6 +195,18 @@ extern "C" int pnp_stereo_ref_solve(const float* pose_f2g, const float* intr4, i
     cam->setId(0);
     cam->setFixed(false);
     opt.addVertex(cam);
+    TrialCounter counter;
+    if (trials_out) {
+        opt.addPreIterationAction(&counter);
+        for (int i = 0; i < 40; i++) trials_out[i] = 0;
+    }
+    Jitter jit(jitter);
+    auto point = [&](int i) {
+        Eigen::Vector3d X(p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]);
+        if (jitter > 0)
+            for (int a = 0; a < 3; a++) X[a] *= 1.0 + 1e-12 * jit.next();
+        return X;
+    };
     const float Chi2D = 5.99, Chi3D = 7.815;
     const float thHuber2D = std::sqrt(5.99), thHuber3D = std::sqrt(7.815);
     const float fx = intr4[0], fy = intr4[1], cx = intr4[2], cy = intr4[3];
@@ -151,7 +218,7 @@ extern "C" int pnp_stereo_ref_solve(const float* pose_f2g, const float* intr4, i
         auto* rk = new WeightedHuber();
         if (d <= 0) {
             auto* e = new MonoEdge();
-            e->Xw = Eigen::Vector3d(p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]);
+            e->Xw = point(i);
             e->fx = fx; e->fy = fy; e->cx = cx; e->cy = cy;
             e->setVertex(0, cam);
             e->setMeasurement(Eigen::Vector2d(kp[2 * i], kp[2 * i + 1]));
@@ -171,7 +238,7 @@ extern "C" int pnp_stereo_ref_solve(const float* pose_f2g, const float* intr4, i
             rk->D = thHuber3D; rk->W = edge_weight;
             e->setRobustKernel(rk);
             e->fx = fx; e->fy = fy; e->cx = cx; e->cy = cy; e->bf = mbf;
-            e->Xw[0] = p3d[3 * i]; e->Xw[1] = p3d[3 * i + 1]; e->Xw[2] = p3d[3 * i + 2];
+            e->Xw = point(i);
             opt.addEdge(e);
             ed[i] = e; maxChi[i] = Chi3D;
         }
@@ -182,7 +249,12 @@ extern "C" int pnp_stereo_ref_solve(const float* pose_f2g, const float* intr4, i
         for (int it = 0; it < 4; it++) {
             cam->setEstimate(toSE3());
             opt.initializeOptimization(0);
+            if (trials_out) counter.reset();
             iters_out[it] = opt.optimize(10);
+            if (trials_out) {
+                g2o::G2OBatchStatistics::setGlobalStats(0);
+                for (int i = 0; i < iters_out[it] && i < 10; i++) trials_out[10 * it + i] = counter.stat[i].levenbergIterations;
+            }
             int nGood = 0;
             for (int i = 0; i < n; i++) {
                 if (bad[i]) ed[i]->computeError();
@@ -201,5 +273,7 @@ extern "C" int pnp_stereo_ref_solve(const float* pose_f2g, const float* intr4, i
     const g2o::SE3Quat& T = cam->estimate();
     state_out[0] = T.rotation().x(); state_out[1] = T.rotation().y(); state_out[2] = T.rotation().z(); state_out[3] = T.rotation().w();
     state_out[4] = T.translation()[0]; state_out[5] = T.translation()[1]; state_out[6] = T.translation()[2];
+    if (trials_out) opt.removePreIterationAction(&counter);
     return good;
 }
+}  // namespace

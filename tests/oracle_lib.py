@@ -323,6 +323,35 @@ def pnp_solve_stereo(L, pr, depth, bl):
     return out
 
 
+class PnpTrace(C.Structure):
+    """OraclePnpTrace of oracle/pnp_oracle.cpp: per round r and iteration i at [10 * r + i]."""
+    _fields_ = [(k, C.c_int32 * 40) for k in ("trials", "accepted", "fails", "lam_nonfinite", "reason")] + \
+               [(k, C.c_double * 40) for k in ("w2_applied", "w2_accepted")]
+
+
+# bits of PnpTrace.reason
+PNP_TEN_TRIALS, PNP_RHO_ZERO, PNP_LAMBDA_NONFINITE, PNP_NO_DECREASE, PNP_BUDGET = 1, 2, 4, 8, 16
+
+
+def pnp_trace(L, pr, depth=None, bl=0.0, small_angle_only=False):
+    """oracle_pnp_trace: pnp_solve_stereo's outputs plus `trace`, a dict of [4, 10] arrays (the fields of PnpTrace).
+    small_angle_only: the test hook that keeps SE3 exp's small-angle constants at |omega| >= 0.5."""
+    import numpy as np
+
+    n = pr["n"]
+    out = dict(pose=np.zeros(16, np.float32), bad=np.zeros(max(n, 1), np.uint8), iters=np.zeros(4, np.int32), state=np.zeros(7, np.float64))
+    f = L.oracle_pnp_trace
+    f.restype = I
+    f.argtypes = [VP, VP, I, VP, VP, VP, VP, VP, C.c_float, I, VP, VP, VP, VP, C.POINTER(PnpTrace)]
+    dep = None if depth is None else np.ascontiguousarray(depth, np.float32)
+    t = PnpTrace()
+    out["ngood"] = f(P(pr["pose"]), P(pr["intr"]), n, P(pr["p3d"]), P(pr["kp"]), P(pr["invsig"]), P(pr["weight"]), None if dep is None else P(dep), float(bl),
+                     int(small_angle_only), P(out["pose"]), P(out["bad"]), P(out["iters"]), P(out["state"]), C.byref(t))
+    out["bad"] = out["bad"][:n]
+    out["trace"] = {k: np.array(getattr(t, k)).reshape(4, 10) for k, _ in PnpTrace._fields_}
+    return out
+
+
 def track_pose(L, fr, table, prev, local_ids, pose0, depth=None, bl=0.0, pose_for_map=None, prev_min_desc_dist=75.0, prev_max_repj_dist=15.0,
                map_min_desc_dist=100.0, map_radius_tracked=4.0, map_radius_lost=15.0, min_inliers=30):
     """oracle_track_pose (oracle/track_oracle.cpp): the tracker's control flow of one frame on a map held as the reference holds it.

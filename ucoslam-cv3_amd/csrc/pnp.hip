@@ -124,11 +124,13 @@ __device__ __forceinline__ double rsq_nr(double x) {   // x > 0
 
 // Hu = the 21 upper-triangle entries row by row (H[a][c], a <= c, at index tri(a, c))
 __device__ __forceinline__ constexpr int tri(int a, int c) { return a * 6 - a * (a - 1) / 2 + (c - a); }
-__device__ __forceinline__ bool p_solve6(const double* Hu, const double* b, double lam, double* x) {   // LDL^T, fails on a zero / non-finite pivot
+__device__ __forceinline__ bool p_solve6(const double* Hu, const double* b, double lam, double* x) {   // LDL^T, fails on a zero pivot
     // Right-looking (every pivot's column updates the trailing block at once) with the right-hand side carried along, then a
     // column-oriented back substitution: the dependent chain per pivot is reciprocal -> scale -> one fma instead of a dot product
     // of growing length — this routine sits on the serial path of every trial.  Fully unrolled, compile-time indices: the system
-    // stays in registers.  x is left alone on failure.
+    // stays in registers.  x is left alone on failure.  Only a pivot that is exactly zero is a failure, as in Eigen's SimplicialLDLT behind
+    // g2o's LinearSolverEigen: a non-finite pivot goes through and leaves a non-finite step, the trial is evaluated at a non-finite pose and
+    // every edge keeps a non-finite chi2 (no match is relabelled from it: a comparison with NaN is false).
     double a[6][6], L[6][6], id[6], y[6];
 #pragma unroll
     for (int i = 0; i < 6; i++) {
@@ -140,7 +142,7 @@ __device__ __forceinline__ bool p_solve6(const double* Hu, const double* b, doub
 #pragma unroll
     for (int j = 0; j < 6; j++) {
         const double dj = a[j][j];
-        ok = ok && !(dj == 0.0 || !isfinite(dj));
+        ok = ok && !(dj == 0.0);
         id[j] = rcp_nr(dj);
 #pragma unroll
         for (int i = j + 1; i < 6; i++) L[i][j] = a[i][j] * id[j];
@@ -854,7 +856,10 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_solve_kernel(PnpArgs A) {
                 {
                     double m = 0;
 #pragma unroll
-                    for (int j = 0; j < 6; j++) m = fmax(fabs(s_H[tri(j, j)]), m);
+                    for (int j = 0; j < 6; j++) {   // computeLambdaInit's std::max(fabs(h), m): a NaN diagonal entry is kept unless a number follows it
+                        const double h = fabs(s_H[tri(j, j)]);
+                        m = h < m ? m : h;
+                    }
                     lambda = 1e-5 * m;
                 }
                 prevChi = FLT_MAX; curChi = FLT_MAX; done = 0; stale_H = false; it = 0;
