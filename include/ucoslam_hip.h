@@ -518,6 +518,64 @@ int  uh_ba_get_marker_results(uh_ba* ba, float* pose_g2m_out /* n_markers x 16 *
                               double* edge_chi2_out /* n_edges or NULL */);
 
 /* ------------------------------------------------------------------------
+ * Loop-closure pose graph — replaces loopClosurePathOptimizationg2o (src/optimization/graphoptsim3.cpp:74-168): g2o's Levenberg
+ * (lambda_init 1e-16, 20 iterations, BlockSolver_7_3 with an exact LDL^T) over VertexSim3Expmap / EdgeSim3 (typesg2o.h:673-749) on
+ * the essential graph of all keyframes.
+ *   vertices  one per pose: Sim3(Quaternion(R), t, 1) from the float 4x4; vertex idx_new starts at expected_pose_new, vertex idx_old is
+ *             fixed; fix_scale is VertexSim3Expmap::_fix_scale of every vertex
+ *   edges     EdgeSim3 (vertex 0 = edge_i, vertex 1 = edge_j) with measurement Sjw * Siw^-1 from the INPUT poses (only the closing
+ *             edge (idx_new, idx_old), in either order, takes expected_pose_new for the new keyframe), information weight * I7;
+ *             the same pair may occur more than once and in either order
+ *   Jacobians g2o's numeric central differences with step (double)fd_delta — BaseBinaryEdge::_delta_der, a float, 1e-9f
+ *   results   [sR | t/s] rounded to float for EVERY pose (a pose without edges and the fixed one go through the quaternion round trip
+ *             and nothing else), and the Sim3 state
+ * Refused before anything is launched: UH_EINVAL for a NULL array, idx_new / idx_old or an edge end out of range, an edge from a
+ * pose to itself, idx_new == idx_old, a non-finite weight, params out of range; UH_ECAPACITY for more than UH_POSEGRAPH_MAX_POSES
+ * poses (the system is dense: 7 n x 7 n doubles, 1.6 GB at the cap).  Without any edge the poses come back after the conversion
+ * round trip with 0 iterations.  The call is synchronous on the context's stream.
+ * ------------------------------------------------------------------------ */
+#define UH_POSEGRAPH_MAX_POSES 2048
+#define UH_POSEGRAPH_MAX_ITERS 256
+typedef struct uh_posegraph uh_posegraph;
+
+typedef struct uh_posegraph_problem {
+    int32_t n_poses;
+    const float*   pose_f2g;           /* n_poses x 16, row-major 4x4 */
+    int32_t n_edges;
+    const int32_t* edge_i;             /* n_edges: index of the edge's first pose */
+    const int32_t* edge_j;             /* n_edges: index of its second pose */
+    const float*   edge_weight;        /* n_edges, or NULL = 1 for every edge */
+    int32_t idx_new, idx_old;          /* IdClosesLoopNew / IdClosesLoopOld as indices */
+    const float*   expected_pose_new;  /* 16 */
+    int32_t fix_scale;
+} uh_posegraph_problem;
+
+typedef struct uh_posegraph_params {   /* 0 = the reference's value */
+    int32_t max_iters;                 /* 20; at most UH_POSEGRAPH_MAX_ITERS */
+    double  lambda_init;               /* 1e-16 */
+    float   fd_delta;                  /* 1e-9f; widened to double as g2o widens _delta_der */
+} uh_posegraph_params;
+
+typedef struct uh_posegraph_info {
+    int32_t iterations;                /* what SparseOptimizer::optimize returns */
+    double  lambda;                    /* the final damping */
+    double  chi2_before, chi2_after;   /* at the initial and at the returned estimates */
+} uh_posegraph_info;
+
+int  uh_posegraph_create(uh_ctx* ctx, uh_posegraph** out);
+void uh_posegraph_destroy(uh_posegraph* pg);
+/* the argument checks of uh_posegraph_optimize alone (host only, no device needed); params may be NULL */
+int  uh_posegraph_check_problem(const uh_posegraph_problem* problem, const uh_posegraph_params* params);
+int  uh_posegraph_optimize(uh_posegraph* pg, const uh_posegraph_problem* problem, const uh_posegraph_params* params /* or NULL */);
+/* every output may be NULL.  state8: qx qy qz qw tx ty tz s; trials: Levenberg trials of each iteration (`iterations` entries, room for
+ * max_iters) */
+int  uh_posegraph_get_results(uh_posegraph* pg, float* poses_out /* n_poses x 16 */, double* state8_out /* n_poses x 8 */,
+                              uh_posegraph_info* info, int32_t* trials_out);
+/* the first linearisation of the latest optimize: per edge the error (7), d error / d vertex 0 and / d vertex 1 (7 x 7 row-major
+ * each, zero for the fixed vertex) and the measurement (8, as state8) */
+int  uh_posegraph_debug_linearisation(uh_posegraph* pg, double* err_out, double* Ji_out, double* Jj_out, double* meas_out);
+
+/* ------------------------------------------------------------------------
  * Bag of words — replaces fbow::Vocabulary::transform / fBow::score:
  *   3rdparty/fbow/fbow/fbow.h:54-116 (class surface), fbow.cpp:51-90 (transform with level), :92-143 (normalised
  *   transform), :171-190 (stream format), :192-243 (score); UcoSLAM call site keyframedatabase.cpp:310-322 (level 3).

@@ -426,4 +426,84 @@ class ProjectionMatcher {
     uh_projmatch* h_ = nullptr;
 };
 
+// ---- ucoslam::loopClosurePathOptimizationg2o (optimization/graphoptsim3.cpp:74-168) ---------------------------------------
+// The pose type is a template parameter (the reference's is cv::Mat, CV_32F 4x4): posegraph_pose_ptr(pose) must give its 16
+// row-major floats; the overloads below cover anything with data() — for cv::Mat add one that returns m.ptr<float>().
+template <class Pose> inline auto posegraph_pose_ptr(Pose& p) -> decltype(p.data()) { return p.data(); }
+template <class Pose> inline auto posegraph_pose_ptr(const Pose& p) -> decltype(p.data()) { return p.data(); }
+
+struct FlatPoseGraph {
+    std::vector<uint32_t> id_of;         // index -> key of optimPoses, in key order (std::map's, which is the reference's vertex order too)
+    std::vector<float> poses;            // id_of.size() x 16
+    std::vector<int32_t> edge_i, edge_j;
+    std::vector<float> weight;           // one per edge: edgeWeight[CovisGraph::join(first, second)], 1 where the map has none
+    float expected[16];
+    int32_t idx_new = -1, idx_old = -1;
+    int32_t fix_scale = 0;
+    uh_posegraph_problem view() const {
+        return uh_posegraph_problem{(int32_t)id_of.size(), poses.data(), (int32_t)edge_i.size(), edge_i.data(), edge_j.data(), weight.data(), idx_new, idx_old,
+                                    expected, fix_scale};
+    }
+};
+
+// CovisGraph::join (map_types/covisgraph.h:102-109): the smaller id in the high word
+inline uint64_t covis_join(uint32_t a, uint32_t b) { if (a > b) std::swap(a, b); return ((uint64_t)a << 32) | b; }
+
+// Throws std::length_error above UH_POSEGRAPH_MAX_POSES, so that a caller can keep "g2o" for such a map, and std::runtime_error for an
+// id that optimPoses does not hold (the reference asserts).
+template <class Pose>
+FlatPoseGraph flatten_posegraph(const std::vector<std::pair<uint32_t, uint32_t>>& edges, uint32_t IdClosesLoopNew, uint32_t IdClosesLoopOld,
+                                const Pose& expectedPoseNew, const std::map<uint32_t, Pose>& optimPoses, bool bFixScale,
+                                const std::map<uint64_t, float>& edgeWeight) {
+    if (optimPoses.size() > (size_t)UH_POSEGRAPH_MAX_POSES)
+        throw std::length_error("loopClosurePathOptimization: " + std::to_string(optimPoses.size()) + " keyframes exceed the dense solver's cap of " +
+                                std::to_string(UH_POSEGRAPH_MAX_POSES));
+    FlatPoseGraph f;
+    std::map<uint32_t, int32_t> index;
+    for (const auto& kv : optimPoses) {
+        index[kv.first] = (int32_t)f.id_of.size();
+        f.id_of.push_back(kv.first);
+        const float* M = posegraph_pose_ptr(kv.second);
+        f.poses.insert(f.poses.end(), M, M + 16);
+    }
+    auto at = [&](uint32_t id) {
+        const auto it = index.find(id);
+        if (it == index.end()) throw std::runtime_error("loopClosurePathOptimization: keyframe " + std::to_string(id) + " is not in optimPoses");
+        return it->second;
+    };
+    for (const auto& e : edges) {
+        f.edge_i.push_back(at(e.first));
+        f.edge_j.push_back(at(e.second));
+        const auto w = edgeWeight.find(covis_join(e.first, e.second));
+        f.weight.push_back(w != edgeWeight.end() ? w->second : 1.f);
+    }
+    f.idx_new = at(IdClosesLoopNew);
+    f.idx_old = at(IdClosesLoopOld);
+    std::memcpy(f.expected, posegraph_pose_ptr(expectedPoseNew), sizeof f.expected);
+    f.fix_scale = bFixScale ? 1 : 0;
+    return f;
+}
+
+// graphoptsim3.cpp:156-165: every pose of optimPoses is replaced by its corrected [sR | t/s]
+template <class Pose>
+void apply_posegraph_results(std::map<uint32_t, Pose>& optimPoses, const FlatPoseGraph& f, const float* poses) {
+    for (size_t k = 0; k < f.id_of.size(); k++) std::memcpy(posegraph_pose_ptr(optimPoses.at(f.id_of[k])), poses + 16 * k, 16 * sizeof(float));
+}
+
+// the reference's argument list behind the context
+template <class Pose>
+void loopClosurePathOptimization(Context& ctx, const std::vector<std::pair<uint32_t, uint32_t>>& edges, uint32_t IdClosesLoopNew, uint32_t IdClosesLoopOld,
+                                 const Pose& expectedPoseNew, std::map<uint32_t, Pose>& optimPoses, bool bFixScale,
+                                 const std::map<uint64_t, float>& edgeWeight = std::map<uint64_t, float>()) {
+    const FlatPoseGraph f = flatten_posegraph(edges, IdClosesLoopNew, IdClosesLoopOld, expectedPoseNew, optimPoses, bFixScale, edgeWeight);
+    uh_posegraph* g = nullptr;
+    check(uh_posegraph_create(ctx.get(), &g));
+    std::unique_ptr<uh_posegraph, void (*)(uh_posegraph*)> hold(g, uh_posegraph_destroy);
+    const uh_posegraph_problem pr = f.view();
+    check(uh_posegraph_optimize(g, &pr, nullptr));
+    std::vector<float> poses(16 * f.id_of.size());
+    check(uh_posegraph_get_results(g, poses.data(), nullptr, nullptr, nullptr));
+    apply_posegraph_results(optimPoses, f, poses.data());
+}
+
 }  // namespace ucoslam_hip
