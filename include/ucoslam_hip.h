@@ -634,7 +634,7 @@ typedef struct uh_match_filter_args {
     const int32_t* q_octave; const float* q_angle; const float* q_pt;   /* query und_kpts fields; q_pt (x,y) only for F12 */
     const int32_t* t_octave; const float* t_angle; const float* t_pt;   /* train und_kpts fields */
     const float* scale_factors;     /* query frame scaleFactors (only with F12) */
-    const float* F12;               /* row-major 3x3 fundamental matrix or NULL (no epipolar gate) */
+    const float* F12;               /* row-major 3x3 fundamental matrix (getFund12: uh_fundamental_12) or NULL (no epipolar gate) */
     float min_desc_dist, nn_match_ratio;
     int32_t check_orientation, max_octave_diff;
     /* sizes of the arrays above; > 0: every mapped keypoint index / octave is range-checked (UH_EINVAL), 0: unchecked */
@@ -666,7 +666,7 @@ typedef struct uh_bow_frame {
 typedef struct uh_bow_match_args {
     uh_bow_frame query, train;
     const float* scale_factors; int32_t n_levels;   /* query frame scaleFactors (only with F12) */
-    const float* F12;               /* row-major 3x3 fundamental matrix (getFund12) or NULL */
+    const float* F12;               /* row-major 3x3 fundamental matrix (getFund12: uh_fundamental_12) or NULL */
     float min_desc_dist, nn_match_ratio;
     int32_t check_orientation, max_octave_diff;
 } uh_bow_match_args;
@@ -674,6 +674,109 @@ typedef struct uh_bowmatch uh_bowmatch;
 int  uh_bowmatch_create(uh_ctx* ctx, uh_bowmatch** out);
 void uh_bowmatch_destroy(uh_bowmatch* bm);
 int  uh_bowmatch_match(uh_bowmatch* bm, const uh_bow_match_args* args, uh_dmatch* out, int cap);
+
+/* getFund12 (framematcher.cpp:58-64) -> computeF12(eye, Ktrain, RT, Kquery) (misc.cpp:893-920): the F12 that uh_match_filter_args::F12
+ * and uh_bow_match_args::F12 take for one (train, query) pair.  Host only.  Both cameras as fx fy cx cy; RT = FQ2T, the row-major
+ * float 4x4 query.pose_f2g * train.pose_f2g.inv(); F12_out row-major 3x3.  The upper-triangular K is inverted in closed form; every
+ * cv::Mat product of the chain accumulates its elements in double and rounds once, as OpenCV's float GEMM does — UNPINNED, like the
+ * products of uh_newpoints_run (a fixture of computeF12 outputs from a machine with OpenCV would pin it). */
+int  uh_fundamental_12(const float* intr4_train, const float* intr4_query, const float* RT, float* F12_out /* 9 */);
+
+/* ------------------------------------------------------------------------
+ * New map points — replaces, for one new keyframe and all its covisible neighbours, the loop of MapManager that follows matchEpipolar
+ * (src/utils/mapmanager.cpp:10087-10696, line numbers of the de-obfuscated text): Triangulate(newKF, neighbour, RT, matches)
+ * (src/basictypes/misc.cpp:923-1041), the distance-ratio / octave-ratio check, and the merge per keypoint of the new keyframe.
+ *
+ * Roles (misc.cpp's names mislead): the new keyframe is Triangulate's `Train`, the neighbour its `Query`; RT = neighbour.pose_f2g *
+ * newKF.pose_f2g.inv() takes the new keyframe's camera to the neighbour's (p3dC2 = R p3dC1 + t); a match's trainIdx is a keypoint of
+ * the new keyframe, its queryIdx one of the neighbour.
+ *
+ * Per match, in this order (status code of the branch that refuses it):
+ *   1  cos of the two rays < 0 or > 0.9998 (:989-997)            6  chi2 of the reprojection in the new keyframe > max_chi2, weighted by
+ *   2  fourth component of A's null vector == 0 (:936)              1 / scaleFactor^2 of its keypoint's octave (:1017-1022)
+ *   3  a coordinate is not finite (:1003)                        7  the same in the neighbour (:1025-1031)
+ *   4  depth <= 0 in the new keyframe's camera (:1007)           8  distance of pg = pose_g2f * p3d to either camera centre is 0
+ *   5  depth <= 0 in the neighbour's camera (:1013)              9  ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor
+ *   0  accepted                                                     with ratioDist = dist1 / dist2, ratioOctave = sf_new[oct] / sf_nb[oct]
+ * ratio_factor is the reference's 1.5f * params.scaleFactor; max_chi2 its 5.998.
+ *
+ * Merge (:10416-10696): the accepted matches of all pairs, in pair order then match order, grouped by trainIdx.  Each group becomes one
+ * point, in ascending trainIdx: position and descriptor distance of the CHOSEN candidate, observations (new keyframe, trainIdx) then
+ * every candidate's (neighbour, queryIdx) in list order.  merge_rule picks the candidate:
+ *   UH_NEWPOINTS_MERGE_SMALLEST_OCTAVE  the first candidate whose neighbour keypoint has the strictly smallest octave — what the
+ *                                       reference's loop is written to find (and ORB-SLAM's intent)
+ *   UH_NEWPOINTS_MERGE_AS_COMPILED      the LAST candidate — what the reference does as compiled: the loop compares each octave with a
+ *                                       running minimum that it never assigns (:10525-10618), so every candidate wins in turn
+ *
+ * Float conventions: float expressions in the reference's written order without contraction.  Two things cannot follow the reference
+ * byte for byte, because it computes them inside OpenCV, which cannot be built here — both UNPINNED:
+ *   - the null vector: cv::SVD in float there; here a one-sided Jacobi in double on the float A, the three quotients rounded to float once
+ *   - the products taken through cv::Mat's operator* (P2 = K2 [R|t], R p + t, R' ray; the chain of uh_fundamental_12): each element
+ *     accumulated in double and rounded once (OpenCV's float GEMM); xn / cv::norm(xn) as a multiplication by (float)(1 / norm)
+ * One fixture of Triangulate outputs and one of computeF12 outputs, generated where OpenCV exists, would pin them.
+ *
+ * Refused with UH_EINVAL before anything is launched, uh_last_error() naming the pair and the match: a queryIdx / trainIdx outside
+ * the keypoint counts, an octave of a matched keypoint outside n_levels, a trainIdx twice within one pair (matchEpipolar's closing
+ * filter_ambiguous_train rules it out; the kernels rely on it), more than UH_NEWPOINTS_MAX_KPTS keypoints in the new keyframe (the
+ * merge is one workgroup), more than UH_NEWPOINTS_MAX_PAIRS pairs, a neighbour with more than 128 levels or 2^24 - 1 matches (a cell
+ * of the candidate table holds both).  The call is synchronous on the context's stream: one upload, two
+ * kernels, one download, one wait; the results are bit-reproducible run to run.
+ * ------------------------------------------------------------------------ */
+#define UH_NEWPOINTS_MAX_KPTS  16384
+#define UH_NEWPOINTS_MAX_PAIRS 1024
+#define UH_NEWPOINTS_MERGE_SMALLEST_OCTAVE 0
+#define UH_NEWPOINTS_MERGE_AS_COMPILED     1
+typedef struct uh_newpoints uh_newpoints;
+
+typedef struct uh_newpoints_pair {     /* one neighbour */
+    float RT[16];                      /* neighbour.pose_f2g * newKF.pose_f2g.inv(), row-major 4x4 */
+    float intr4[4];                    /* fx fy cx cy */
+    float cam_center[3];               /* Frame::getCameraCenter */
+    int32_t n_levels;
+    const float* scale_factors;        /* n_levels */
+    int32_t n_kpts;
+    const float* pt;                   /* n_kpts x 2, undistorted */
+    const int32_t* octave;             /* n_kpts */
+    int32_t n_matches;
+    const uh_dmatch* matches;          /* queryIdx = the neighbour's keypoint, trainIdx = the new keyframe's */
+} uh_newpoints_pair;
+
+typedef struct uh_newpoints_args {
+    float intr4[4];                    /* the new keyframe: fx fy cx cy */
+    float pose_g2f[16];                /* pose_f2g.inv() as the caller's Se3Transform gives it (camera -> global) */
+    float cam_center[3];
+    int32_t n_levels;
+    const float* scale_factors;
+    int32_t n_kpts;                    /* <= UH_NEWPOINTS_MAX_KPTS */
+    const float* pt;
+    const int32_t* octave;
+    int32_t n_pairs;
+    const uh_newpoints_pair* pairs;
+    float max_chi2;                    /* the reference: 5.998 */
+    float ratio_factor;                /* the reference: 1.5f * params.scaleFactor */
+    int32_t merge_rule;                /* UH_NEWPOINTS_MERGE_* */
+} uh_newpoints_args;
+
+/* Pointers into pinned memory owned by the handle, valid until its next run or its destruction (as uh_ba_results_view). */
+typedef struct uh_newpoints_result {
+    int32_t n_total;                   /* matches of all pairs; the per-match arrays are concatenated in pair order */
+    const uint8_t* status;             /* n_total: the codes above */
+    const float*   xyz_cam;            /* n_total x 3: Triangulate's return value, in the new keyframe's camera frame; NaN where it leaves NaN */
+    int32_t n_new;
+    int32_t n_obs;                     /* obs_ptr[n_new] */
+    const int32_t* kp_idx;             /* n_new, ascending: the keypoint of the new keyframe */
+    const float*   xyz_global;         /* n_new x 3: pg of the chosen candidate */
+    const float*   distance;           /* n_new: its match distance */
+    const int32_t* chosen_pair;        /* n_new */
+    const int32_t* chosen_match;       /* n_new: index in that pair's match list */
+    const int32_t* obs_ptr;            /* n_new + 1: CSR offsets into obs_pair / obs_kpt */
+    const int32_t* obs_pair;           /* -1 = the new keyframe itself (always a list's first entry), else the pair */
+    const int32_t* obs_kpt;            /* the keypoint in that frame */
+} uh_newpoints_result;
+
+int  uh_newpoints_create(uh_ctx* ctx, uh_newpoints** out);
+void uh_newpoints_destroy(uh_newpoints* np);
+int  uh_newpoints_run(uh_newpoints* np, const uh_newpoints_args* args, uh_newpoints_result* result);
 
 /* ------------------------------------------------------------------------
  * One frame stream sharded over the GPUs of a node (BASELINE config 5): pyramid levels of frame t, the map's train tiles

@@ -12,6 +12,7 @@
 // OpenCV, neither of which exists where this repository is built and tested, so they have never been compiled — INTEGRATION.md
 // sections 1 and 4 list them as the binding a maintainer adds inside the reference tree, on top of the classes below.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -504,6 +505,138 @@ void loopClosurePathOptimization(Context& ctx, const std::vector<std::pair<uint3
     std::vector<float> poses(16 * f.id_of.size());
     check(uh_posegraph_get_results(g, poses.data(), nullptr, nullptr, nullptr));
     apply_posegraph_results(optimPoses, f, poses.data());
+}
+
+// ---- ucoslam::Triangulate (basictypes/misc.h:65) and MapManager's new-point loop (utils/mapmanager.cpp:10087-10696) ------------
+// The frame type is a template parameter shaped like ucoslam::Frame: idx, pose_f2g (16 row-major floats through posegraph_pose_ptr),
+// und_kpts (elements with pt.x, pt.y, octave), scaleFactors (std::vector<float>) and imageParams with fx() fy() cx() cy()
+// (imageparams.h:52-55).
+inline void se3_inverse(const float* M, float* o) {   // Se3Transform::inv, basictypes/se3transform.h:89-107
+    o[0] = M[0]; o[1] = M[4]; o[2] = M[8]; o[4] = M[1]; o[5] = M[5]; o[6] = M[9]; o[8] = M[2]; o[9] = M[6]; o[10] = M[10];
+    o[3] = -(M[3] * o[0] + M[7] * o[1] + M[11] * o[2]);
+    o[7] = -(M[3] * o[4] + M[7] * o[5] + M[11] * o[6]);
+    o[11] = -(M[3] * o[8] + M[7] * o[9] + M[11] * o[10]);
+    o[12] = o[13] = o[14] = 0;
+    o[15] = 1;
+}
+inline void camera_center(const float* p, float c[3]) {   // Frame::getCameraCenter, map_types/frame.h:189-197
+    c[0] = -(p[3] * p[0] + p[7] * p[4] + p[11] * p[8]);
+    c[1] = -(p[3] * p[1] + p[7] * p[5] + p[11] * p[9]);
+    c[2] = -(p[3] * p[2] + p[7] * p[6] + p[11] * p[10]);
+}
+inline void mat44_product(const float* A, const float* B, float* C) {   // cv::Mat's operator* on CV_32F: double sums, one rounding (unpinned)
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double s = 0;
+            for (int k = 0; k < 4; k++) s += (double)A[4 * i + k] * (double)B[4 * k + j];
+            C[4 * i + j] = (float)s;
+        }
+}
+
+// the arrays uh_newpoints_run reads of one frame, owned
+struct NewPointsFrame {
+    float intr4[4], center[3];
+    std::vector<float> pt, scale_factors;
+    std::vector<int32_t> octave;
+    template <class Frame> explicit NewPointsFrame(const Frame& f) : scale_factors(f.scaleFactors.begin(), f.scaleFactors.end()) {
+        intr4[0] = f.imageParams.fx(); intr4[1] = f.imageParams.fy(); intr4[2] = f.imageParams.cx(); intr4[3] = f.imageParams.cy();
+        camera_center(posegraph_pose_ptr(f.pose_f2g), center);
+        pt.reserve(2 * f.und_kpts.size());
+        octave.reserve(f.und_kpts.size());
+        for (const auto& k : f.und_kpts) { pt.push_back(k.pt.x); pt.push_back(k.pt.y); octave.push_back((int32_t)k.octave); }
+    }
+    void fill(uh_newpoints_pair& p, const float* RT, const std::vector<uh_dmatch>& matches) const {
+        std::memcpy(p.RT, RT, sizeof p.RT);
+        std::memcpy(p.intr4, intr4, sizeof intr4);
+        std::memcpy(p.cam_center, center, sizeof center);
+        p.n_levels = (int32_t)scale_factors.size(); p.scale_factors = scale_factors.data();
+        p.n_kpts = (int32_t)octave.size(); p.pt = pt.data(); p.octave = octave.data();
+        p.n_matches = (int32_t)matches.size(); p.matches = matches.data();
+    }
+    void fill(uh_newpoints_args& a, const float* pose_f2g) const {
+        std::memcpy(a.intr4, intr4, sizeof intr4);
+        se3_inverse(pose_f2g, a.pose_g2f);
+        std::memcpy(a.cam_center, center, sizeof center);
+        a.n_levels = (int32_t)scale_factors.size(); a.scale_factors = scale_factors.data();
+        a.n_kpts = (int32_t)octave.size(); a.pt = pt.data(); a.octave = octave.data();
+    }
+};
+
+struct NewPointInfo {   // MapManager::NewPointInfo (utils/mapmanager.h) + the keypoint of the new keyframe
+    uint32_t kp_idx;
+    float xyz[3];       // the reference's `pose` (cv::Point3f, global coordinates)
+    float dist;
+    std::vector<std::pair<uint32_t, uint32_t>> frame_kpt;   // (frame idx, keypoint): the new keyframe first
+};
+
+class NewPointCreator {
+   public:
+    explicit NewPointCreator(Context& ctx) { check(uh_newpoints_create(ctx.get(), &h_)); }
+    ~NewPointCreator() { uh_newpoints_destroy(h_); }
+    NewPointCreator(const NewPointCreator&) = delete;
+    NewPointCreator& operator=(const NewPointCreator&) = delete;
+
+    // matchesPerNeighbour[j] = matchEpipolar(neighbour j, MODE_UNASSIGNED, RT) of a FrameMatcher set up on newKF: queryIdx in the
+    // neighbour, trainIdx in newKF.  scaleFactorParam = System::getParams().scaleFactor.  mergeRule: UH_NEWPOINTS_MERGE_* (see ucoslam_hip.h:
+    // AS_COMPILED is what the reference binary does, SMALLEST_OCTAVE what its source is written to do).
+    template <class Frame>
+    std::vector<NewPointInfo> create(const Frame& newKF, const std::vector<const Frame*>& neighbours, const std::vector<std::vector<uh_dmatch>>& matchesPerNeighbour,
+                                     float scaleFactorParam, int mergeRule = UH_NEWPOINTS_MERGE_SMALLEST_OCTAVE, float maxChi2 = 5.998f) {
+        if (neighbours.size() != matchesPerNeighbour.size()) throw std::runtime_error("NewPointCreator::create: one match list per neighbour");
+        const NewPointsFrame nf(newKF);
+        std::vector<NewPointsFrame> nb;
+        nb.reserve(neighbours.size());
+        std::vector<uh_newpoints_pair> pairs(neighbours.size());
+        float inv[16], RT[16];
+        se3_inverse(posegraph_pose_ptr(newKF.pose_f2g), inv);
+        for (size_t j = 0; j < neighbours.size(); j++) {
+            nb.emplace_back(*neighbours[j]);
+            mat44_product(posegraph_pose_ptr(neighbours[j]->pose_f2g), inv, RT);   // mapmanager.cpp:10045-10062
+            nb.back().fill(pairs[j], RT, matchesPerNeighbour[j]);
+        }
+        uh_newpoints_args a{};
+        nf.fill(a, posegraph_pose_ptr(newKF.pose_f2g));
+        a.n_pairs = (int32_t)pairs.size(); a.pairs = pairs.data();
+        a.max_chi2 = maxChi2; a.ratio_factor = 1.5f * scaleFactorParam; a.merge_rule = mergeRule;
+        uh_newpoints_result r{};
+        check(uh_newpoints_run(h_, &a, &r));
+        last_ = r;
+        std::vector<NewPointInfo> out(r.n_new);
+        for (int i = 0; i < r.n_new; i++) {
+            NewPointInfo& p = out[i];
+            p.kp_idx = (uint32_t)r.kp_idx[i];
+            for (int c = 0; c < 3; c++) p.xyz[c] = r.xyz_global[3 * i + c];
+            p.dist = r.distance[i];
+            for (int k = r.obs_ptr[i]; k < r.obs_ptr[i + 1]; k++)
+                p.frame_kpt.emplace_back(r.obs_pair[k] < 0 ? (uint32_t)newKF.idx : (uint32_t)neighbours[r.obs_pair[k]]->idx, (uint32_t)r.obs_kpt[k]);
+        }
+        return out;
+    }
+    const uh_newpoints_result& last_result() const { return last_; }   // per-match status / xyz_cam of the latest create (valid until the next)
+   private:
+    uh_newpoints* h_ = nullptr;
+    uh_newpoints_result last_{};
+};
+
+// misc.h:65 — as many points as matches, NaN where the triangulation is refused; RT = Query.pose_f2g * Train.pose_f2g.inv()
+template <class TrainView, class QueryView>
+std::vector<std::array<float, 3>> Triangulate(Context& ctx, const TrainView& Train, const QueryView& Query, const float RT[16], const std::vector<uh_dmatch>& matches,
+                                              float maxChi2 = 5.998f) {
+    const NewPointsFrame tf(Train), qf(Query);
+    uh_newpoints_pair pair{};
+    qf.fill(pair, RT, matches);
+    uh_newpoints_args a{};
+    tf.fill(a, posegraph_pose_ptr(Train.pose_f2g));
+    a.n_pairs = 1; a.pairs = &pair;
+    a.max_chi2 = maxChi2; a.ratio_factor = 1.f; a.merge_rule = UH_NEWPOINTS_MERGE_SMALLEST_OCTAVE;   // the ratio check comes after Triangulate's surface
+    uh_newpoints* h = nullptr;
+    check(uh_newpoints_create(ctx.get(), &h));
+    std::unique_ptr<uh_newpoints, void (*)(uh_newpoints*)> hold(h, uh_newpoints_destroy);
+    uh_newpoints_result r{};
+    check(uh_newpoints_run(h, &a, &r));
+    std::vector<std::array<float, 3>> out(matches.size());
+    for (size_t i = 0; i < out.size(); i++) out[i] = {r.xyz_cam[3 * i], r.xyz_cam[3 * i + 1], r.xyz_cam[3 * i + 2]};
+    return out;
 }
 
 }  // namespace ucoslam_hip
