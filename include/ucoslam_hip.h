@@ -1035,6 +1035,66 @@ int uh_knn_debug_push_cycles(uh_knn* knn, int k, int n, long long* out3);
  * MUST hold 512 entries (4096 bytes: the whole stamp block is copied) */
 int uh_pnp_debug_clocks(uh_pnp* pnp, int on, long long* out512);
 
+/* ------------------------------------------------------------------------
+ * Relocalisation RANSAC: PnPSolver::solvePnPRansac (src/optimization/pnpsolver.cpp:36-114), batched over the candidate keyframes of one
+ * lost frame (System::relocalize runs it once per candidate) and over the hypotheses of each.  Lives on the uh_pnp object.
+ *
+ * Per problem and iteration `it`: the four matches samples[4 it .. 4 it + 3] give a three-point pose (the reference calls cv::solvePnP
+ * with SOLVEPNP_P3P): EVERY real solution with positive point distances of the three-point problem of samples 0-2 on pixels normalised
+ * with intr4, in double; among them the one with the smallest squared reprojection error of sample 3 (normalised coordinates, double),
+ * the lowest solution index on ties, solutions numbered in ascending (distance of sample 2) / (distance of sample 0).  No solution —
+ * no real root, coincident or collinear sample points (sin^2 of the angle at sample 0 below 1e-16), non-finite sample data: the
+ * iteration is skipped and its count is -1.  The pose goes matrix -> Rodrigues vector in double (direct axis-angle extraction, own
+ * branches below sin(theta) = 1e-5), then through Se3Transform(rv, tv): cast to float rt[6], the 3x4 built in float in the written order
+ * (se3transform.h:143-176; cos / sin in double on the float angle, rounded once).  Every match j is then tested as :75-100 do it, in
+ * float in the written order: inlier iff distX * distX + distY * distY < 5.99f and not getViewCos(camCenter) < 0.5.  There is no test of
+ * the depth's sign (a point behind the camera can be an inlier); a zero depth gives inf / NaN and a false comparison.  The FIRST
+ * iteration with the strictly largest count >= 1 wins: rt6 / pose are its pose and inliers its inliers in ascending j; ok = 1 iff it has
+ * at least 4.  With fewer the pose is STILL the winner's (the reference overwrites posef2g_io before it returns false); with no winner
+ * rt6 = rt6_in.  pose = Se3Transform::set(rt6), 4x4 row-major.
+ * UNPINNED (no OpenCV exists in the build container): (a) the three-point solver — any method meeting the contract above gives the same
+ * answers up to rounding on well-conditioned samples; the closed form used is in csrc/p3p_math.hpp; (b) cv::Rodrigues re-orthonormalises
+ * by SVD first; (c) whether the unqualified cos / sin of se3transform.h:157-158 are the double or the float functions; (d) OpenCV 4 orders
+ * the solutions by the error over all four points, OpenCV 3 by the fourth.
+ * One packed upload, two launches (whatever the number of problems), one download, ONE wait on the context's stream.  A problem with
+ * n < 4 is valid: ok = 0, n_inliers = 0, best_iter = -1, rt6 = rt6_in, counts all -1, and nothing is launched for it.  Refused with
+ * UH_EINVAL before anything is launched: NULL arrays with n > 0, cap < n, a sample index outside [0, n), an index twice within one
+ * sample, n / iters / n_problems beyond the caps below, iters < 1, non-finite intrinsics.  Non-finite coordinates are NOT refused: they
+ * are scored as the reference scores them.  The hypothesis masks live in device scratch of the uh_pnp object: 8 * ceil(n / 64) bytes per
+ * hypothesis (128 MiB when every cap is reached at once).
+ * ------------------------------------------------------------------------ */
+#define UH_RANSAC_MAX_PROBLEMS 64
+#define UH_RANSAC_MAX_ITERS    1024
+#define UH_RANSAC_MAX_MATCHES  16384
+typedef struct uh_ransac_problem {      /* one candidate keyframe */
+    int32_t n;                          /* matches; < 4 is valid and gives ok = 0 without a launch for it */
+    const float* p3d;                   /* n x 3  MapPoint::getCoordinates() */
+    const float* normal;                /* n x 3  MapPoint normal (getViewCos) */
+    const float* kp;                    /* n x 2  und_kpts[queryIdx].pt */
+    int32_t iters;                      /* maxIters, 1..UH_RANSAC_MAX_ITERS */
+    const int32_t* samples;             /* iters x 4 indices into the matches */
+    const float* rt6_in;                /* posef2g_io as it goes in (rvec, tvec) */
+} uh_ransac_problem;
+typedef struct uh_ransac_result {
+    int32_t ok, n_inliers, best_iter;   /* best_iter = -1: no hypothesis had an inlier */
+    float rt6[6], pose[16];
+    int32_t* inliers; int32_t cap;      /* in: buffer of >= n entries */
+    int32_t* counts;                    /* iters entries or NULL: count per hypothesis, -1 = skipped */
+} uh_ransac_result;
+int uh_pnp_ransac(uh_pnp* pnp, const float* intr4, int n_problems, const uh_ransac_problem* problems, uh_ransac_result* results);
+/* Host code: the samples the reference draws for n matches and `iters` iterations — std::random_shuffle of libstdc++ on ONE index vector
+ * that starts as the identity and carries its permutation from one iteration to the next (for i in 1..n-1: j = rand() % (i + 1), swap),
+ * the first four entries after each shuffle.  Draws (n - 1) * iters numbers from libc rand(): a host that calls srand as the reference's
+ * process would gets the reference's samples, and rand()'s state ends where the reference leaves it.  n >= 4. */
+int uh_pnp_ransac_samples(int n, int iters, int32_t* samples_out /* iters x 4 */);
+/* test hook: ONE hypothesis of a problem on the device, every solution in double (R row-major then t, 12 per solution), the pick
+ * (-1: skipped) and the chosen (rvec, tvec) before its cast to float */
+int uh_pnp_ransac_debug_hypothesis(uh_pnp* pnp, const float* intr4, const uh_ransac_problem* problem, int iter,
+        int32_t* n_solutions, double* Rt_4x12 /* every solution */, int32_t* chosen, double* rvec_tvec6);
+/* measurement hook (scripts/time_pnp_ransac.py): uniform_roots = 1 makes the calls that follow run the form of the hypothesis kernel in which
+ * every lane takes all four roots one after the other; 0 (the default) the form with one root per lane.  The results are equal bit for bit. */
+int uh_pnp_ransac_debug_form(uh_pnp* pnp, int uniform_roots);
+
 #ifdef __cplusplus
 }
 #endif

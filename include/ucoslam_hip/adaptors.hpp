@@ -371,6 +371,62 @@ class PnPSolver {
         bad.resize(n);
         return rc;
     }
+    // ---- ucoslam::PnPSolver::solvePnPRansac (pnpsolver.cpp:36-114), the relocalisation RANSAC (uh_pnp_ransac) ----
+    // frame: und_kpts[i].pt.x / .y and imageParams.fx() fy() cx() cy() as ucoslam::Frame has them; map: point_coordinates(id, float[3])
+    // and point_normal(id, float[3]) (MapPoint::getCoordinates / getNormal); matches_io: queryIdx = the frame's keypoint, trainIdx = the
+    // map point's id; pose_io: the se3's rt[6] (rvec, tvec).  Returns what the reference returns and leaves matches_io / pose_io as it
+    // leaves them: false below 4 matches (nothing touched, no sample drawn), false below 4 inliers (matches untouched, pose overwritten
+    // by the best hypothesis if one had an inlier), else the inliers in their order.  The samples come from libc rand() exactly as the
+    // reference's std::random_shuffle draws them (uh_pnp_ransac_samples).
+    template <class Frame, class MapView>
+    bool solvePnPRansac(const Frame& frame, const MapView& map, std::vector<uh_dmatch>& matches_io, float pose_io[6], int maxIters = 50) {
+        std::vector<std::vector<uh_dmatch>*> m{&matches_io};
+        std::vector<float*> p{pose_io};
+        return solvePnPRansac(frame, map, m, p, maxIters)[0];
+    }
+    // all candidate keyframes of one lost frame in one call (System::relocalize runs the function once per candidate): candidate c has
+    // matches_io[c] and pose_io[c]; the samples are drawn candidate by candidate in that order
+    template <class Frame, class MapView>
+    std::vector<bool> solvePnPRansac(const Frame& frame, const MapView& map, const std::vector<std::vector<uh_dmatch>*>& matches_io, const std::vector<float*>& pose_io,
+                                     int maxIters = 50) {
+        if (matches_io.size() != pose_io.size()) throw std::runtime_error("PnPSolver::solvePnPRansac: one pose per match list");
+        const size_t C = matches_io.size();
+        const float intr4[4] = {frame.imageParams.fx(), frame.imageParams.fy(), frame.imageParams.cx(), frame.imageParams.cy()};
+        std::vector<std::vector<float>> p3d(C), nrm(C), kp(C);
+        std::vector<std::vector<int32_t>> smp(C), inl(C);
+        std::vector<uh_ransac_problem> pr(C);
+        std::vector<uh_ransac_result> res(C);
+        for (size_t c = 0; c < C; c++) {
+            const std::vector<uh_dmatch>& m = *matches_io[c];
+            const size_t n = m.size();
+            p3d[c].resize(3 * n); nrm[c].resize(3 * n); kp[c].resize(2 * n); inl[c].resize(n ? n : 1);
+            for (size_t i = 0; i < n; i++) {
+                map.point_coordinates((uint32_t)m[i].trainIdx, &p3d[c][3 * i]);
+                map.point_normal((uint32_t)m[i].trainIdx, &nrm[c][3 * i]);
+                kp[c][2 * i] = frame.und_kpts[m[i].queryIdx].pt.x; kp[c][2 * i + 1] = frame.und_kpts[m[i].queryIdx].pt.y;
+            }
+            smp[c].assign(4 * (size_t)(maxIters > 0 ? maxIters : 0), 0);
+            if (n >= 4 && maxIters > 0) check(uh_pnp_ransac_samples((int)n, maxIters, smp[c].data()));
+            pr[c] = uh_ransac_problem{(int32_t)n, p3d[c].data(), nrm[c].data(), kp[c].data(), maxIters, smp[c].data(), pose_io[c]};
+            res[c] = uh_ransac_result{};
+            res[c].inliers = inl[c].data(); res[c].cap = (int32_t)n;
+        }
+        std::vector<bool> ok(C, false);
+        if (maxIters <= 0) {   // the reference's loop does not run: below four matches or not, nothing is found
+            return ok;
+        }
+        check(uh_pnp_ransac(p_, intr4, (int)C, pr.data(), res.data()));
+        for (size_t c = 0; c < C; c++) {
+            if (matches_io[c]->size() < 4) continue;
+            std::copy(res[c].rt6, res[c].rt6 + 6, pose_io[c]);   // (equal to what went in when no hypothesis had an inlier)
+            if (!res[c].ok) continue;
+            std::vector<uh_dmatch> kept((size_t)res[c].n_inliers);
+            for (int i = 0; i < res[c].n_inliers; i++) kept[i] = (*matches_io[c])[inl[c][i]];
+            *matches_io[c] = std::move(kept);
+            ok[c] = true;
+        }
+        return ok;
+    }
    private:
     std::shared_ptr<Context> ctx_;
     uh_pnp* p_ = nullptr;

@@ -930,7 +930,9 @@ struct uh_pnp {
     unsigned long long seq = 0;
     bool attr_set[2][2] = {{false, false}, {false, false}};   // the LDS attribute of pnp_solve_kernel<true, STEREO, MARKERS>, per [MARKERS][STEREO]
     long long* d_clk = nullptr;   // measurement hook (uh_pnp_debug_clocks)
-    ~uh_pnp() { if (d_clk) (void)hipFree(d_clk); }
+    void* ransac = nullptr;       // the relocalisation RANSAC's buffers (pnp_ransac.hip makes them on first use and names their deleter)
+    void (*ransac_free)(void*) = nullptr;
+    ~uh_pnp() { if (d_clk) (void)hipFree(d_clk); if (ransac && ransac_free) ransac_free(ransac); }
 };
 
 namespace {
@@ -1006,6 +1008,8 @@ int solve_dev(const char* fn, uh_pnp* p, const float* d_pose_f2g, const float* d
 
 namespace uh {
 uh_ctx* pnp_ctx(uh_pnp* p) { return p->ctx; }
+// the slot of the object for pnp_ransac.hip's state; a non-NULL `free_fn` (given once, when the state is made) is kept for the destructor
+void** pnp_ransac_slot(uh_pnp* p, void (*free_fn)(void*)) { if (free_fn) p->ransac_free = free_fn; return &p->ransac; }
 // the scratch a solve over n_cap matches needs beyond the LDS (uh_track_pose reserves it before its first launch)
 int pnp_reserve(uh_pnp* p, int n_cap, bool stereo) {
     return n_cap > kPnpLdsMatches ? p->d_work.reserve((size_t)n_cap * pnp_rec_bytes(stereo)) : UH_OK;
