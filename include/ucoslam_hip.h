@@ -1094,6 +1094,9 @@ int uh_pnp_ransac_debug_hypothesis(uh_pnp* pnp, const float* intr4, const uh_ran
 /* measurement hook (scripts/time_pnp_ransac.py): uniform_roots = 1 makes the calls that follow run the form of the hypothesis kernel in which
  * every lane takes all four roots one after the other; 0 (the default) the form with one root per lane.  The results are equal bit for bit. */
 int uh_pnp_ransac_debug_form(uh_pnp* pnp, int uniform_roots);
+/* test hook: the real roots of n <= UH_RANSAC_MAX_ITERS quartics A0 + A1 v + .. + A4 v^4 (A_nx5, five doubles each) as the hypothesis kernel's
+ * root finder returns them, one launch, one lane per quartic: ascending, the absent ones +inf, and their number */
+int uh_pnp_ransac_debug_roots(uh_pnp* pnp, int n, const double* A_nx5, double* roots_nx4, int32_t* n_roots);
 
 #ifdef __cplusplus
 }

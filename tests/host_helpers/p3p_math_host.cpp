@@ -23,6 +23,41 @@ int p3p_host_hypothesis(const float* intr4, const float* P, const float* px, dou
     return n;
 }
 
+// the quartic's real roots from its coefficients A[0..4] (A[i] of v^i) alone: r[4] ascending, the absent ones +inf; returns their number
+int p3p_host_roots(const double* A, double* r) {
+    p3p::Setup S{};
+    S.ok = true;
+    S.A0 = A[0]; S.A1 = A[1]; S.A2 = A[2]; S.A3 = A[3]; S.A4 = A[4];
+    return p3p::roots(S, r[0], r[1], r[2], r[3]);
+}
+
+// Which branches roots() takes on the quartic A5 = A0..A4, from the same expressions: form[0] = 1 it is solved in 1 / v, form[1] = 1 the
+// resolvent cubic takes its trigonometric form (0: Cardano), form[2] = 1 the biquadratic branch.  Returns 0 when nothing is solved.
+int p3p_host_roots_form(const double* A5, int* form) {
+    const bool rev = p3p::reversed_form(A5[0], A5[1], A5[2], A5[3], A5[4]);
+    const double a4 = rev ? A5[0] : A5[4], a3 = rev ? A5[1] : A5[3], a2 = A5[2], a1 = rev ? A5[3] : A5[1], a0 = rev ? A5[4] : A5[0];
+    form[0] = rev; form[1] = form[2] = 0;
+    if (!(std::fabs(a4) > 0.0)) return 0;
+    const double B = a3 / a4, Cc = a2 / a4, Dd = a1 / a4, E = a0 / a4;
+    const double B2 = B * B;
+    const double p = Cc - 0.375 * B2, q = Dd - 0.5 * B * Cc + 0.125 * B2 * B;
+    const double r = E - 0.25 * B * Dd + 0.0625 * B2 * Cc - (3.0 / 256.0) * B2 * B2;
+    const double c2 = p, c1 = 0.25 * p * p - r, c0 = -0.125 * q * q;
+    const double Q = (c2 * c2 - 3.0 * c1) / 9.0, R = (2.0 * c2 * c2 * c2 - 9.0 * c2 * c1 + 27.0 * c0) / 54.0;
+    form[1] = R * R < Q * Q * Q;
+    const double m = p3p::cubic_largest_root(c2, c1, c0);
+    form[2] = !(m > 1e-14 * (std::fabs(p) + std::sqrt(std::fabs(r)) + 1e-300));
+    return 1;
+}
+
+// the same for one hypothesis; A5: its coefficients.  Returns 0 for a degenerate sample.
+int p3p_host_form(const float* intr4, const float* P, const float* px, int* form, double* A5) {
+    p3p::Setup S;
+    p3p::setup(intr4, P, px, S);
+    A5[0] = S.A0; A5[1] = S.A1; A5[2] = S.A2; A5[3] = S.A3; A5[4] = S.A4;
+    return p3p_host_roots_form(A5, form) && S.ok;
+}
+
 void p3p_host_se3(const float* rt6, float* m12) {
     p3p::M34 M;
     p3p::se3_set(rt6, M);

@@ -2,8 +2,10 @@
 
 The three-point problem is solved by a route that is numerically different from csrc/p3p_math.hpp: the same cosine-rule equations,
 but with the roles of the points rotated (the unknown of the quartic is s1 / s2 where the kernel's is s3 / s1), the polynomial
-multiplied out by np.polymul, its roots taken from the companion matrix (np.roots) where the kernel uses Ferrari's closed form, and
-the pose from an SVD alignment (Kabsch) where the kernel builds two orthonormal frames.  Every solution can be checked on its own
+multiplied out by np.polymul, its roots taken from the companion matrix (np.roots) where the kernel uses Ferrari's closed form, the
+three distances refined by Newton with a general linear solve (where the kernel takes two steps with the adjugate written out), and
+the pose from an SVD alignment (Kabsch) where the kernel builds two orthonormal frames.  Both are judged by the 60-digit solve of
+tests/golden/p3p_golden.npz (tests/test_p3p_branches_host.py).  Every solution can be checked on its own
 (check_solution).  The fourth-point pick is in double; the matrix construction and the inlier test are float32 in the written order.
 """
 from __future__ import annotations
@@ -33,6 +35,31 @@ def _kabsch(P, C):
     d = np.sign(np.linalg.det(Vt.T @ U.T))
     R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
     return R, cm - R @ pm
+
+
+def _refine_distances(s, j, P):
+    """Newton on the three cosine-rule equations |s_a j_a - s_b j_b|^2 = |P_a - P_b|^2 in the three distances (np.linalg.solve on the
+    3 x 3 Jacobian, until the step no longer shrinks): u = N / D carries the quartic root's error magnified by 1 / D, and without this
+    the oracle was up to 3.3e-5 off a 60-digit solve on well-separated roots (tests/golden/make_p3p_golden.py)."""
+    pairs = ((0, 1), (0, 2), (1, 2))
+    d2 = np.array([(P[a] - P[b]) @ (P[a] - P[b]) for a, b in pairs])
+    cs = np.array([j[a] @ j[b] for a, b in pairs])
+    last = np.inf
+    for _ in range(6):
+        f = np.array([s[a] ** 2 + s[b] ** 2 - 2 * s[a] * s[b] * c for (a, b), c in zip(pairs, cs)]) - d2
+        J = np.zeros((3, 3))
+        for r, ((a, b), c) in enumerate(zip(pairs, cs)):
+            J[r, a], J[r, b] = 2 * (s[a] - s[b] * c), 2 * (s[b] - s[a] * c)
+        with np.errstate(all="ignore"):
+            try:
+                step = np.linalg.solve(J, f)
+            except np.linalg.LinAlgError:
+                break
+        size = np.abs(step).max()
+        if not np.isfinite(size) or size >= last:
+            break
+        s, last = s - step, size
+    return s
 
 
 def p3p(intr4, P, px):
@@ -73,6 +100,9 @@ def p3p(intr4, P, px):
         sA = np.sqrt(b2 / den)
         s = np.zeros(3)
         s[o[0]], s[o[1]], s[o[2]] = sA, u * sA, v * sA
+        s = _refine_distances(s, j[:3], P[:3])
+        if not (s > 0).all():
+            continue
         R, t = _kabsch(P[:3], s[:, None] * j[:3])
         if not (np.isfinite(R).all() and np.isfinite(t).all()):
             continue
@@ -115,8 +145,8 @@ def rodrigues_vec(R):
     w, V = np.linalg.eig(R)
     ax = np.real(V[:, np.argmin(np.abs(w - 1))])
     ax /= np.linalg.norm(ax)
-    if s >= 1e-7:
-        if ax @ sk < 0:
+    if s >= 1e-13:   # the skew part (absolute error 1e-16) still says which of a, -a it is; below 1e-7 this was taken for pi itself,
+        if ax @ sk < 0:   # which cost up to 1e-7 on R at pi - 1e-8 (tests/test_p3p_branches_host.py, family rot)
             ax = -ax
     else:   # theta = pi: the sign convention of the near-pi branch (first non-tiny component positive, as the diagonal form gives)
         big = np.argmax(np.abs(ax) > 1e-6)

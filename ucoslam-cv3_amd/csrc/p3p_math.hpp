@@ -2,15 +2,15 @@
 // PnPSolver::solvePnPRansac, src/optimization/pnpsolver.cpp:36-114 — a three-point pose from four matches (cv::solvePnP with
 // SOLVEPNP_P3P), Se3Transform::set (src/basictypes/se3transform.h:143-176) and the inlier test of :75-100.
 //
-// Double part (UNPINNED: no OpenCV exists to compare with; the contract is mathematical — every real solution with positive point
+// Double part (not pinned to OpenCV, none exists to compare with; pinned to a 60-digit solve, tests/golden/p3p_golden.npz; the contract is mathematical — every real solution with positive point
 // distances, the one with the smallest reprojection error of the fourth point, the lowest index on ties):
 //   Grunert's formulation.  Unit bearings j1 j2 j3, point distances s1 s2 s3, s2 = u s1, s3 = v s1, a = |P2 P3|, b = |P1 P3|,
 //   c = |P1 P2|, cos(alpha) = j2.j3, cos(beta) = j1.j3, cos(gamma) = j1.j2.  The cosine rule on the three sides gives
 //       u = N(v) / D(v),  N = (k - 1) v^2 - 2 k cos(beta) v + (k + 1),  D = 2 (cos(gamma) - v cos(alpha)),  k = (a^2 - c^2) / b^2
 //   and, put back into the side c,  N^2 + D^2 (1 - q (1 - 2 cos(beta) v + v^2)) - 2 cos(gamma) N D = 0,  q = c^2 / b^2: a quartic in v,
 //   whose coefficients are formed here by multiplying the polynomials out.  Its real roots come from Ferrari's resolvent (largest
-//   real root of the cubic, trigonometric or Cardano form) and two Newton steps on the quartic itself.  Solutions are numbered in
-//   ascending v = s3 / s1.  The pose of a root is the rigid motion between the orthonormal frames of the triangle in the world and in
+//   real root of the cubic, trigonometric or Cardano form) and two Newton steps on the quartic itself; where the leading coefficient
+//   is small against the others the same is done in w = 1 / v (reversed_form below).  Solutions are numbered in ascending v = s3 / s1.  The pose of a root is the rigid motion between the orthonormal frames of the triangle in the world and in
 //   the camera (exact for an exact root).
 // Float part: every float expression of the reference stays a float expression in its written order, without contraction (the library
 //   is built with -ffp-contract=off; the pragma below says the same to a host compiler); `1./x` is a double quotient rounded to
@@ -111,10 +111,10 @@ P3P_HD double cubic_largest_root(double a2, double a1, double a0) {
     return t;
 }
 
-P3P_HD double polish(const Setup& S, double v) {
+P3P_HD double polish(double a4, double a3, double a2, double a1, double a0, double v) {
     for (int it = 0; it < 2; it++) {
-        const double f = (((S.A4 * v + S.A3) * v + S.A2) * v + S.A1) * v + S.A0;
-        const double df = ((4.0 * S.A4 * v + 3.0 * S.A3) * v + 2.0 * S.A2) * v + S.A1;
+        const double f = (((a4 * v + a3) * v + a2) * v + a1) * v + a0;
+        const double df = ((4.0 * a4 * v + 3.0 * a3) * v + 2.0 * a2) * v + a1;
         const double w = df != 0.0 ? v - f / df : v;
         v = w == w ? w : v;
     }
@@ -123,11 +123,25 @@ P3P_HD double polish(const Setup& S, double v) {
 
 #define P3P_CSWAP(a, b) { const double lo = a < b ? a : b, hi = a < b ? b : a; a = lo; b = hi; }
 
+// The leading coefficient A4 = 4 (c^2 / b^2) (cos^2 A - cos^2 alpha) (A: the triangle's angle at P1) vanishes on a whole surface of
+// camera centres: P1 and the circumcircle, turned about the line P2 P3.  Ferrari's form divides by it, so below this share of the
+// largest coefficient (and below |A0|) the quartic is solved in w = 1 / v instead, A0 w^4 + A1 w^3 + A2 w^2 + A3 w + A4, whose
+// leading coefficient is then the larger of the two; a root w = 0 (A4 = 0 exactly) is the root of v at infinity and is no solution.
+constexpr double kSmallLead = 1e-4;
+
+P3P_HD bool reversed_form(double A0, double A1, double A2, double A3, double A4) {
+    const double m01 = fabs(A0) > fabs(A1) ? fabs(A0) : fabs(A1), m23 = fabs(A2) > fabs(A3) ? fabs(A2) : fabs(A3);
+    const double amax = m01 > m23 ? m01 : m23;
+    return fabs(A4) < kSmallLead * amax && fabs(A4) < fabs(A0);
+}
+
 // The real roots of the quartic in ascending order (r0 <= r1 <= ...), the absent ones +inf; returns their number.
 P3P_HD int roots(const Setup& S, double& r0, double& r1, double& r2, double& r3) {
     r0 = r1 = r2 = r3 = INFINITY;
-    if (!S.ok || !(fabs(S.A4) > 0.0)) return 0;
-    const double B = S.A3 / S.A4, Cc = S.A2 / S.A4, Dd = S.A1 / S.A4, E = S.A0 / S.A4;
+    const bool rev = reversed_form(S.A0, S.A1, S.A2, S.A3, S.A4);
+    const double a4 = rev ? S.A0 : S.A4, a3 = rev ? S.A1 : S.A3, a2 = S.A2, a1 = rev ? S.A3 : S.A1, a0 = rev ? S.A4 : S.A0;
+    if (!S.ok || !(fabs(a4) > 0.0)) return 0;
+    const double B = a3 / a4, Cc = a2 / a4, Dd = a1 / a4, E = a0 / a4;
     const double B2 = B * B;
     const double p = Cc - 0.375 * B2, q = Dd - 0.5 * B * Cc + 0.125 * B2 * B;
     const double r = E - 0.25 * B * Dd + 0.0625 * B2 * Cc - (3.0 / 256.0) * B2 * B2;
@@ -150,8 +164,12 @@ P3P_HD int roots(const Setup& S, double& r0, double& r1, double& r2, double& r3)
         if (dA >= 0.0) { const double sd = sqrt(dA); r0 = shift + 0.5 * (s + sd); r1 = shift + 0.5 * (s - sd); }
         if (dB >= 0.0) { const double sd = sqrt(dB); r2 = shift + 0.5 * (-s + sd); r3 = shift + 0.5 * (-s - sd); }
     }
-    r0 = r0 < INFINITY ? polish(S, r0) : r0; r1 = r1 < INFINITY ? polish(S, r1) : r1;
-    r2 = r2 < INFINITY ? polish(S, r2) : r2; r3 = r3 < INFINITY ? polish(S, r3) : r3;
+    r0 = r0 < INFINITY ? polish(a4, a3, a2, a1, a0, r0) : r0; r1 = r1 < INFINITY ? polish(a4, a3, a2, a1, a0, r1) : r1;
+    r2 = r2 < INFINITY ? polish(a4, a3, a2, a1, a0, r2) : r2; r3 = r3 < INFINITY ? polish(a4, a3, a2, a1, a0, r3) : r3;
+    if (rev) {   // back to v = 1 / w; w = 0 is the root at infinity (1 / inf = 0 would be a root at v = 0 that does not exist)
+        r0 = (r0 < INFINITY && r0 != 0.0) ? 1.0 / r0 : INFINITY; r1 = (r1 < INFINITY && r1 != 0.0) ? 1.0 / r1 : INFINITY;
+        r2 = (r2 < INFINITY && r2 != 0.0) ? 1.0 / r2 : INFINITY; r3 = (r3 < INFINITY && r3 != 0.0) ? 1.0 / r3 : INFINITY;
+    }
     P3P_CSWAP(r0, r1) P3P_CSWAP(r2, r3) P3P_CSWAP(r0, r2) P3P_CSWAP(r1, r3) P3P_CSWAP(r1, r2)
     return (r0 < INFINITY ? 1 : 0) + (r1 < INFINITY ? 1 : 0) + (r2 < INFINITY ? 1 : 0) + (r3 < INFINITY ? 1 : 0);
 }
@@ -212,7 +230,7 @@ P3P_HD bool back_substitute(const Setup& S, double v, Pose& T, double& err4) {
 }
 
 // Rotation matrix -> Rodrigues vector in double: theta = atan2(sin, cos) from the skew part and the trace; near theta = 0 the skew
-// part itself (first order); near theta = pi the axis from the diagonal, signs from the off-diagonal sums (the form cv::Rodrigues has).
+// part itself (first order); near theta = pi the axis from the symmetric part, its sign from the skew part.
 P3P_HD void rodrigues(const Pose& T, double& rx, double& ry, double& rz) {
     const double sx = T.r21 - T.r12, sy = T.r02 - T.r20, sz = T.r10 - T.r01;
     const double s = 0.5 * sqrt(sx * sx + sy * sy + sz * sz);
@@ -223,12 +241,16 @@ P3P_HD void rodrigues(const Pose& T, double& rx, double& ry, double& rz) {
         if (c > 0.0) {
             rx = 0.5 * sx; ry = 0.5 * sy; rz = 0.5 * sz;
         } else {
-            const double tx = 0.5 * (T.r00 + 1.0), ty = 0.5 * (T.r11 + 1.0), tz = 0.5 * (T.r22 + 1.0);
-            double ax = sqrt(tx > 0.0 ? tx : 0.0);
-            double ay = sqrt(ty > 0.0 ? ty : 0.0) * (T.r01 < 0.0 ? -1.0 : 1.0);
-            double az = sqrt(tz > 0.0 ? tz : 0.0) * (T.r02 < 0.0 ? -1.0 : 1.0);
-            if (fabs(ax) < fabs(ay) && fabs(ax) < fabs(az) && ((T.r12 > 0.0) != (ay * az > 0.0))) az = -az;
-            // the diagonal fixes the axis up to its sign; short of pi itself the skew part says which of the two it is
+            // (R + R') / 2 - c I = (1 - c) a a': the column of its largest diagonal entry is the axis times a factor of at least
+            // (1 - c) / sqrt(3), every component to an absolute 1e-16.  (The square roots of the diagonal, the form cv::Rodrigues has, lose
+            // half the digits of a component near zero: 2.8e-7 on R for a turn by pi about a coordinate axis.)
+            const double m00 = T.r00 - c, m11 = T.r11 - c, m22 = T.r22 - c;
+            const double m01 = 0.5 * (T.r01 + T.r10), m02 = 0.5 * (T.r02 + T.r20), m12 = 0.5 * (T.r12 + T.r21);
+            const bool c0 = m00 >= m11 && m00 >= m22, c1 = !c0 && m11 >= m22;
+            double ax = c0 ? m00 : (c1 ? m01 : m02), ay = c0 ? m01 : (c1 ? m11 : m12), az = c0 ? m02 : (c1 ? m12 : m22);
+            // at pi itself a and -a are the same turn: the first component that is not zero is made positive
+            if (ax < 0.0 || (ax == 0.0 && (ay < 0.0 || (ay == 0.0 && az < 0.0)))) { ax = -ax; ay = -ay; az = -az; }
+            // short of pi itself the skew part says which of the two it is
             const double sgn = ax * sx + ay * sy + az * sz < 0.0 ? -1.0 : 1.0;
             const double k = sgn * theta / sqrt(ax * ax + ay * ay + az * az);
             rx = ax * k; ry = ay * k; rz = az * k;

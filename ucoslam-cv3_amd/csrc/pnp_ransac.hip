@@ -252,6 +252,19 @@ __global__ __launch_bounds__(64) void pr_debug_kernel(PrDebugArgs a) {
     if (lane == 0) { a.out[54] = pick.n_solutions; a.out[55] = pick.chosen; }
 }
 
+// test hook: lane i takes the quartic A[5 i .. 5 i + 4] (A0 .. A4) through roots() and writes its four roots (absent: +inf) and their number
+__global__ __launch_bounds__(64) void pr_debug_roots_kernel(const double* A, int n, double* out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    p3p::Setup S{};
+    S.ok = true;
+    S.A0 = A[5 * (size_t)i]; S.A1 = A[5 * (size_t)i + 1]; S.A2 = A[5 * (size_t)i + 2]; S.A3 = A[5 * (size_t)i + 3]; S.A4 = A[5 * (size_t)i + 4];
+    double r0, r1, r2, r3;
+    const int k = p3p::roots(S, r0, r1, r2, r3);
+    double* o = out + 5 * (size_t)i;
+    o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3; o[4] = k;
+}
+
 struct PrState {
     uh::DevBuf d_in, d_work, d_out;
     uh::PinBuf h_in, h_out;
@@ -471,6 +484,40 @@ int uh_pnp_ransac_debug_hypothesis(uh_pnp* p, const float* intr4, const uh_ransa
     std::memcpy(rvec_tvec6, h + 48, 6 * sizeof(double));
     *n_solutions = (int32_t)h[54];
     *chosen = (int32_t)h[55];
+    return UH_OK;
+}
+
+int uh_pnp_ransac_debug_roots(uh_pnp* p, int n, const double* A_nx5, double* roots_nx4, int32_t* n_roots) {
+    UH_REQUIRE(n >= 0 && n <= UH_RANSAC_MAX_ITERS, "uh_pnp_ransac_debug_roots: %d quartics outside [0, %d]", n, UH_RANSAC_MAX_ITERS);
+    if (n == 0) return UH_OK;
+    UH_REQUIRE(A_nx5 && roots_nx4 && n_roots, "uh_pnp_ransac_debug_roots: NULL argument");
+    UH_REQUIRE(p, "uh_pnp_ransac_debug_roots: NULL solver");
+    PrState* st = pr_state(p);
+    uh_ctx* ctx = uh::pnp_ctx(p);
+    UH_HIP_CHECK(hipSetDevice(ctx->device));
+    int rc;
+    const size_t bytes = 5 * (size_t)n * sizeof(double);
+    if ((rc = st->d_in.reserve(bytes))) return rc;
+    if ((rc = st->d_out.reserve(bytes))) return rc;
+    std::vector<double> h(5 * (size_t)n);
+    double* dA = st->d_in.as<double>();
+    double* dout = st->d_out.as<double>();
+    hipError_t e = hipMemcpyAsync(dA, A_nx5, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        UH_LAUNCH(ctx, pr_debug_roots_kernel, dim3(uh_div_up(n, 64)), dim3(64), 0, (const double*)dA, n, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), dout, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);   // A_nx5 is pageable caller memory: nothing is left in flight
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        uh::set_error("uh_pnp_ransac_debug_roots: %s", hipGetErrorString(e));
+        return UH_ENODEVICE;
+    }
+    for (int i = 0; i < n; i++) {
+        for (int k = 0; k < 4; k++) roots_nx4[4 * (size_t)i + k] = h[5 * (size_t)i + k];
+        n_roots[i] = (int32_t)h[5 * (size_t)i + 4];
+    }
     return UH_OK;
 }
 

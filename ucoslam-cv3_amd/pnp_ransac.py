@@ -26,6 +26,7 @@ def _declare(L, sig):
     sig("uh_pnp_ransac", I, VP, VP, I, VP, VP)
     sig("uh_pnp_ransac_samples", I, I, I, VP)
     sig("uh_pnp_ransac_debug_form", I, VP, I)
+    sig("uh_pnp_ransac_debug_roots", I, VP, I, VP, VP, VP)
     sig("uh_pnp_ransac_debug_hypothesis", I, VP, VP, C.POINTER(_Problem), I, C.POINTER(C.c_int32), VP, C.POINTER(C.c_int32), VP)
 
 
@@ -115,6 +116,14 @@ class PnPRansac:
         Rt, rv = np.zeros((4, 12)), np.zeros(6)
         check(lib().uh_pnp_ransac_debug_hypothesis(self._h, np_ptr(intr), C.byref(q), int(it), C.byref(ns), np_ptr(Rt), C.byref(ch), np_ptr(rv)))
         return dict(n_solutions=int(ns.value), Rt=Rt[:ns.value].copy(), chosen=int(ch.value), rvec_tvec=rv)
+
+    def debug_roots(self, A):
+        """Test hook: A (n, 5) float64, the coefficients A0..A4 of n quartics -> (roots (n, 4) float64 ascending with +inf for the absent
+        ones, their number (n) int32), from the device's root finder."""
+        A = np.ascontiguousarray(A, np.float64).reshape(-1, 5)
+        r, k = np.zeros((len(A), 4)), np.zeros(len(A), np.int32)
+        check(lib().uh_pnp_ransac_debug_roots(self._h, len(A), np_ptr(A), np_ptr(r), np_ptr(k)))
+        return r, k
 
     def close(self):
         if self._own:
