@@ -183,8 +183,8 @@ __device__ __forceinline__ void schur_item_product(const double* ra, const doubl
 }
 
 // Tagged exchange words.  Element i of a buffer = words 2i (low 32 payload bits) and 2i+1 (high 32 bits), each with the round's tag in
-// its upper half; both are single-copy-atomic 64-bit write-through stores / L2-bypassing loads, so a word whose tag matches IS the
-// datum: no flag, no store drain, no ordering between words is needed.
+// its upper half; each is written and read whole (the two halves of ONE 16-byte write-through store / L2-bypassing load: tst, tld_raw),
+// so a word whose tag matches IS the datum: no flag, no store drain, no ordering between words is needed.
 typedef unsigned long long pword;
 struct TWord { pword lo, hi; };
 // The two words of an element are adjacent and 16-byte aligned: ONE 16-byte write-through store carries both (each 8-byte half is still
@@ -199,10 +199,20 @@ __device__ __forceinline__ void tst(pword* base, size_t i, double v, unsigned ta
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7FFFFFFF, 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(i * 16), 0, 16);
 }
-__device__ __forceinline__ TWord tld_raw(const pword* base, size_t i) {
+// The fetch is the store's mirror image: ONE 16-byte L2-bypassing (sc1) buffer load brings both words of an element — two 8-byte atomic
+// loads were twice the wave instructions and walked every 128-byte line twice, using half of it each time.  The load may tear BETWEEN
+// the halves (each half still arrives whole, which is all the store side assumes too): tok() validates each half by its own tag.
+// A buffer load is no atomic: every polling loop opens with tpoll_begin(), which keeps the compiler from lifting the load out of the spin.
+// (trsrc: the resource of a base pointer, built once outside the loops.)
+typedef __amdgpu_buffer_rsrc_t trsrc_t;
+__device__ __forceinline__ trsrc_t trsrc(const pword* base) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<pword*>(base), 0, 0x7FFFFFFF, 0x00020000); }
+__device__ __forceinline__ void tpoll_begin() { asm volatile("" ::: "memory"); }
+__device__ __forceinline__ TWord tld_raw(trsrc_t rs, size_t i) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(i * 16), 0, 16);   // aux 16 = sc1
     TWord w;
-    w.lo = __hip_atomic_load(base + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    w.hi = __hip_atomic_load(base + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    w.lo = (pword)r.x | ((pword)r.y << 32);
+    w.hi = (pword)r.z | ((pword)r.w << 32);
     return w;
 }
 __device__ __forceinline__ bool tok(const TWord& w, unsigned tag) { return (unsigned)(w.lo >> 32) == tag && (unsigned)(w.hi >> 32) == tag; }
@@ -589,16 +599,22 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
     };
     // up to eight tagged elements (first, first + stride, ...), all loads in flight together; spins until every tag matches
     // (need: bit u clear = element u is not wanted — nobody sent it this round — and is neither fetched nor waited for)
-    auto tload8 = [&](const pword* base, size_t first, size_t stride, int cnt, unsigned tag, double (&v)[8], unsigned need = 0xFFu) {
+    // A failed poll re-issues only the elements whose tag has not matched yet (todo: one bit per element; a matched v[u] is kept): the
+    // workgroups that spin do not fill the memory queues they are waiting on.
+    const trsrc_t rs_part = trsrc(q.part), rs_red = trsrc(q.red), rs_partC = trsrc(q.partC);
+    auto tload8 = [&](trsrc_t rs, size_t first, size_t stride, int cnt, unsigned tag, double (&v)[8], unsigned need = 0xFFu) {
         long long t0 = 0;
+        unsigned todo = need & ((1u << cnt) - 1u);
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = 0.0;
         for (;;) {
+            tpoll_begin();
             TWord w[8];
-            bool ok = true;
 #pragma unroll
-            for (int u = 0; u < 8; u++) if (u < cnt && ((need >> u) & 1u)) w[u] = tld_raw(base, first + u * stride);
+            for (int u = 0; u < 8; u++) if ((todo >> u) & 1u) w[u] = tld_raw(rs, first + u * stride);
 #pragma unroll
-            for (int u = 0; u < 8; u++) { if (u < cnt && ((need >> u) & 1u)) { ok = ok && tok(w[u], tag); v[u] = tval(w[u]); } else v[u] = 0.0; }
-            if (ok || give_up(t0)) return;
+            for (int u = 0; u < 8; u++) if (((todo >> u) & 1u) && tok(w[u], tag)) { v[u] = tval(w[u]); todo &= ~(1u << u); }
+            if (!todo || give_up(t0)) return;
         }
     };
     // (i / SL and h-range / HG by multiplication: a 32-bit division is ~25 instructions, and the hand-offs did nine of them per thread and trial;
@@ -841,7 +857,7 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
             for (int h = hg; used && h < G; h += 8 * HG) {   // eight elements in flight, added in ascending order
                 double v[8];
                 const int cnt = min(8, HG == 1 ? G - h : (int)__umulhi((unsigned)(G - h + HG - 1), hg_inv));   // (the multiplier of a division by one does not fit 32 bits)
-                tload8(q.part, src + (size_t)h * SL + e, (size_t)HG * SL, cnt, tagA, v);
+                tload8(rs_part, src + (size_t)h * SL + e, (size_t)HG * SL, cnt, tagA, v);
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
                     if (u >= cnt) continue;
@@ -974,7 +990,8 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
                     const size_t i_d1 = d1 < n ? (size_t)(OFF_CAM + sc1 * 27 + (a1 * 6 - a1 * (a1 - 1) / 2)) : (size_t)OFF_SC;
                     long long t0 = 0;
                     for (;;) {
-                        const TWord wm = tld_raw(q.red, OFF_SC + 2), wd0 = tld_raw(q.red, i_d0), wd1 = tld_raw(q.red, i_d1), wc = tld_raw(q.red, OFF_SC);
+                        tpoll_begin();
+                        const TWord wm = tld_raw(rs_red, OFF_SC + 2), wd0 = tld_raw(rs_red, i_d0), wd1 = tld_raw(rs_red, i_d1), wc = tld_raw(rs_red, OFF_SC);
                         m = lane == 0 ? tval(wm) : 0.0;
                         if (d0 < n) m = fmax(m, fabs(tval(wd0)));
                         if (d1 < n) m = fmax(m, fabs(tval(wd1)));
@@ -998,7 +1015,7 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
                 unsigned need = 0;
 #pragma unroll
                 for (int u = 0; u < 8; u++) need |= ((b0 == 0 ? asm_dst[u] : dst_of(b0 + tid + u * kPThreads)) >= 0 ? 1u : 0u) << u;
-                tload8(q.red, (size_t)(b0 + tid), kPThreads, cnt, tagB, rv, need);
+                tload8(rs_red, (size_t)(b0 + tid), kPThreads, cnt, tagB, rv, need);
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
                     const int t = b0 == 0 ? asm_dst[u] : dst_of(b0 + tid + u * kPThreads);
@@ -1140,11 +1157,12 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
                     const int cnt = lane < G ? (G - lane + 63) / 64 : 0;
                     long long t0 = 0;
                     for (;;) {
+                        tpoll_begin();
                         TWord wc[4], ws[4];
                         bool okw = true;
 #pragma unroll
-                        for (int u = 0; u < 4; u++) if (u < cnt) { wc[u] = tld_raw(q.partC, 4 * (size_t)(lane + 64 * u)); ws[u] = tld_raw(q.partC, 4 * (size_t)(lane + 64 * u) + 1); }
-                        const TWord wst = tld_raw(q.partC, 2);
+                        for (int u = 0; u < 4; u++) if (u < cnt) { wc[u] = tld_raw(rs_partC, 4 * (size_t)(lane + 64 * u)); ws[u] = tld_raw(rs_partC, 4 * (size_t)(lane + 64 * u) + 1); }   // (chi2 and scale: two consecutive elements, one address)
+                        const TWord wst = tld_raw(rs_partC, 2);
                         c = 0; sc = 0;
 #pragma unroll
                         for (int u = 0; u < 4; u++) if (u < cnt) { okw = okw && tok(wc[u], tagC) && tok(ws[u], tagC); c += tval(wc[u]); sc += tval(ws[u]); }
