@@ -1098,6 +1098,27 @@ int uh_pnp_ransac_debug_form(uh_pnp* pnp, int uniform_roots);
  * root finder returns them, one launch, one lane per quartic: ascending, the absent ones +inf, and their number */
 int uh_pnp_ransac_debug_roots(uh_pnp* pnp, int n, const double* A_nx5, double* roots_nx4, int32_t* n_roots);
 
+/* ------------------------------------------------------------------------
+ * Test hooks: ONE reduced-system solve S x = b (fp64 L D L^T without pivoting) in a chosen production form, on a system the caller gives.
+ * The hooks load [S; b^T] into the layout the form expects and call the device functions (form 7: the launches) the optimisers call;
+ * no problem has to be set.  S is n x n row-major and only its lower triangle is read; n = 6 nfree for the bundle adjustment.
+ *   form 1  row per lane, as the persistent kernel runs it          nfree 1..10     5  packed triangle in LDS, MFMA update   nfree 1..32
+ *   form 2  two rows per lane, as the persistent kernel runs it     nfree 11..16    6  row stride in HBM, MFMA update        nfree 1..64
+ *   form 3  row per lane, the launch chain's fused solve            nfree 1..10     7  blocked, 64-column panels (wide form) nfree 1..341
+ *   form 4  two rows per lane, the launch chain's fused solve       nfree 11..21
+ * x [n]: the solution, all zeros where the solve failed.  failed: 1 where a pivot was zero or not finite (the optimisers reject the trial).
+ * LD [(n + 1) x (n + 1)] row-major (may be NULL): the form's matrix as the factorisation leaves it — L strictly below the diagonal, row n =
+ * z = D^-1 L^-1 b (form 7 substitutes in that row, panel by panel from the last: only the last 64-column panel's part of it is still z).
+ * The diagonal holds D in forms 5, 6, 7; forms 1-4 do not keep D.  On and above the diagonal, and in column n, the forms leave
+ * what their updates happened to write (forms 2, 4: zeros on and above the diagonal of rows 0 .. n - 1; forms 5, 7: untouched words);
+ * the words the hook did not load from S and b are set to NaN beforehand in forms 1-6 (production leaves them uninitialised) and to zero in
+ * form 7 (production clears the matrix).  UH_EINVAL, nothing launched: a form outside 1..7, nfree outside the form's range, a NULL array.
+ * uh_posegraph_debug_solve: the same for the pose graph's blocked solve with its skip of empty 64-row groups (csrc/dense_ldlt.hpp), any
+ * 1 <= n <= 4096; LD as in form 7; x is whatever the substitution gave where the solve failed (the optimiser rejects that trial unseen).
+ * ------------------------------------------------------------------------ */
+int uh_ba_debug_solve(uh_ba* ba, int form, int nfree, const double* S, const double* b, double* x, double* LD, int* failed);
+int uh_posegraph_debug_solve(uh_posegraph* pg, int n, const double* S, const double* b, double* x, double* LD, int* failed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,23 @@ def _declare(L, sig):
     sig("uh_ba_set_problem_staged_stereo", I, VP, I, I, I, C.POINTER(ParamSet), C.c_double, C.c_double)
     sig("uh_ba_set_problem_markers", I, VP, C.POINTER(_Problem), C.POINTER(_Stereo), C.POINTER(_Markers), C.POINTER(ParamSet))
     sig("uh_ba_get_marker_results", I, VP, VP, VP, VP)
+    sig("uh_ba_debug_solve", I, VP, I, I, VP, VP, VP, VP, C.POINTER(C.c_int))
+
+
+# uh_ba_debug_solve: free keyframes a form holds, and whether it keeps D on the diagonal
+SOLVE_FORMS = {1: (1, 10, False), 2: (11, 16, False), 3: (1, 10, False), 4: (11, 21, False), 5: (1, 32, True), 6: (1, 64, True), 7: (1, 341, True)}
+
+
+def split_factor(LD, keeps_d: bool, blocked: bool = False):
+    """(L, D or None, z) from the (n + 1) x (n + 1) matrix a solve form leaves: L unit lower with everything a form documents as garbage (on
+    and above the diagonal, column n) masked out, D where the form keeps it, z = D^-1 L^-1 b from row n.  The blocked forms substitute in
+    row n itself, panel by panel from the last one: only the last 64-column panel's part of it is still z, the rest is NaN here."""
+    n = LD.shape[0] - 1
+    L = np.tril(LD[:n, :n], -1) + np.eye(n)
+    z = LD[n, :n].copy()
+    if blocked:
+        z[:((n - 1) // 64) * 64] = np.nan
+    return L, (np.diag(LD)[:n].copy() if keeps_d else None), z
 
 
 _lib._EXTRA_DECLS.append(_declare)
@@ -251,6 +268,21 @@ class GlobalOptimizer:
 
         return dict(poses=view(v.poses, np.float32, (K, 16)), points=view(v.points, np.float32, (P, 3)), chi2=view(v.chi2, np.float64, (E,)),
                     bad=view(v.bad, np.uint8, (E,)), state=view(v.pose_state, np.float64, (K, 7)), iters=np.array(list(v.iters), np.int32))
+
+    def debug_solve(self, form: int, S, b) -> dict:
+        """Test hook (uh_ba_debug_solve): S x = b through one production solve form (SOLVE_FORMS), S (n, n) with n = 6 nfree, only its lower
+        triangle read.  dict(x, failed, L, D (None where the form does not keep it), z, LD (the raw (n + 1, n + 1) matrix))."""
+        S = np.ascontiguousarray(S, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        n = len(b)
+        if S.shape != (n, n) or n % 6:
+            raise ValueError("debug_solve: S must be (n, n) and b (n,) with n a multiple of 6")
+        x = np.zeros(n)
+        LD = np.zeros((n + 1, n + 1))
+        failed = C.c_int(-1)
+        check(lib().uh_ba_debug_solve(self._h, int(form), n // 6, np_ptr(S), np_ptr(b), np_ptr(x), np_ptr(LD), C.byref(failed)))
+        L, D, z = split_factor(LD, SOLVE_FORMS[form][2], blocked=form == 7)
+        return dict(x=x, failed=int(failed.value), L=L, D=D, z=z, LD=LD)
 
     def optimize(self, stop_asap: np.ndarray | None = None):
         check(lib().uh_ba_optimize(self._h, np_ptr(stop_asap) if stop_asap is not None else None))

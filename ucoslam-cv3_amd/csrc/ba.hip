@@ -47,6 +47,7 @@
 // the side effects (residency back-off, LDS grant); enqueue_steps() only reads the plan.  DESIGN.md section 4.3 has the table.
 #include <cfloat>
 #include <climits>
+#include <limits>
 #include <cstdio>
 #include <emmintrin.h>
 #include <immintrin.h>
@@ -1493,6 +1494,41 @@ __device__ __forceinline__ bool ldlt_bordered_lds(double* M, int n, int ld, int 
     return failed;
 }
 
+// L^T x = z of the fused solve (system in LDS, row stride ld, bordered: z = D^-1 L^-1 b is row n) for n <= 64, behind ldlt_rowlane_v2<true>:
+// one wave, x_i lives in lane i; row j of L (column j of L^T) is read conflict-free thanks to the odd row stride.  x_j is
+// broadcast with v_readlane (j is wave-uniform) and the n dependent steps are branch-free: a lane the step does not touch
+// multiplies by 0.  x goes to s_x and xp.  (A function since the solve forms are tested one by one: solve_debug.hpp runs this text too.)
+__device__ __forceinline__ void backsolve1_fused(const double* M, int n, int ld, double* s_x, double* xp) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    auto IX = [&](int r, int c) -> size_t { return (size_t)r * ld + c; };
+    if (wv == 0) {
+        double x = lane < n ? M[(size_t)n * ld + lane] : 0.0;
+        const int lr = lane < n ? lane : n - 1;
+        double l[8], ln[8];
+#pragma unroll
+        for (int t = 0; t < 8; t++) { const int jj = n - 1 - t >= 0 ? n - 1 - t : 0; l[t] = M[IX(jj, lr)]; }
+        for (int j0 = n - 1; j0 >= 0; j0 -= 8) {
+#pragma unroll
+            for (int t = 0; t < 8; t++) { const int jj = j0 - 8 - t >= 0 ? j0 - 8 - t : 0; ln[t] = M[IX(jj, lr)]; }
+#pragma unroll
+            for (int t = 0; t < 8; t++) { const int j = j0 - t; l[t] = lane < j ? l[t] : 0.0; }
+#pragma unroll
+            for (int t = 0; t < 8; t++) x = fma(-l[t], readlane_f64(x, j0 - t > 0 ? j0 - t : 0), x);
+#pragma unroll
+            for (int t = 0; t < 8; t++) l[t] = ln[t];
+        }
+        if (lane < n) { s_x[lane] = x; xp[lane] = x; }
+    }
+}
+// ... and for 64 < n <= 128, behind ldlt_rowlane2_lds: backsolve2_lds, then every thread of the NT-thread workgroup publishes x (contains a barrier)
+template <int NT>
+__device__ __forceinline__ void backsolve2_fused(const double* M, int n, int ld, double* s_x, double* xp) {
+    const int tid = threadIdx.x;
+    backsolve2_lds(M, n, ld, s_x);
+    __syncthreads();
+    for (int i = tid; i < n; i += NT) xp[i] = s_x[i];
+}
+
 // ------------------------------------------------------------------------------------------------ solve + pose update
 // One workgroup.  Assembles S = Hpp + lambda I - sum of the schur partials (chunk order), factorises it as L D L^T (no
 // pivoting; fails on a zero / non-finite pivot like Eigen's SimplicialLDLT) in LDS when it fits (n <= 126) else in HBM,
@@ -1514,7 +1550,7 @@ __device__ __forceinline__ void solve_body(const BAPtrs& p, const BADims& d, int
     // 131 KB that way and never leaves the CU; only entries (r, c <= r) are ever written (reads of the few (r, c > r) the trailing update
     // loads and discards land in the next row)
     auto IX = [&](int r, int c) -> size_t { if constexpr (PACKED) return (size_t)r * (r + 1) / 2 + c; else return (size_t)r * ld + c; };
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const long long clk_begin = wall_clock64();
     // assemble the lower triangle (+ diagonal) from the pair partials.  Four elements per thread and round, every partial
     // load of the four issued before the first add: the kernel is one workgroup, so exposed L2 latency is its whole cost
@@ -1693,31 +1729,9 @@ __device__ __forceinline__ void solve_body(const BAPtrs& p, const BADims& d, int
         // the fused solve (system in LDS, bordered: z = D^-1 L^-1 b is row n): L^T x = z
         if constexpr (USE_LDS) {
             if (n <= 64) {
-                // one wave, x_i lives in lane i; row j of L (column j of L^T) is read conflict-free thanks to the odd row stride.  x_j is
-                // broadcast with v_readlane (j is wave-uniform) and the n dependent steps are branch-free: a lane the step does not touch
-                // multiplies by 0
-                if (wv == 0) {
-                    double x = lane < n ? M[(size_t)n * ld + lane] : 0.0;
-                    const int lr = lane < n ? lane : n - 1;
-                    double l[8], ln[8];
-#pragma unroll
-                    for (int t = 0; t < 8; t++) { const int jj = n - 1 - t >= 0 ? n - 1 - t : 0; l[t] = M[IX(jj, lr)]; }
-                    for (int j0 = n - 1; j0 >= 0; j0 -= 8) {
-#pragma unroll
-                        for (int t = 0; t < 8; t++) { const int jj = j0 - 8 - t >= 0 ? j0 - 8 - t : 0; ln[t] = M[IX(jj, lr)]; }
-#pragma unroll
-                        for (int t = 0; t < 8; t++) { const int j = j0 - t; l[t] = lane < j ? l[t] : 0.0; }
-#pragma unroll
-                        for (int t = 0; t < 8; t++) x = fma(-l[t], readlane_f64(x, j0 - t > 0 ? j0 - t : 0), x);
-#pragma unroll
-                        for (int t = 0; t < 8; t++) l[t] = ln[t];
-                    }
-                    if (lane < n) { s_x[lane] = x; p.xp[lane] = x; }
-                }
+                backsolve1_fused(M, n, ld, s_x, p.xp);
             } else if (n <= 128) {   // two unknowns per lane of wave 0, one broadcast per column
-                backsolve2_lds(M, n, ld, s_x);
-                __syncthreads();
-                for (int i = tid; i < n; i += NT) p.xp[i] = s_x[i];
+                backsolve2_fused<NT>(M, n, ld, s_x, p.xp);
             } else {                 // (not reached by the launch chain: the fused solve serves n <= 126) column sweeps, two barriers per column
                 for (int i = tid; i < n; i += NT) s_x[i] = M[(size_t)n * ld + i];
                 __syncthreads();
@@ -2626,6 +2640,7 @@ struct uh_ba {
                                           // re-reads the staging block and must not do so once the caller may have refilled it
     bool persist_not_resident = false;    // the last persistent launch ended because a workgroup never became resident (as opposed to a launch that vanished)
     unsigned dT_gen = ~0u, tseq = 0;
+    uh::DevBuf dbg_arena;                 // uh_ba_debug_solve: the system, x, the wide form's panel buffer, two states, the failure word
     uh::DevBuf dscratch;                  // BAState[2], 64 phase clocks, completion counter
     unsigned done_base = 0;               // what the completion counter holds before the next launch
     unsigned char* h_res = nullptr;       // pinned, device-visible result block: the kernel's tail writes getResults' outputs here
@@ -2681,6 +2696,22 @@ namespace {
         else UH_LAUNCH((b)->ctx, (K<T0, false>), grid, block, shmem, __VA_ARGS__);                                 \
     } while (0)
 
+// The wide form's blocked LDL^T of W.S (d.n + 1 rows, row d.n = right-hand side) and L^T x = z into p.xp: four kernels per 64-column panel.
+// `run`: the state slot whose phase the kernels look at (a finished pass: they do nothing).  uh_ba_debug_solve enqueues the same launches.
+void enqueue_wide_ldlt(uh_ctx* ctx, const BAPtrs& p, const BADims& d, const BAWide& W, int run) {
+    for (int k0 = 0; k0 < d.n; k0 += kWNB) {
+        const int nb = std::min(kWNB, d.n - k0), rows = d.n + 1 - (k0 + nb);   // rows behind the panel, border row included
+        UH_LAUNCH(ctx, ba_ldlw_diag_kernel, dim3(1), dim3(256), 0, p, W, run, k0, nb);
+        UH_LAUNCH(ctx, ba_ldlw_panel_kernel, dim3(uh_div_up(rows, 256)), dim3(256), 0, p, d, W, run, k0, nb);
+        const int ntile = uh_div_up(rows, 64);
+        if (k0 + nb < d.n) UH_LAUNCH(ctx, ba_ldlw_update_kernel, dim3(ntile * (ntile + 1) / 2), dim3(256), 0, p, d, W, run, k0, nb, ntile);
+    }
+    for (int k0 = ((d.n - 1) / kWNB) * kWNB; k0 >= 0; k0 -= kWNB) {
+        const int nb = std::min(kWNB, d.n - k0);
+        UH_LAUNCH(ctx, ba_ldlw_back_kernel, dim3(std::max(uh_div_up(k0, 256), 1)), dim3(256), 0, p, W, run, k0, nb);
+    }
+}
+
 // nsteps LM trials of the problem's plan (plan_ba decided everything; nothing is decided here) and the closing decision
 int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
     hipStream_t st = b->ctx->stream;
@@ -2701,17 +2732,7 @@ int enqueue_steps(uh_ba* b, int nsteps, bool pass_start) {
             UH_LAUNCH_BA(b, ba_schurw_kernel, dim3(W.n_items + d.nfree * kCamChunks), dim3(kThreads), 0, b->ptrs, d, W, run);
             UH_LAUNCH(b->ctx, ba_assemblew_kernel, dim3(W.n_pairs), dim3(64), 0, b->ptrs, d, W, run);
             if (b->n_mk) UH_LAUNCH(b->ctx, ba_mk_assemble_kernel, dim3(d.nfree), dim3(64), 0, b->ptrs, d, W, b->mk, run);
-            for (int k0 = 0; k0 < d.n; k0 += kWNB) {
-                const int nb = std::min(kWNB, d.n - k0), rows = d.n + 1 - (k0 + nb);   // rows behind the panel, border row included
-                UH_LAUNCH(b->ctx, ba_ldlw_diag_kernel, dim3(1), dim3(256), 0, b->ptrs, W, run, k0, nb);
-                UH_LAUNCH(b->ctx, ba_ldlw_panel_kernel, dim3(uh_div_up(rows, 256)), dim3(256), 0, b->ptrs, d, W, run, k0, nb);
-                const int ntile = uh_div_up(rows, 64);
-                if (k0 + nb < d.n) UH_LAUNCH(b->ctx, ba_ldlw_update_kernel, dim3(ntile * (ntile + 1) / 2), dim3(256), 0, b->ptrs, d, W, run, k0, nb, ntile);
-            }
-            for (int k0 = ((d.n - 1) / kWNB) * kWNB; k0 >= 0; k0 -= kWNB) {
-                const int nb = std::min(kWNB, d.n - k0);
-                UH_LAUNCH(b->ctx, ba_ldlw_back_kernel, dim3(std::max(uh_div_up(k0, 256), 1)), dim3(256), 0, b->ptrs, W, run, k0, nb);
-            }
+            enqueue_wide_ldlt(b->ctx, b->ptrs, d, W, run);
             UH_LAUNCH(b->ctx, ba_posew_kernel, dim3(uh_div_up(d.nfree, 256)), dim3(256), 0, b->ptrs, d, W, run);
             if (b->n_mk) UH_LAUNCH(b->ctx, ba_mk_lin_kernel, dim3(b->mk.n_edges), dim3(64), 0, b->ptrs, d, b->mk, run, 1);
             UH_LAUNCH_BA1(b, ba_backsub_kernel, false, dim3(d.nPointBlocks), dim3(kThreads), 0, b->ptrs, d, pl.nsplit, run);
@@ -4036,3 +4057,59 @@ int uh_ba_results_view_get(uh_ba* b, uh_ba_results_view* out) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ test hook: one solve form on a given system
+namespace {
+#include "solve_debug.hpp"
+}  // namespace
+
+extern "C" int uh_ba_debug_solve(uh_ba* b, int form, int nfree, const double* S, const double* bv, double* x, double* LD, int* failed) {
+    UH_REQUIRE(b && S && bv && x && failed, "uh_ba_debug_solve: NULL argument");
+    UH_REQUIRE(form >= 1 && form <= 7, "uh_ba_debug_solve: form %d outside 1..7", form);
+    static const int lo[8] = {0, 1, 11, 1, 11, 1, 1, 1}, hi[8] = {0, 10, 16, 10, 21, kPackedFree, kMaxFree, 341};
+    UH_REQUIRE(nfree >= lo[form] && nfree <= hi[form], "uh_ba_debug_solve: form %d holds %d..%d free keyframes, not %d", form, lo[form], hi[form], nfree);
+    UH_HIP_CHECK(hipSetDevice(b->ctx->device));
+    hipStream_t st = b->ctx->stream;
+    const int n = 6 * nfree;
+    const size_t ld = (size_t)n + 1;
+    // [S; b^T] with row stride ld; the words production leaves uninitialised are NaN (form 7: zero — the wide form clears its matrix)
+    std::vector<double> A(ld * ld, form == 7 ? 0.0 : std::numeric_limits<double>::quiet_NaN());
+    for (int r = 0; r < n; r++) for (int c = 0; c <= r; c++) A[r * ld + c] = S[(size_t)r * n + c];
+    for (int c = 0; c < n; c++) A[n * ld + c] = bv[c];
+    uh::Layout L;
+    const size_t o_A = L.take<double>(ld * ld), o_x = L.take<double>(n), o_Y = L.take<double>(form == 7 ? ld * kWNB : 0), o_st = L.take<BAState>(2), o_fail = L.take<int>(1);
+    if (const int rc = b->dbg_arena.reserve(L.off + 256)) return rc;
+    char* base = b->dbg_arena.as<char>();
+    double* dA = (double*)(base + o_A); double* dx = (double*)(base + o_x); int* dfail = (int*)(base + o_fail);
+    UH_HIP_CHECK(hipMemcpyAsync(dA, A.data(), ld * ld * sizeof(double), hipMemcpyHostToDevice, st));
+    UH_HIP_CHECK(hipMemsetAsync(dx, 0xFF, (size_t)n * sizeof(double), st));   // (NaN: an x the solve did not write shows)
+    UH_HIP_CHECK(hipMemsetAsync(dfail, 0, sizeof(int), st));
+    const size_t tri = ld * (ld + 1) / 2;
+#define UH_DBG_SOLVE(K, threads, lds)                                                                                                   \
+    do {                                                                                                                                \
+        if ((lds) > 48 * 1024) UH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)));   \
+        UH_LAUNCH(b->ctx, (K), dim3(1), dim3(threads), (lds), dA, dx, dfail, nfree);                                                    \
+    } while (0)
+    if (form == 1 || form == 2) UH_DBG_SOLVE(ba_dbg_solve_rowlane_kernel<true>, kPThreads, (ld * ld + 2 * 129 * 6) * sizeof(double));
+    else if (form == 3 || form == 4) UH_DBG_SOLVE(ba_dbg_solve_rowlane_kernel<false>, kFusedThreads, ld * ld * sizeof(double));
+    else if (form == 5) UH_DBG_SOLVE(ba_dbg_solve_mfma_kernel<true>, kPackedThreads, (tri + 2 + kLdltAux) * sizeof(double));
+    else if (form == 6) UH_DBG_SOLVE(ba_dbg_solve_mfma_kernel<false>, kHbmThreads, 0);
+    else {
+        BAPtrs p{}; BADims d{}; BAWide W{};
+        p.st = (BAState*)(base + o_st); p.xp = dx;
+        d.nfree = nfree; d.n = n;
+        W.ld = (int)ld; W.S = dA; W.Y = (double*)(base + o_Y); W.fail = dfail;
+        UH_LAUNCH(b->ctx, ba_dbg_state_kernel, dim3(1), dim3(64), 0, p.st);
+        enqueue_wide_ldlt(b->ctx, p, d, W, 0);
+    }
+#undef UH_DBG_SOLVE
+    UH_HIP_CHECK(hipGetLastError());
+    int hfail = 0;
+    UH_HIP_CHECK(hipMemcpyAsync(x, dx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    UH_HIP_CHECK(hipMemcpyAsync(&hfail, dfail, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (LD) UH_HIP_CHECK(hipMemcpyAsync(LD, dA, ld * ld * sizeof(double), hipMemcpyDeviceToHost, st));
+    UH_HIP_CHECK(hipStreamSynchronize(st));
+    if (form == 7 && hfail) for (int i = 0; i < n; i++) x[i] = 0.0;   // (ba_posew_kernel's part: a failed solve leaves no increment)
+    *failed = hfail ? 1 : 0;
+    return UH_OK;
+}

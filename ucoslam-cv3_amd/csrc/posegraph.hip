@@ -315,6 +315,7 @@ __global__ __launch_bounds__(256) void pg_results_kernel(PG p) {
 struct uh_posegraph {
     uh_ctx* ctx = nullptr;
     uh::DevBuf arena;
+    uh::DevBuf dbg_arena;   // uh_posegraph_debug_solve
     bool have = false;
     int n = 0, E = 0;
     std::vector<float> poses;
@@ -507,6 +508,37 @@ int uh_posegraph_debug_linearisation(uh_posegraph* g, double* err_out, double* J
         if (Jj_out) std::memcpy(Jj_out + 49 * (size_t)e, g->dbg_J.data() + 98 * (size_t)e + 49, 392);
         if (meas_out) std::memcpy(meas_out + 8 * (size_t)e, g->meas.data() + 8 * (size_t)e, 64);
     }
+    return UH_OK;
+}
+
+// test hook: pgl::factor_and_solve on a system the caller gives, laid out and cleared as uh_posegraph_optimize does it
+int uh_posegraph_debug_solve(uh_posegraph* g, int n, const double* S, const double* bv, double* x, double* LD, int* failed) {
+    UH_REQUIRE(g && S && bv && x && failed, "uh_posegraph_debug_solve: NULL argument");
+    UH_REQUIRE(n >= 1 && n <= 4096, "uh_posegraph_debug_solve: n = %d outside 1..4096", n);
+    UH_HIP_CHECK(hipSetDevice(g->ctx->device));
+    hipStream_t st = g->ctx->stream;
+    const size_t ld = (size_t)n + 1;
+    std::vector<double> A(ld * ld, 0.0);   // (the optimiser clears S before every assembly)
+    for (int r = 0; r < n; r++) for (int c = 0; c <= r; c++) A[r * ld + c] = S[(size_t)r * n + c];
+    for (int c = 0; c < n; c++) A[n * ld + c] = bv[c];
+    uh::Layout L;
+    const size_t o_x = L.take<double>(n), o_fail = L.take<int>(1), o_gz = L.take<int>((n + 64) / 64 + 1), o_Y = L.take<double>(ld * pgl::kNB), o_S = L.take<double>(ld * ld);
+    if (const int rc = g->dbg_arena.reserve(L.off + 256)) return rc;
+    char* base = g->dbg_arena.as<char>();
+    pgl::Sys w{};
+    w.S = (double*)(base + o_S); w.Y = (double*)(base + o_Y); w.x = (double*)(base + o_x); w.fail = (int*)(base + o_fail); w.group_nz = (int*)(base + o_gz);
+    w.n = n; w.ld = ld;
+    UH_HIP_CHECK(hipMemcpyAsync(w.S, A.data(), ld * ld * sizeof(double), hipMemcpyHostToDevice, st));
+    UH_HIP_CHECK(hipMemsetAsync(w.x, 0xFF, (size_t)n * sizeof(double), st));   // (NaN: an x the solve did not write shows)
+    UH_HIP_CHECK(hipMemsetAsync(w.fail, 0, sizeof(int), st));
+    pgl::factor_and_solve(w, st);
+    UH_HIP_CHECK(hipGetLastError());
+    int hfail = 0;
+    UH_HIP_CHECK(hipMemcpyAsync(x, w.x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    UH_HIP_CHECK(hipMemcpyAsync(&hfail, w.fail, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (LD) UH_HIP_CHECK(hipMemcpyAsync(LD, w.S, ld * ld * sizeof(double), hipMemcpyDeviceToHost, st));
+    UH_HIP_CHECK(hipStreamSynchronize(st));
+    *failed = hfail ? 1 : 0;
     return UH_OK;
 }
 

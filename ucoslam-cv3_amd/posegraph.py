@@ -34,6 +34,7 @@ def _declare(L, sig):
     sig("uh_posegraph_optimize", I, VP, C.POINTER(_Problem), C.POINTER(_Params))
     sig("uh_posegraph_get_results", I, VP, VP, VP, C.POINTER(_Info), VP)
     sig("uh_posegraph_debug_linearisation", I, VP, VP, VP, VP, VP)
+    sig("uh_posegraph_debug_solve", I, VP, I, VP, VP, VP, VP, C.POINTER(C.c_int))
 
 
 _lib._EXTRA_DECLS.append(_declare)
@@ -88,6 +89,23 @@ class PoseGraph:
         o = dict(err=np.zeros((E, 7)), Ji=np.zeros((E, 7, 7)), Jj=np.zeros((E, 7, 7)), meas=np.zeros((E, 8)))
         check(lib().uh_posegraph_debug_linearisation(self._h, np_ptr(o["err"]), np_ptr(o["Ji"]), np_ptr(o["Jj"]), np_ptr(o["meas"])))
         return o
+
+    def debug_solve(self, S, b) -> dict:
+        """Test hook (uh_posegraph_debug_solve): S x = b through the optimiser's blocked LDL^T (csrc/dense_ldlt.hpp), S (n, n), only its lower
+        triangle read.  dict(x, failed, L, D, z, LD (the raw (n + 1, n + 1) matrix)); x is unspecified where failed = 1."""
+        from .ba import split_factor
+
+        S = np.ascontiguousarray(S, np.float64)
+        b = np.ascontiguousarray(b, np.float64)
+        n = len(b)
+        if S.shape != (n, n):
+            raise ValueError("debug_solve: S must be (n, n) and b (n,)")
+        x = np.zeros(n)
+        LD = np.zeros((n + 1, n + 1))
+        failed = C.c_int(-1)
+        check(lib().uh_posegraph_debug_solve(self._h, n, np_ptr(S), np_ptr(b), np_ptr(x), np_ptr(LD), C.byref(failed)))
+        L, D, z = split_factor(LD, True, blocked=True)
+        return dict(x=x, failed=int(failed.value), L=L, D=D, z=z, LD=LD)
 
     def close(self):
         if self._h:
