@@ -344,6 +344,61 @@ int uh_orb_extract_batch(uh_orb* orb, const uint8_t* imgs, int w, int h, size_t 
 int uh_orb_debug_level(uh_orb* orb, int frame, int level, int which, uint8_t* out, int* w_out, int* h_out);
 
 /* ------------------------------------------------------------------------
+ * Stereo / RGB-D frames: Frame::depth per keypoint — FrameExtractor::processStereo and process_rgbd (src/utils/frameextractor.cpp from
+ * :1419) for kptImageScaleFactor == 1 (the resize branch is not built: a host that sets another factor keeps the reference's extractor).
+ * Per left keypoint i (depth[i] = 0 unless every step succeeds):
+ *   row    r = int(std::round(und.y)); candidates = the right keypoints j with int(std::round(pt.y)) == r (a right keypoint whose rounded
+ *          row is outside the image is in no row), skipping right.pt.x > left.und.x and |octave difference| > 1
+ *   match  smallest 256-bit Hamming distance d with float(d) < max_desc_dist; among equals the lowest j
+ *   SAD    6 x 6 windows (cv::Range(c-3, c+3)) of the UNBLURRED gray images around the rounded centres (both must satisfy 3 <= c, c+3 < size),
+ *          the right one shifted by -7 .. 7; first smallest sum of absolute differences
+ *   depth  only if that minimum is strictly inside the evaluated offsets: parabola through the three costs (double), xr = right.pt.x + delta,
+ *          depth = float(double(bl * fx) / (double(und.x) - xr)) with bl * fx a float product.  Negative / infinite values are kept.
+ * Bit for bit the reference's result, with two deviations where the reference reads out of bounds or throws: a left row outside
+ * [0, rows) has no candidates (the reference indexes a std::vector unchecked), and the offsets stop where the shifted window still lies
+ * inside the image (the reference throws cv::Exception there; ORB keypoints keep 16 px from the border, so neither occurs in its own use).
+ *
+ * uh_stereo_depth: the operator on caller-supplied HOST arrays (uploads, three launches, one wait).  Keypoints are cv::KeyPoint records: pt and
+ * octave are read.  depth_out: n_left floats; match_out: NULL, or n_left ints receiving the matched right index or -1.
+ * uh_stereo_depth_dev: every pointer (images, keypoints, descriptors, outputs) is device memory, descriptors 16-byte aligned; asynchronous on
+ * the context stream.  uh_stereo_depth_host: the same result from the same arithmetic on the CPU, no GPU involved.
+ * ------------------------------------------------------------------------ */
+typedef struct uh_stereo_args {
+    const uint8_t* left;  size_t left_stride;      /* CV_8UC1, rows x cols, row stride in bytes */
+    const uint8_t* right; size_t right_stride;
+    int32_t cols, rows;                            /* of the left image */
+    int32_t right_cols, right_rows;                /* must equal cols, rows */
+    int32_t n_left;  const uh_keypoint* left_und_kpts; const uint8_t* left_desc;    /* Frame::und_kpts, Frame::desc (n x 32) */
+    int32_t n_right; const uh_keypoint* right_kpts;    const uint8_t* right_desc;   /* detectAndCompute of the right image */
+    float bl, fx;                                  /* ImageParams::bl (> 0), fx() */
+    float max_desc_dist;                           /* Params::maxDescDistance */
+} uh_stereo_args;
+int uh_stereo_depth(uh_ctx* ctx, const uh_stereo_args* args, float* depth_out, int32_t* match_out);
+int uh_stereo_depth_dev(uh_ctx* ctx, const uh_stereo_args* args, float* d_depth_out, int32_t* d_match_out);
+int uh_stereo_depth_host(const uh_stereo_args* args, float* depth_out, int32_t* match_out);
+/* process_rgbd's gather alone: depth[i] = float(D(cvRound(kpts[i].pt))) * depth_scale where that pixel is non-zero, else 0 (kpts = the
+ * DISTORTED keypoints; a pixel outside the depth image gives 0 where the reference reads unchecked).  depth_stride in bytes (even). */
+int uh_rgbd_depth(uh_ctx* ctx, const uh_keypoint* kpts, int32_t n, const uint16_t* depth_img, int32_t cols, int32_t rows, size_t depth_stride,
+                  float depth_scale, float* depth_out);
+int uh_rgbd_depth_host(const uh_keypoint* kpts, int32_t n, const uint16_t* depth_img, int32_t cols, int32_t rows, size_t depth_stride,
+                       float depth_scale, float* depth_out);
+
+/* FrameExtractor::processStereo in one call: gray conversion and extraction of both images, then the three stereo launches, one wait.
+ * Needs uh_orb_set_camera (fx, und_kpts) and uh_orb_set_stereo (bl > 0, max_desc_dist).  Left outputs (kps, desc, und_xy, *n_out, and
+ * `frame` if not NULL) are exactly uh_orb_extract_frame / uh_orb_extract_frame_dev of the left image; depth receives *n_out floats (room
+ * for cap).  right_out (NULL, or for inspection): the right image's keypoints / descriptors / count, exactly uh_orb_extract of the right
+ * gray image; kps / desc hold uh_orb_max_keypoints entries.  Both images are w x h with the same channel count and row stride (bytes). */
+typedef struct uh_stereo_right { uh_keypoint* kps; uint8_t* desc; int32_t n; } uh_stereo_right;
+int uh_orb_set_stereo(uh_orb* orb, float bl, float max_desc_dist);
+int uh_orb_extract_stereo(uh_orb* orb, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, int channels,
+                          uh_keypoint* kps, uint8_t* desc, float* und_xy, float* depth, int cap, int* n_out, uh_dev_frame* frame,
+                          uh_stereo_right* right_out);
+/* FrameExtractor::process_rgbd in one call: uh_orb_extract_frame (uh_orb_extract_frame_dev when `frame` is not NULL) plus the depth gather
+ * behind it on the device, one wait.  depth_img: h rows of w uint16, depth_stride in bytes; depth_scale = ImageParams::rgb_depthscale. */
+int uh_orb_extract_rgbd(uh_orb* orb, const uint8_t* img, int w, int h, size_t stride, int channels, const uint16_t* depth_img, size_t depth_stride,
+                        float depth_scale, uh_keypoint* kps, uint8_t* desc, float* und_xy, float* depth, int cap, int* n_out, uh_dev_frame* frame);
+
+/* ------------------------------------------------------------------------
  * Bundle adjustment — replaces GlobalOptimizerG2O behind the GlobalOptimizer plugin:
  *   src/optimization/globaloptimizer.h:28-68       setParams / optimize(bool* stopASAP) / getResults
  *   src/optimization/globaloptimizer_g2o.cpp:77-401 (graph build), :418-464 (two-pass LM), :466-537 (results)

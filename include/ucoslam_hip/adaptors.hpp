@@ -695,4 +695,81 @@ std::vector<std::array<float, 3>> Triangulate(Context& ctx, const TrainView& Tra
     return out;
 }
 
+// ---- ucoslam::FrameExtractor::processStereo / process_rgbd (utils/frameextractor.cpp from :1419), kptImageScaleFactor == 1 --------------
+// Images are non-owning views (for cv::Mat: {m.data, m.cols, m.rows, m.step, m.channels()}).  The frame type is a template parameter shaped
+// like ucoslam::Frame: kpts (elements with x, y), und_kpts (elements with pt.x, pt.y, size, angle, response, octave, class_id), depth
+// (std::vector<float>), fseq_idx, and its descriptors through frame_set_desc(frame, bytes, n) — the overload below fills a
+// std::vector<uint8_t> desc; for cv::Mat add one that creates n x 32 CV_8UC1 and copies.  Markers, the image-scale branch and the frame's
+// id / pose bookkeeping stay with the caller; `dev` (optional) also leaves the frame on the device as uh_orb_extract_frame_dev does.
+struct ImageView { const void* data; int cols, rows; size_t step; int channels; };
+struct StereoImageParams {   // the fields of ucoslam::ImageParams this stage reads
+    float fx, fy, cx, cy;
+    std::vector<float> dist;   // k1 k2 p1 p2 [k3 [k4 k5 k6]]
+    float bl = 0, rgb_depthscale = 1;
+};
+template <class Frame> inline auto frame_set_desc(Frame& f, const uint8_t* bytes, int n) -> decltype(f.desc.assign(bytes, bytes)) { return f.desc.assign(bytes, bytes + (size_t)n * 32); }
+
+class FrameExtractor {
+   public:
+    FrameExtractor(std::shared_ptr<Context> ctx, const FeatParams& fp, float maxDescDistance) : orb_(std::move(ctx)), max_desc_dist_(maxDescDistance) {
+        uh_feat_params p{fp.nthreads, fp.maxFeatures, fp.nOctaveLevels, fp.scaleFactor, fp.sensitivity};
+        check(uh_orb_set_params(orb_.handle(), &p));
+    }
+    template <class Frame>
+    void processStereo(const ImageView& LeftRect, const ImageView& RightRect, const StereoImageParams& ip, Frame& frame, uint32_t frameseq_idx = UINT32_MAX,
+                       uh_dev_frame* dev = nullptr) {
+        if (LeftRect.cols != RightRect.cols || LeftRect.rows != RightRect.rows || LeftRect.step != RightRect.step || LeftRect.channels != RightRect.channels)
+            throw std::runtime_error("processStereo: the two images differ in size, step or channels");
+        set_camera(ip);
+        check(uh_orb_set_stereo(orb_.handle(), ip.bl, max_desc_dist_));
+        reserve();
+        int n = 0;
+        check(uh_orb_extract_stereo(orb_.handle(), static_cast<const uint8_t*>(LeftRect.data), static_cast<const uint8_t*>(RightRect.data), LeftRect.cols,
+                                    LeftRect.rows, LeftRect.step, LeftRect.channels, kps_.data(), desc_.data(), und_.data(), depth_.data(), (int)kps_.size(), &n, dev,
+                                    nullptr));
+        fill(frame, n, frameseq_idx);
+    }
+    template <class Frame>
+    void process_rgbd(const ImageView& image, const ImageView& depthImage, const StereoImageParams& ip, Frame& frame, uint32_t frameseq_idx = UINT32_MAX,
+                      uh_dev_frame* dev = nullptr) {
+        if (image.cols != depthImage.cols || image.rows != depthImage.rows) throw std::runtime_error("process_rgbd: colour and depth image differ in size");
+        set_camera(ip);
+        reserve();
+        int n = 0;
+        check(uh_orb_extract_rgbd(orb_.handle(), static_cast<const uint8_t*>(image.data), image.cols, image.rows, image.step, image.channels,
+                                  static_cast<const uint16_t*>(depthImage.data), depthImage.step, ip.rgb_depthscale, kps_.data(), desc_.data(), und_.data(),
+                                  depth_.data(), (int)kps_.size(), &n, dev));
+        fill(frame, n, frameseq_idx);
+    }
+    ORBextractor& extractor() { return orb_; }
+   private:
+    void set_camera(const StereoImageParams& ip) {
+        if (ip.dist.size() > 8) throw std::runtime_error("FrameExtractor: more than 8 distortion coefficients");
+        uh_camera c{ip.fx, ip.fy, ip.cx, ip.cy, {0}, (int32_t)ip.dist.size()};
+        for (size_t i = 0; i < ip.dist.size(); i++) c.dist[i] = ip.dist[i];
+        check(uh_orb_set_camera(orb_.handle(), &c));
+    }
+    void reserve() {
+        const size_t cap = (size_t)std::max(uh_orb_max_keypoints(orb_.handle()), 1);
+        kps_.resize(cap); desc_.resize(cap * 32); und_.resize(cap * 2); depth_.resize(cap);
+    }
+    template <class Frame>
+    void fill(Frame& f, int n, uint32_t frameseq_idx) {
+        f.kpts.resize(n); f.und_kpts.resize(n); f.depth.assign(depth_.begin(), depth_.begin() + n);
+        for (int i = 0; i < n; i++) {
+            const uh_keypoint& k = kps_[i];
+            f.kpts[i].x = k.x; f.kpts[i].y = k.y;
+            auto& u = f.und_kpts[i];
+            u.pt.x = und_[2 * i]; u.pt.y = und_[2 * i + 1]; u.size = k.size; u.angle = k.angle; u.response = k.response; u.octave = k.octave; u.class_id = k.class_id;
+        }
+        frame_set_desc(f, desc_.data(), n);
+        f.fseq_idx = frameseq_idx;
+    }
+    ORBextractor orb_;
+    float max_desc_dist_;
+    std::vector<uh_keypoint> kps_;
+    std::vector<uint8_t> desc_;
+    std::vector<float> und_, depth_;
+};
+
 }  // namespace ucoslam_hip

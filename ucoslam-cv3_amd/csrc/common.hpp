@@ -176,6 +176,7 @@ struct uh_ctx {
     bool owns_stream = false;
     int num_cus = 0;
     uh_prof prof;
+    uh::DevBuf stereo_ws;   // uh_stereo_depth[_dev] / uh_rgbd_depth: row index, staged inputs and results (stereo.hip)
 };
 
 namespace uh {

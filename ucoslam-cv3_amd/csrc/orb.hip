@@ -29,6 +29,7 @@
 #include "devframe.hpp"
 #include "glibc_sincosf.hpp"
 #include "introselect.hpp"
+#include "stereo.hpp"
 #include "../../include/ucoslam_hip_orb_pattern.inc"
 
 namespace {
@@ -1415,11 +1416,16 @@ struct uh_orb {
         int cap = 0;
         size_t o_cnt = 0, o_kps = 0, o_desc = 0, o_und = 0;
         uh_dev_frame* fr = nullptr;   // receives the final keypoint count
+        float* depth = nullptr; size_t o_depth = 0;   // uh_orb_extract_stereo / _rgbd: Frame::depth follows the keypoints
     } pending;
     uh::MappedBuf h_out;           // one-frame form: [completion word | count | keypoints | descriptors] when the caller's buffers are not pinned
     unsigned long long seq = 0;
     CamModel cam{};                // uh_orb_set_camera: on = 1 -> the one-frame entry can return the undistorted keypoints
     uh::DevBuf d_raw;              // an interleaved BGR / BGRA frame on its way to gray (uh_orb_extract_frame)
+    // uh_orb_extract_stereo / _rgbd (stereo.hip): the right image's gray pixels (its keypoints / descriptors / count go to d_kps / d_desc / d_counts),
+    // the depth image, the row index and match scratch
+    float st_bl = 0.f, st_max_desc_dist = 0.f;
+    uh::DevBuf d_right, d_depth_img, d_st_ws;
 };
 
 namespace {
@@ -1938,9 +1944,46 @@ int uh_orb_extract_dev(uh_orb* o, const uint8_t* d_imgs, int w, int h, size_t st
 
 static int extract_finish(uh_orb* o, int* n_out);
 
+// What uh_orb_extract_stereo / uh_orb_extract_rgbd add to an extraction: Frame::depth, computed on the device between the extraction's last
+// kernel and its completion word.  right != NULL: the right image (same size, stride and channels), extracted FIRST with the same launch set
+// (the left extraction then runs exactly as without this, and leaves the object — level counts for the kd-tree build included — as it always does).
+struct DepthJob {
+    const uint8_t* right = nullptr;
+    const uint16_t* depth_img = nullptr; size_t depth_stride = 0; float depth_scale = 0.f;
+    float* depth = nullptr;        // the caller's array (cap floats)
+};
+
+// one frame's pixels, as the caller holds them, to `dst` (w x h gray bytes on the device), on the context stream
+static int ingest_frame(uh_orb* o, const uint8_t* img, int w, int h, size_t stride, int cn, uint8_t* dst) {
+    int rc;
+    hipStream_t st = o->ctx->stream;
+    const uint8_t* h_img = static_cast<const uint8_t*>(uh::device_alias_of_host(img));
+    if (cn != 1) {
+        const uint8_t* src = h_img;
+        size_t sstride = stride;
+        if (!src) {
+            if ((rc = o->d_raw.reserve((size_t)w * cn * h + 16))) return rc;
+            UH_HIP_CHECK(hipMemcpy2DAsync(o->d_raw.p, (size_t)w * cn, img, stride, (size_t)w * cn, h, hipMemcpyHostToDevice, st));
+            src = o->d_raw.as<uint8_t>(); sstride = (size_t)w * cn;
+        }
+        UH_LAUNCH(o->ctx, ingest_bgr_kernel, dim3(uh_div_up(((w + 3) / 4) * h, 256)), dim3(256), 0, src, w, h, sstride, cn, dst);
+        return UH_OK;
+    }
+    if (h_img && stride == (size_t)w && (reinterpret_cast<uintptr_t>(h_img) & 15) != 0) h_img = nullptr;
+    if (h_img) {
+        const int chunks = stride == (size_t)w ? (int)(((size_t)w * h + 15) / 16) : ((w + 15) / 16) * h;
+        UH_LAUNCH(o->ctx, ingest_kernel, dim3(uh_div_up(chunks, 256)), dim3(256), 0, h_img, w, h, stride, dst);
+    } else if (stride == (size_t)w) {
+        UH_HIP_CHECK(hipMemcpyAsync(dst, img, (size_t)w * h, hipMemcpyHostToDevice, st));
+    } else {
+        UH_HIP_CHECK(hipMemcpy2DAsync(dst, w, img, stride, w, h, hipMemcpyHostToDevice, st));
+    }
+    return UH_OK;
+}
+
 // early != NULL: return as soon as the undistorted keypoints are on the host (*early = this object's array of them); uh_orb_extract_frame_dev_end completes the call
 static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t stride, int cn, uh_keypoint* kps, uint8_t* desc, float* und_xy, int cap,
-                       int* n_out, uh_dev_frame* fr = nullptr, const uh_keypoint** early = nullptr) {
+                       int* n_out, uh_dev_frame* fr = nullptr, const uh_keypoint** early = nullptr, const DepthJob* job = nullptr) {
     UH_REQUIRE(o && n_out, "uh_orb_extract: NULL argument");
     UH_REQUIRE(!o->pending.active, "uh_orb_extract: uh_orb_extract_frame_dev_begin without its _end");
     *n_out = 0;
@@ -1971,32 +2014,28 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
     if ((rc = o->d_in.reserve((size_t)w * h + 16))) return rc;
     // (the 16-byte loads / stores of the pinned paths need 16-byte aligned bases: an interior pointer — an ROI, a numpy view inside a pinned
     // block — that is not aligned takes the staging paths below instead of relying on the hardware's unaligned-access mode)
-    const uint8_t* h_img = static_cast<const uint8_t*>(uh::device_alias_of_host(img));
-    if (cn != 1) {   // colour frame: to gray on the way in (cv::cvtColor COLOR_BGR2GRAY, frameextractor.cpp:2960) — from pinned memory in place, else through a staged copy
-        const uint8_t* src = h_img;
-        size_t sstride = stride;
-        if (!src) {
-            if ((rc = o->d_raw.reserve((size_t)w * cn * h + 16))) return rc;
-            UH_HIP_CHECK(hipMemcpy2DAsync(o->d_raw.p, (size_t)w * cn, img, stride, (size_t)w * cn, h, hipMemcpyHostToDevice, st));
-            src = o->d_raw.as<uint8_t>(); sstride = (size_t)w * cn;
-        }
-        UH_LAUNCH(o->ctx, ingest_bgr_kernel, dim3(uh_div_up(((w + 3) / 4) * h, 256)), dim3(256), 0, src, w, h, sstride, cn, o->d_in.as<uint8_t>());
-    } else {
-    if (h_img && stride == (size_t)w && (reinterpret_cast<uintptr_t>(h_img) & 15) != 0) h_img = nullptr;   // (the strided path copies 4-byte pieces of any alignment)
-    if (h_img) {
-        const int chunks = stride == (size_t)w ? (int)(((size_t)w * h + 15) / 16) : ((w + 15) / 16) * h;
-        UH_LAUNCH(o->ctx, ingest_kernel, dim3(uh_div_up(chunks, 256)), dim3(256), 0, h_img, w, h, stride, o->d_in.as<uint8_t>());
-    } else if (stride == (size_t)w) {   // pageable frame: through the runtime's staging copy
-        UH_HIP_CHECK(hipMemcpyAsync(o->d_in.p, img, (size_t)w * h, hipMemcpyHostToDevice, st));
-    } else {
-        UH_HIP_CHECK(hipMemcpy2DAsync(o->d_in.p, w, img, stride, w, h, hipMemcpyHostToDevice, st));
+    if (job && job->right) {   // processStereo's second detectAndCompute, first: keypoints / descriptors / count stay on the device
+        if ((rc = o->d_right.reserve((size_t)w * h + 16)) || (rc = o->d_kps.reserve((size_t)maxk * sizeof(uh_keypoint))) ||
+            (rc = o->d_desc.reserve((size_t)maxk * 32)) || (rc = o->d_counts.reserve(64)))
+            return rc;
+        if ((rc = ingest_frame(o, job->right, w, h, stride, cn, o->d_right.as<uint8_t>()))) return rc;
+        if ((rc = run_frames(o, o->d_right.as<uint8_t>(), w, h, (size_t)w, (size_t)w * h, 1, o->d_kps.as<KeyPointOut>(), o->d_desc.as<uint8_t>(), maxk,
+                             o->d_counts.as<int>())))
+            return rc;
     }
+    if (job && job->depth_img) {
+        if ((rc = o->d_depth_img.reserve((size_t)w * h * 2 + 16))) return rc;
+        UH_HIP_CHECK(hipMemcpy2DAsync(o->d_depth_img.p, (size_t)w * 2, job->depth_img, job->depth_stride, (size_t)w * 2, h, hipMemcpyHostToDevice, st));
     }
+    // colour frame: to gray on the way in (cv::cvtColor COLOR_BGR2GRAY, frameextractor.cpp:2960) — from pinned memory in place, else through a staged
+    // copy; gray: by a kernel from pinned memory (the strided path copies 4-byte pieces of any alignment), else through the runtime's staging copy
+    if ((rc = ingest_frame(o, img, w, h, stride, cn, o->d_in.as<uint8_t>()))) return rc;
     const uint8_t* d_img = o->d_in.as<uint8_t>();
     const size_t in_stride = (size_t)w;
     const int slots = std::min(maxk, std::max(cap, 1));
+    const bool want_und = und_xy || fr || (job && job->right);   // (the stereo match reads Frame::und_kpts)
     const size_t o_cnt = 64, o_kps = 128, o_desc = o_kps + (((size_t)maxk * sizeof(uh_keypoint) + 63) & ~(size_t)63), o_und = o_desc + (size_t)maxk * 32,
-                 total = o_und + ((und_xy || fr) ? (size_t)maxk * 8 : 0);
+                 o_depth = o_und + (want_und ? (size_t)maxk * 8 : 0), total = o_depth + (job ? (size_t)maxk * 4 : 0);
     if ((rc = o->h_out.reserve(total))) return rc;
     char* hb = o->h_out.host<char>();
     char* db = o->h_out.dev<char>();
@@ -2009,7 +2048,7 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
     // (with staged keypoints the launch runs at cap_per_frame = maxk, so describe_kernel stores up to maxk positions — the caller's
     // array holds only `cap` of them: write into it only when the launch itself is bounded by `cap`, or `cap` covers every slot)
     const bool und_direct = d_und && (reinterpret_cast<uintptr_t>(d_und) & 7) == 0 && (direct || cap >= maxk);
-    if ((und_xy || fr) && !und_direct) d_und = reinterpret_cast<float*>(db + o_und);
+    if (want_und && !und_direct) d_und = reinterpret_cast<float*>(db + o_und);
     const int cap_launch = direct ? slots : maxk;
     EarlyUnd ea{};
     if (early) {
@@ -2025,6 +2064,30 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
     }
     rc = run_frames(o, d_img, w, h, in_stride, (size_t)in_stride * h, 1, d_kps, d_desc, cap_launch, reinterpret_cast<int*>(db + o_cnt), d_und, fr, early ? &ea : nullptr);
     if (rc) return rc;
+    if (job) {   // Frame::depth into the pinned block, behind describe_kernel and ahead of the completion word: no host round trip
+        const int n_cap = std::min(cap_launch, maxk);
+        const int* d_n = reinterpret_cast<const int*>(db + o_cnt);
+        float* d_depth = reinterpret_cast<float*>(db + o_depth);
+        if (job->right) {
+            uh::Layout lay;
+            const size_t o_ptr = lay.take<int>((size_t)h + 1), o_idx = lay.take<int>(maxk), o_match = lay.take<int>(maxk);
+            if ((rc = o->d_st_ws.reserve(lay.off))) return rc;
+            char* ws = o->d_st_ws.as<char>();
+            uh::StereoLaunch s{};
+            s.left = d_img; s.left_stride = in_stride; s.right = o->d_right.as<uint8_t>(); s.right_stride = (size_t)w; s.cols = w; s.rows = h;
+            s.l_xy = d_und; s.l_xy_stride = 2; s.l_oct = &d_kps->octave; s.l_oct_stride = sizeof(KeyPointOut) / 4;
+            s.l_desc = d_desc; s.n_left = n_cap; s.d_n_left = d_n;
+            s.r_kps = o->d_kps.as<uh_keypoint>(); s.r_desc = o->d_desc.as<uint8_t>(); s.n_right = maxk; s.d_n_right = o->d_counts.as<int>();
+            s.blfx = o->st_bl * o->cam.ffx; s.max_desc_dist = o->st_max_desc_dist;
+            s.depth = d_depth; s.match = reinterpret_cast<int*>(ws + o_match);
+            s.row_ptr = reinterpret_cast<int*>(ws + o_ptr); s.row_idx = reinterpret_cast<int*>(ws + o_idx);
+            if ((rc = uh::stereo_launch(o->ctx, s))) return rc;
+        } else {
+            if ((rc = uh::rgbd_launch(o->ctx, reinterpret_cast<const uh_keypoint*>(d_kps), n_cap, d_n, o->d_depth_img.as<uint16_t>(), (size_t)w, w, h,
+                                      job->depth_scale, d_depth)))
+                return rc;
+        }
+    }
     // the completion word as its own one-thread launch behind the last kernel (a ticket counter inside describe_kernel — one system-scope
     // release and one same-address atomic per workgroup — cost 10 us more than this launch)
     const unsigned long long word = ++o->seq;
@@ -2035,6 +2098,7 @@ static int extract_one(uh_orb* o, const uint8_t* img, int w, int h, size_t strid
     uh_orb::Pending& pd = o->pending;
     pd.active = true; pd.direct = direct; pd.und_direct = und_direct; pd.word = word; pd.kps = kps; pd.desc = desc; pd.und_xy = und_xy; pd.cap = cap;
     pd.o_cnt = o_cnt; pd.o_kps = o_kps; pd.o_desc = o_desc; pd.o_und = o_und; pd.fr = fr;
+    pd.depth = job ? job->depth : nullptr; pd.o_depth = o_depth;
     if (early) {   // the keypoints' undistorted positions and octaves are enough for the caller to go on with (the kd-tree): the rest is collected by _end
         char* he = o->h_early.host<char>();
         if ((rc = uh::wait_host_word(reinterpret_cast<volatile unsigned long long*>(he), ea.word, st, "uh_orb_extract_frame_dev_begin"))) { pd.active = false; return rc; }
@@ -2065,6 +2129,7 @@ static int extract_finish(uh_orb* o, int* n_out) {
         std::memcpy(pd.desc, hb + pd.o_desc, (size_t)n * 32);
     }
     if (pd.und_xy && !pd.und_direct && n > 0) std::memcpy(pd.und_xy, hb + pd.o_und, (size_t)n * 8);
+    if (pd.depth && n > 0) std::memcpy(pd.depth, hb + pd.o_depth, (size_t)n * 4);
     return UH_OK;
 }
 
@@ -2093,6 +2158,49 @@ int uh_orb_extract_frame_dev_end(uh_orb* o, int* n_out) {
     UH_REQUIRE(o, "uh_orb_extract_frame_dev_end: NULL extractor");
     if (!o->pending.active) return UH_OK;   // (an empty image: _begin had nothing to launch)
     return extract_finish(o, n_out);
+}
+int uh_orb_set_stereo(uh_orb* o, float bl, float max_desc_dist) {
+    UH_REQUIRE(o, "uh_orb_set_stereo: NULL extractor");
+    UH_REQUIRE(bl > 0.f, "uh_orb_set_stereo: baseline bl = %g must be > 0", (double)bl);
+    o->st_bl = bl; o->st_max_desc_dist = max_desc_dist;
+    return UH_OK;
+}
+int uh_orb_extract_stereo(uh_orb* o, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, int channels, uh_keypoint* kps, uint8_t* desc,
+                          float* und_xy, float* depth, int cap, int* n_out, uh_dev_frame* frame, uh_stereo_right* right_out) {
+    UH_REQUIRE(o && n_out, "uh_orb_extract_stereo: NULL argument");
+    UH_REQUIRE(left && right && w > 0 && h > 0, "uh_orb_extract_stereo: both images are needed (%d x %d)", w, h);
+    UH_REQUIRE(o->cam.on, "uh_orb_extract_stereo: no camera set (uh_orb_set_camera): the match needs Frame::und_kpts and fx");
+    UH_REQUIRE(o->st_bl > 0.f, "uh_orb_extract_stereo: no stereo parameters set (uh_orb_set_stereo)");
+    UH_REQUIRE(o->lvl_first == 0 && o->lvl_end < 0, "uh_orb_extract_stereo: a pyramid-level shard is not a frame");
+    UH_REQUIRE(cap >= 0 && (cap == 0 || depth), "uh_orb_extract_stereo: NULL depth array");
+    UH_REQUIRE(!right_out || (right_out->kps && right_out->desc), "uh_orb_extract_stereo: right_out without buffers");
+    DepthJob job;
+    job.right = right; job.depth = depth;
+    if (right_out) right_out->n = 0;
+    int rc = extract_one(o, left, w, h, stride, channels, kps, desc, und_xy, cap, n_out, frame, nullptr, &job);
+    if (rc || !right_out) return rc;
+    // inspection: the right image's extraction, copied out behind the call's one wait
+    int nr = 0;
+    UH_HIP_CHECK(hipMemcpyAsync(&nr, o->d_counts.p, sizeof(int), hipMemcpyDeviceToHost, o->ctx->stream));
+    UH_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
+    nr = std::min(std::max(nr, 0), std::max(o->fp.maxFeatures, 1));
+    if (nr > 0) {
+        UH_HIP_CHECK(hipMemcpyAsync(right_out->kps, o->d_kps.p, (size_t)nr * sizeof(uh_keypoint), hipMemcpyDeviceToHost, o->ctx->stream));
+        UH_HIP_CHECK(hipMemcpyAsync(right_out->desc, o->d_desc.p, (size_t)nr * 32, hipMemcpyDeviceToHost, o->ctx->stream));
+        UH_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
+    }
+    right_out->n = nr;
+    return UH_OK;
+}
+int uh_orb_extract_rgbd(uh_orb* o, const uint8_t* img, int w, int h, size_t stride, int channels, const uint16_t* depth_img, size_t depth_stride,
+                        float depth_scale, uh_keypoint* kps, uint8_t* desc, float* und_xy, float* depth, int cap, int* n_out, uh_dev_frame* frame) {
+    UH_REQUIRE(o && n_out, "uh_orb_extract_rgbd: NULL argument");
+    UH_REQUIRE(img && depth_img && w > 0 && h > 0, "uh_orb_extract_rgbd: colour and depth image are needed (%d x %d)", w, h);
+    UH_REQUIRE(depth_stride >= (size_t)w * 2 && (depth_stride & 1) == 0, "uh_orb_extract_rgbd: depth stride %zu (bytes) below the row or odd", depth_stride);
+    UH_REQUIRE(cap >= 0 && (cap == 0 || depth), "uh_orb_extract_rgbd: NULL depth array");
+    DepthJob job;
+    job.depth_img = depth_img; job.depth_stride = depth_stride; job.depth_scale = depth_scale; job.depth = depth;
+    return extract_one(o, img, w, h, stride, channels, kps, desc, und_xy, cap, n_out, frame, nullptr, &job);
 }
 int uh_orb_set_camera(uh_orb* o, const uh_camera* cam) {
     UH_REQUIRE(o, "uh_orb_set_camera: NULL extractor");
