@@ -1,11 +1,13 @@
 // Times the persistent local BA's per-workgroup Schur product S = Yt^T Yt (4x4 register blocks, nblk upper blocks x KS splits of the K range,
-// ba_persist.hpp) WITHOUT the rest of a trial: one workgroup of 256 threads (one wave per SIMD) on every CU, a random panel in LDS, the loop
+// the kernel's form until the product moved to the f64 matrix pipe, now schur_item_product.hpp beside this file; schur_product_mfma.hip times the
+// two against each other) WITHOUT the rest of a trial: one workgroup of 256 threads (one wave per SIMD) on every CU, a random panel in LDS, the loop
 // the kernel had before the hand-pipelined one (form 0: four rows per iteration, clamped row index, 1.0 / 0.0 row mask, the compiler's own
 // schedule) against schur_item_product (form 1).  Per form: shader clocks (s_memtime) of the best of `reps` repetitions on workgroup 0, the
 // wall clock (100 MHz) over all repetitions, and the two results compared bit for bit.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I ucoslam-cv3_amd/csrc -I include scripts/micro/schur_product.hip ucoslam-cv3_amd/csrc/ctx.hip -o scripts/micro/schur_product.bin
 #include <hip/hip_runtime.h>
 #include "ba.hip"
+#include "schur_item_product.hpp"
 #include <cstdio>
 #include <cstring>
 #include <random>

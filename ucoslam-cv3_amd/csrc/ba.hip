@@ -2535,18 +2535,12 @@ static bool plan_persist(const BAPlanIn& in, const BAKnobs& kn, const BALimits& 
     pl.krows = (3 * Lw + 15) & ~15;
     const int n = 6 * nfree;
     pl.nb4 = (n + 3) / 4; pl.nblk = pl.nb4 * (pl.nb4 + 1) / 2;
-    pl.off_cam = pl.nblk * 16;   // the product part of a partial: the upper 4 x 4 blocks (vector FMA; the v_mfma_f64 form of rounds 2-4 was slower on gfx950 and is gone: docs/DESIGN_history_r1_r3.md, profiles/r03_mfma_f64.json)
+    pl.off_cam = pl.nblk * 16;   // the product part of a partial: the upper 4 x 4 blocks (the format the v_mfma_f64 product writes its 16 x 16 tiles into)
     pl.nelem = pl.off_cam + NF * 27 + 6 * NF + 4;
     pl.SL = (uh_div_up(pl.nelem, G) + 1) & ~1;
-    // K-splits of the Schur product: work items = nblk * KS over 256 lanes, each krows / KS rows deep; the splits' partial blocks must
-    // fit the LDS region the reduced system occupies later ((n + 1)^2 doubles)
-    pl.KS = 1;
-    int best = 1 << 30;
-    for (int ks = 1; ks <= 6; ks++) {
-        if (ks > 1 && ks * pl.off_cam > (n + 1) * (n + 1) + 1452) break;
-        const int rounds = uh_div_up(pl.nblk * ks, kPThreads), depth = (uh_div_up(pl.krows, ks) + 3) & ~3;
-        if (rounds * depth < best) { best = rounds * depth; pl.KS = ks; }
-    }
+    // K-splits of the Schur product = the partials its form leaves in LDS (schur_product_mfma: one per wave up to three tile rows, one
+    // from four on); persist_lds sizes U from it
+    pl.KS = schur_mfma_splits(uh_div_up(n, 16));
     pl.lds = NF == 8 ? persist_lds<8>(pl.krows, n, pl.max_fix, pl.kfix, pl.off_cam, pl.KS, pl.SL).total_bytes
                      : persist_lds<16>(pl.krows, n, pl.max_fix, pl.kfix, pl.off_cam, pl.KS, pl.SL).total_bytes;
     return pl.lds <= lim.max_lds;

@@ -11,8 +11,12 @@
 //     the 24-byte observation, forms Hll, its Cholesky factor L (3x3) and the whitened blocks Y_e = Hpl_e L^-T straight into an
 //     LDS panel Yt[3*landmark + k][6*camera + a];
 //   * Schur complement (g2o/core/block_solver.hpp:341-392): sum_l Hpl D^-1 Hpl^T = Yt^T Yt, a dense 48 x 48 x (3*Lw) fp64 product
-//     per workgroup — vector FMA on 4x4 register blocks (v_mfma_f64_16x16x4_f64 on the six upper 16x16 tiles was measured in rounds
-//     2-4 and removed in round 5: 6.4 FMA / clock / SIMD against 11.4 for v_fma_f64 on gfx950);  b_schur = Yt^T (L^-1 b_l);
+//     per workgroup — v_mfma_f64_16x16x4_f64 on the upper 16x16 tiles, every panel register fetched once per k-step for all the tiles
+//     that use it (schur_product_mfma; one MFMA per 64 clocks = 16 FMA / clock / SIMD, against ~11 for v_fma_f64 on 4x4 register
+//     blocks, which also read 4 bytes of LDS per FMA.  The MFMA form of rounds 2-4 lost for how it was fed — uneven tile loads per
+//     wave, run-time operand selection: 267-376 clocks per MFMA —, not for the instruction's rate: the "one MFMA per ~160 cycles" of
+//     scripts/micro/mfma_f64_rate.hip was contradicted by that run's own counters, SQ_VALU_MFMA_BUSY_CYCLES / SQ_INSTS_MFMA = 64.0);
+//     b_schur = Yt^T (L^-1 b_l);
 //   * back-substitution (block_solver.hpp:419-442): dx_l = L^-T (L^-1 b_l - Y_l^T dx_p) from the same panel;
 //   * workgroups exchange only reduction partials, through write-through (sc1) stores of SELF-VALIDATING words: every double travels
 //     as two 64-bit words (32 payload bits | 32-bit tag = launch sequence and exchange round), so a reader polls the data itself —
@@ -45,7 +49,7 @@ constexpr long long kPTimeoutTicksDefault = 10000000ll;   // 100 ms of the 100 M
 
 struct BAPersist {
     int G, Lw, krows, SL, nelem, max_fix, kfix;
-    int nb4, nblk, KS;   // the product's 4x4 block grid: nb4 = ceil(n / 4) block columns, nblk upper blocks, KS splits of the K range
+    int nb4, nblk, KS;   // the product partial's 4x4 block grid: nb4 = ceil(n / 4) block columns, nblk upper blocks; KS: the K-split slots the product writes (schur_mfma_splits)
     int n1, n2, stop_at_begin;
     int speculate;        // 1: speculative trials (see the trial loop); UH_BA_SPEC=0 keeps the three-hand-off form for A/B measurements
     unsigned launch_id;   // tags the error / completion words of this launch
@@ -79,7 +83,7 @@ constexpr int kFxCam = 20;   // doubles per fixed frame in LDS: R | t (12), fx f
 struct PersistLds {      // offsets in doubles into the dynamic LDS block
     int Yt, U, usz, out, wsum, x, bp, bs, bsp, wv, pose, poseR, red, sc, fxchi, fxobs, fxcam, fxact_bytes, fxk_bytes, fxid_bytes, fxptr_bytes, pair_bytes, blk_bytes, flag_bytes, total_bytes;
 };
-// off_cam = elements of the product part of a partial (nblk * 16, or the six MFMA tiles), KS = K-splits of the product, SL = slice length
+// off_cam = elements of the product part of a partial (nblk * 16), KS = K-split slots of the product, SL = slice length
 template <int NF>
 __host__ __device__ inline PersistLds persist_lds(int krows, int n, int max_fix, int kfix, int off_cam, int KS, int SL) {
     constexpr int NP = 6 * NF, YS = NP + 2;
@@ -116,70 +120,121 @@ __host__ __device__ inline PersistLds persist_lds(int krows, int n, int max_fix,
     return o;
 }
 
-// One item of the Schur product S = Yt^T Yt: acc4[r * 4 + c] += sum over `nrows` panel rows of ra[r] * rb[c], rows ascending (ra / rb:
-// the item's first row at its two block columns, in LDS, 16-byte aligned; a row is YS doubles; nrows <= 0: nothing).
-// Software-pipelined by hand: the compiler's own schedule issues a group's sixteen ds_read_b128 at the top of an iteration and the
-// FMAs behind a ladder of waits, fetching nothing ahead, so every group of four rows exposed an LDS round trip with all four waves
-// of the CU on the LDS at once, behind 12 v_mul_f64 of a row mask and the clamped row index's integer multiplies.  Here
-// the reads are inline asm with counted waits, which the compiler neither merges nor moves: whole groups of four rows run
-// through ONE operand set that is refilled row by row — as soon as row u of a group has been multiplied, row u of the next group
-// is requested into the same registers, so twelve to sixteen reads (three to four rows, >= 48 FMAs of cover) are in flight at every
-// wait.  LDS reads return in order: lgkmcnt(12) at 16 outstanding means the oldest row has arrived; anything else the compiler has
-// in flight only makes a counted wait stricter.  The wait statements name the row's registers as in-outs (no consumer can be placed
-// ahead of them) and are followed by sched_barrier(0) (register-only arithmetic is otherwise moved past an asm wait).
-// Rows beyond the last whole group (a K-split of 11 or 10 rows: 33 landmarks, three splits) go one at a time through ordinary loads.
-// scripts/micro/schur_product.hip, MI355X, eight free cameras x 96 rows (512 FMAs per lane), product + stores + barrier: 8 600 clocks
-// before, 6 230 now; the same loop's FMAs alone (operands held in registers) 5 320, its reads alone 5 120 — the two limits lie
-// together, ~17 % below the loop (profiles/ba_product_micro.txt).
-typedef double ba_d2 __attribute__((ext_vector_type(2)));
-template <int YS>
-__device__ __forceinline__ void schur_item_product(const double* ra, const double* rb, int nrows, double (&acc4)[16]) {
-    constexpr int RB = YS * 8;   // bytes per panel row: the four rows of a group are immediate offsets (3 * RB + 16 < 65536) from one base each
-    static_assert(RB % 16 == 0 && 3 * RB + 16 < 65536, "panel row stride");
+// The Schur product S = Yt^T Yt on the f64 matrix pipe, in 16x16 tiles: v_mfma_f64_16x16x4_f64 over k-steps of four panel rows.  Lane
+// (i16 = lane & 15, kq = lane >> 4) reads Yt[4 k4 + kq][16 cg + i16]: that ONE register is the A operand of every tile in tile row cg
+// and the B operand of every tile in tile column cg, so a k-step costs NTT ds_read_b64 per lane for all NTT (NTT + 1) / 2 upper tiles
+// (~1 byte of LDS per FMA; consecutive lanes read consecutive doubles).  The next k-step's operands are requested behind this step's
+// first MFMA.  A wave's tile list is static (constant register-array indices, no predicate around an MFMA):
+//   KSPLIT:  the wave owns EVERY upper tile over the k-steps [k4beg, k4end) — its quarter of the K range — and writes K-split slot Uw;
+//   !KSPLIT: the wave owns tiles WV, WV + 4, ... over the whole K range (one slot).
+// Write-out: C layout row = 4 reg + (lane >> 4), col = lane & 15 (as ba_schur_reduce_kernel reads it) into the partial's 4x4-block
+// format — element (row, col) at prod_index(row, col) for every block (bi <= bj < nb4), i.e. exactly the words the 4x4 form wrote
+// (panel columns >= n are zero, so are their products); a (tile, reg) pair lands on 64 consecutive doubles.
+typedef double ba_f64x4 __attribute__((ext_vector_type(4)));
+template <int YS, int NTT, int WV, bool KSPLIT>
+__device__ __forceinline__ void schur_mfma_tiles(const double* Yt, int k4beg, int k4end, double* Uw, int nb4, int lane) {
+    constexpr int TT = NTT * (NTT + 1) / 2, NOWN = KSPLIT ? TT : (TT - WV + 3) / 4, T0 = KSPLIT ? 0 : WV, TS = KSPLIT ? 1 : 4;
+    static_assert(NOWN >= 1 && 16 * NTT <= YS, "tile list / panel row");
+    const int i16 = lane & 15, kq = lane >> 4;
+    ba_f64x4 acc[NOWN];
+    // The whole k loop is inline asm, which the compiler neither merges nor moves (statements keep their order among themselves):
+    //   * operands: two sets; a step waits for its own set — the only reads in flight, so lgkmcnt(0); LDS reads return in order and
+    //     anything older the compiler has in flight only arrives first —, issues its first MFMA, requests the NEXT step's set and
+    //     issues the rest: the reads have the remaining MFMAs (64 clocks each) to arrive.  (Left to itself the compiler folds a
+    //     prefetch back into load -> wait -> MFMA inside one k-step.)  The wait statements name the set's registers as in-outs: no
+    //     consumer, and no copy, can be placed ahead of them.  The last step requests its own rows again (adv 0) and the wait behind
+    //     the loop drains them: nothing past the range is touched, no read stays in flight into a register that has been handed on.
+    //   * accumulators: "v" operands — the MFMA's VGPR form.  The builtin takes accumulator registers (AGPRs) in a kernel that may
+    //     use more than 256 registers, on top of the ~130 AGPRs this kernel's long-lived state already occupies: <8> grew from 383
+    //     to 458 registers and <16> spilled to scratch.  Here the product needs 8 NOWN + 4 NTT VGPRs, fewer than the 4x4 form's 96.
+    //   * wait states the compiler cannot see into: a step's first MFMA opens with s_nop 1; an accumulate chain (D -> the next MFMA's
+    //     C, whole) needs none; behind the loop 2 x s_nop 15 stand between the last MFMA (16 passes) and the first reader of an
+    //     accumulator.  The first k-step multiplies onto a literal 0.
     typedef __attribute__((address_space(3))) const double* lds_cptr;
-    unsigned pa = (unsigned)(size_t)(lds_cptr)ra, pb = (unsigned)(size_t)(lds_cptr)rb;
-    const int ng = nrows >> 2;
-    ba_d2 a01[4], a23[4], b01[4], b23[4];
-#define UH_SP_READ(u)                                                                                                   \
-    asm volatile("ds_read_b128 %0, %4 offset:%6\n\tds_read_b128 %1, %4 offset:%7\n\t"                                  \
-                 "ds_read_b128 %2, %5 offset:%6\n\tds_read_b128 %3, %5 offset:%7"                                      \
-                 : "=&v"(a01[u]), "=&v"(a23[u]), "=&v"(b01[u]), "=&v"(b23[u])                                          \
-                 : "v"(pa), "v"(pb), "n"((u) * RB), "n"((u) * RB + 16))
-#define UH_SP_WAIT(cnt, u)                                                                                              \
-    do {                                                                                                                \
-        asm volatile("s_waitcnt lgkmcnt(" #cnt ")" : "+v"(a01[u]), "+v"(a23[u]), "+v"(b01[u]), "+v"(b23[u]));          \
-        __builtin_amdgcn_sched_barrier(0);                                                                              \
-    } while (0)
-#define UH_SP_FMA(A01, A23, B01, B23)                                                                                   \
-    do {                                                                                                                \
-        const double av[4] = {(A01).x, (A01).y, (A23).x, (A23).y}, bv[4] = {(B01).x, (B01).y, (B23).x, (B23).y};       \
-        _Pragma("unroll") for (int r = 0; r < 4; r++)                                                                   \
-            _Pragma("unroll") for (int c = 0; c < 4; c++) acc4[r * 4 + c] = fma(av[r], bv[c], acc4[r * 4 + c]);        \
-    } while (0)
-#define UH_SP_ROW(cnt, u, refill)                                                                                       \
-    do {                                                                                                                \
-        UH_SP_WAIT(cnt, u);                                                                                             \
-        UH_SP_FMA(a01[u], a23[u], b01[u], b23[u]);                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                              \
-        if (refill) UH_SP_READ(u);                                                                                      \
-    } while (0)
-    if (ng > 0) {
-        UH_SP_READ(0); UH_SP_READ(1); UH_SP_READ(2); UH_SP_READ(3);
-        for (int g = 1; g < ng; g++) {   // group g - 1 is multiplied while group g arrives
-            pa += 4 * RB; pb += 4 * RB;
-            UH_SP_ROW(12, 0, true); UH_SP_ROW(12, 1, true); UH_SP_ROW(12, 2, true); UH_SP_ROW(12, 3, true);
+    unsigned pa = (unsigned)(size_t)(lds_cptr)(Yt + (4 * k4beg + kq) * YS + i16);
+    double opA[NTT], opB[NTT];
+    auto rd = [&](double (&x)[NTT]) {
+#pragma unroll
+        for (int cg = 0; cg < NTT; cg++) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=&v"(x[cg]) : "v"(pa), "n"(128 * cg));
+    };
+    auto wait_for = [&](double (&x)[NTT]) {
+#pragma unroll
+        for (int cg = 0; cg < NTT; cg++) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[cg]));
+    };
+    auto step = [&](double (&x)[NTT], double (&y)[NTT], unsigned adv, bool first) {
+        wait_for(x);
+#pragma unroll
+        for (int u = 0; u < NOWN; u++) {   // upper tile: tile row = the smaller index
+            const double a = x[schur_tile_col(T0 + TS * u)], b = x[schur_tile_row(T0 + TS * u)];
+            if (first) {
+                if (u == 0) asm volatile("s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, 0" : "=&v"(acc[u]) : "v"(a), "v"(b));
+                else asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, 0" : "=&v"(acc[u]) : "v"(a), "v"(b));
+            } else {
+                if (u == 0) asm volatile("s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[u]) : "v"(a), "v"(b));
+                else asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[u]) : "v"(a), "v"(b));
+            }
+            if (u == 0) {
+                pa += adv;
+                rd(y);
+            }
         }
-        UH_SP_ROW(12, 0, false); UH_SP_ROW(8, 1, false); UH_SP_ROW(4, 2, false); UH_SP_ROW(0, 3, false);
+    };
+    constexpr unsigned RB4 = 4 * YS * 8;   // bytes per k-step
+    // The two sets alternate and are never copied (a register copy of a set whose reads are in flight would copy stale words: the
+    // compiler does not know they are pending): the first step is peeled, then the steps go in pairs, an odd one behind them.
+    const int ks = k4end - k4beg;
+    rd(opA);
+    step(opA, opB, 1 < ks ? RB4 : 0u, true);
+    int sdone = 1;
+    for (; sdone + 2 <= ks; sdone += 2) {
+        step(opB, opA, RB4, false);
+        step(opA, opB, sdone + 2 < ks ? RB4 : 0u, false);
     }
-    for (int k = 4 * ng; k < nrows; k++) {   // the split's last one to three rows; a row past the end is not touched
-        const ba_d2 ta01 = *reinterpret_cast<const ba_d2*>(ra + k * YS), ta23 = *reinterpret_cast<const ba_d2*>(ra + k * YS + 2);
-        const ba_d2 tb01 = *reinterpret_cast<const ba_d2*>(rb + k * YS), tb23 = *reinterpret_cast<const ba_d2*>(rb + k * YS + 2);
-        UH_SP_FMA(ta01, ta23, tb01, tb23);
+    if (sdone < ks) { step(opB, opA, 0u, false); wait_for(opA); }
+    else wait_for(opB);
+    asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc[0]));
+#pragma unroll
+    for (int u = 1; u < NOWN; u++) asm volatile("" : "+v"(acc[u]));
+    // Write-out.  Everything a store's address and predicate need is worked out HERE from an opaque copy of the lane index: these
+    // values are the same in every trial, and hoisted out of the trial loop they were 26 more long-lived registers in <8> and put
+    // <16> (twelve tile lists) into scratch.  One lane offset + a scalar per (tile, reg): a v_add and a store each.
+    int lo = lane;
+    asm volatile("" : "+v"(lo));
+    const int bjl = (lo & 15) >> 2;
+    double* const Ul = Uw + (bjl * 16 + (lo >> 4) * 4 + (lo & 3));
+#pragma unroll
+    for (int u = 0; u < NOWN; u++) {
+        const int ti = schur_tile_col(T0 + TS * u), tj = schur_tile_row(T0 + TS * u);
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+            const int bi = 4 * ti + reg;   // block row (a constant); the lane's block column is 4 tj + bjl
+            if ((ti < tj || reg <= bjl) && 4 * tj + bjl < nb4) Ul[(bi * nb4 - bi * (bi - 1) / 2 - bi + 4 * tj) * 16] = acc[u][reg];
+        }
     }
-#undef UH_SP_ROW
-#undef UH_SP_FMA
-#undef UH_SP_WAIT
-#undef UH_SP_READ
+}
+// K-split slots the MFMA form of the product writes for ntt tile rows: up to three (18 columns a tile row: up to eight free cameras) every
+// wave takes a quarter of the K range (krows is a multiple of 16: whole k-steps) and all tiles — 24 accumulator doubles at most; from
+// four on (up to 21 tiles: 84 accumulator doubles per lane would not fit beside the trial's state) the tiles are dealt to the waves.
+__host__ __device__ constexpr int schur_mfma_splits(int ntt) { return ntt <= 3 ? kPWaves : 1; }
+// The workgroup's product, one call: every wave its static instantiation (wv: the wave index as a scalar).
+template <int NF>
+__device__ __forceinline__ void schur_product_mfma(const double* Yt, int krows, int ntt, double* U, int off_cam, int nb4, int wv, int lane) {
+    constexpr int YS = 6 * NF + 2;
+    const int k4 = krows >> 2, ks = krows >> 4;
+    switch (ntt) {
+    case 1: schur_mfma_tiles<YS, 1, 0, true>(Yt, wv * ks, wv * ks + ks, U + wv * off_cam, nb4, lane); break;
+    case 2: schur_mfma_tiles<YS, 2, 0, true>(Yt, wv * ks, wv * ks + ks, U + wv * off_cam, nb4, lane); break;
+    case 3: schur_mfma_tiles<YS, 3, 0, true>(Yt, wv * ks, wv * ks + ks, U + wv * off_cam, nb4, lane); break;
+    default:
+        if constexpr (NF == 16) {
+#define UH_SCHUR_MFMA_NTT(N) case N: switch (wv) { \
+            case 0: schur_mfma_tiles<YS, N, 0, false>(Yt, 0, k4, U, nb4, lane); break; case 1: schur_mfma_tiles<YS, N, 1, false>(Yt, 0, k4, U, nb4, lane); break; \
+            case 2: schur_mfma_tiles<YS, N, 2, false>(Yt, 0, k4, U, nb4, lane); break; default: schur_mfma_tiles<YS, N, 3, false>(Yt, 0, k4, U, nb4, lane); break; } break;
+            switch (ntt) { UH_SCHUR_MFMA_NTT(4) UH_SCHUR_MFMA_NTT(5) default: UH_SCHUR_MFMA_NTT(6) }
+#undef UH_SCHUR_MFMA_NTT
+        }
+        break;
+    }
 }
 
 // Tagged exchange words.  Element i of a buffer = words 2i (low 32 payload bits) and 2i+1 (high 32 bits), each with the round's tag in
@@ -479,8 +534,7 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
     int* const s_flag = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + o.flag_bytes);   // [0] solve ok, [1] error
 
     const int G = q.G, SL = q.SL;
-    // (OFF_CAM / OFF_BS / OFF_SC: element offsets of a partial — the product (the nblk upper 4x4 blocks of the vector-FMA form, or six 16x16
-    // MFMA tiles), camera sums, b_schur, scalars)
+    // (OFF_CAM / OFF_BS / OFF_SC: element offsets of a partial — the product (its nblk upper 4x4 blocks), camera sums, b_schur, scalars)
     const int l0 = g * q.Lw;
     const int nl = min(q.Lw, d.P - l0);
     const int ll = tid >> LG, s = tid & (NF - 1);
@@ -778,30 +832,14 @@ __global__ __launch_bounds__(kPThreads) void ba_persist_kernel(BAPtrs p, BADims 
         // scalars of a partial: chi2 at the linearisation point, (speculative trial:) the previous trial's scale sum, max |Hll_jj|, stop flag
         if (tid == 0) { s_out[NF * 27 + NP] = cs; s_out[NF * 27 + NP + 1] = ss; s_out[NF * 27 + NP + 2] = mx; s_out[NF * 27 + NP + 3] = g == 0 ? stop_val : 0.0; }
         if (!first) UH_BA_CLKT(54);
-        // S = Yt^T Yt: vector FMA, 4x4 register blocks — the nblk upper blocks of the nb4 x nb4 block grid x KS splits of the K
-        // range (78 x 3 = 234 items for eight free cameras: one per lane; more cameras: several per lane), 16 accumulators each, four
-        // ds_read_b128 per 16 FMAs; the splits are added in order through LDS.  Measured on MI355X (scripts/micro/mfma_f64_rate.hip):
-        // v_fma_f64 sustains 9.1-11.4 FMA/clk/SIMD, v_mfma_f64_16x16x4_f64 issues every ~160 cycles = 6.4: the MFMA form of this product
-        // (six upper 16x16 tiles split over the waves, accumulators resident in AGPRs; rounds 2-4 behind UH_BA_SCHUR=mfma) lost on
-        // gfx950 — kernel 0.454 against 0.430 ms — and was removed in round 5.
-        if (!first) {   // (U is free: its last users — the reduced system, the slice reduction's scratch — are behind barriers)
-            const int nitems = q.nblk * q.KS;
-            const int kc = (q.krows + q.KS - 1) / q.KS;
-            for (int item = tid; item < nitems; item += kPThreads) {
-                const int kt = item / q.nblk, bq = item - kt * q.nblk;
-                const int bi = s_blk[bq][0], bj = s_blk[bq][1];
-                const int kbeg = kt * kc, kend = min(q.krows, kbeg + kc);
-                double acc4[16];
-#pragma unroll
-                for (int i = 0; i < 16; i++) acc4[i] = 0;
-                // four rows per group, each row's reads requested a group ahead of its FMAs (schur_item_product: the pipeline is
-                // pinned with inline asm — left to itself the compiler serialises load -> wait -> FMA inside an iteration)
-                schur_item_product<YS>(Yt + kbeg * YS + 4 * bi, Yt + kbeg * YS + 4 * bj, kend - kbeg, acc4);
-#pragma unroll
-                for (int i = 0; i < 16; i++) U[kt * OFF_CAM + bq * 16 + i] = acc4[i];
-            }
-            // (the K-splits' partials stay apart: the store loop at the end adds them, in order, on the way out)
-        }
+        // S = Yt^T Yt on the f64 matrix pipe (schur_product_mfma): the upper 16x16 tiles, every wave a quarter of the K range up to three
+        // tile rows (one K-split slot per wave; the splits are added in order on the way out), the tiles dealt to the waves from four on.
+        // scripts/micro/schur_product_mfma.hip, MI355X, eight free cameras x 96 rows, product + write-out + barrier: 4 600 shader
+        // clocks (36 MFMAs per wave at 64 clocks each behind the pipe's start-up) against 6 300 for the 4x4 register-block vector-FMA
+        // form it replaces, which was bound by its LDS reads (4 bytes per FMA; here ~1) and by the FMA issue rate together
+        // (profiles/ba_mfma_product_micro.txt).
+        if (!first)   // (U is free: its last users — the reduced system, the slice reduction's scratch — are behind barriers)
+            schur_product_mfma<NF>(Yt, q.krows, (n + 15) >> 4, U, OFF_CAM, q.nb4, wvu, lane);
         if (!first) UH_BA_CLKT(55);
         __syncthreads();   // the product (U) and the camera sums (s_out) are complete
         if (!first) UH_BA_CLKT(56);
