@@ -1068,6 +1068,59 @@ int  uh_projmatch_debug_tree(uh_projmatch* pm, int32_t* n_nodes, const void** no
 /* the same build as a host-only function (no GPU needed): nodes24_out has room for 2n+2 nodes, leaf_idx_out for n entries */
 int  uh_kdtree_build_host(const float* xy, int32_t n, int32_t* n_nodes, void* nodes24_out, uint32_t* leaf_idx_out,
                           double* root_box4, int32_t* max_depth);
+
+/* ------------------------------------------------------------------------
+ * Fuse search — one projection search of the mapper's search-and-fuse step (src/utils/mapmanager.cpp, the private member of MapManager
+ * that returns vector<uint32_t> and takes Frame&: ORB-SLAM's SearchInNeighbors), the stage between the new map points and local BA.
+ * The reference runs it once per neighbour keyframe with the new keyframe's points and once with every neighbour's points against the
+ * new keyframe; each of those K + 1 searches is one call here, and the caller applies a call's events (fuseMapPoints /
+ * addMapPointObservation, which rewrite normals, distances and descriptors) before the next: ucoslam_hip::MapPointFuser
+ * (adaptors.hpp) and fuse.py's search_in_neighbors do exactly that.  Within one call no point depends on another.
+ *
+ * Per point of the table, in this order (status code of what ends it):
+ *   1  skip[i] != 0 (the caller's tests: not a map point, bad, already observed in the searched frame)
+ *   2  Frame::project(p, true, true) is NaN: depth < 0, or outside [min, max) of the image bounds (frame.h:140-159)
+ *   3  dist = cv::norm(camera centre - p) < 0.8f * min or > 1.2f * max distance invariance (both ends are kept)
+ *   4  MapPoint::getViewCos(camera centre) < 0.5 (mappoint.h:99)
+ *   then level = predictScale(dist, max) of the NEW keyframe (predict_scale_factors[1], predict_n_levels; frame.h:129-136),
+ *   radius = th * target scale_factors[level], times `widen` where viewCos < 0.98, Frame::getKeyPointsInRegion(p2d, radius, level - 1,
+ *   level) in kd-tree order (frame.cpp:102-115), and the FIRST keypoint of the strictly smallest Hamming distance below
+ *   (float)(max_desc_dist + 1e-3):
+ *   0  found: best_kp / best_dist          5  none: best_kp = -1, best_dist = the threshold (as for codes 1-4)
+ * The camera centre is Frame::getCameraCenter of pose_f2g (frame.h:189-197).  th = 0 means the reference's 2.5; widen is 1.4f for a
+ * neighbour keyframe (first half) and 1 for the new keyframe (second half).
+ *
+ * The point table lives in pinned memory of the handle as 64-byte records: uh_fuse_set_points packs it once per keyframe insertion,
+ * uh_fuse_update_points rewrites the rows the apply step changed (new_values holds n_rows points, the k-th for rows[k]).  ids is not read.
+ * uh_fuse_search: `target` / `target_params` are the argument pair of uh_projmatch_set_frame_dev, with either tree builder; target ==
+ * NULL uploads the host arrays of target_params into a frame object of the handle first (a utility path).  One launch, one wait, on the
+ * context's stream.  uh_fuse_search_host is the same search on the calling core from host arrays (uh_kdtree_build_host's tree, no GPU
+ * needed): the same three outputs bit for bit.
+ *
+ * Refused with UH_EINVAL before any launch: predict_n_levels > the target's n_levels (the reference would index past the target's
+ * scaleFactors) or < 2, more than 16 target levels, a row outside the table, a device frame without a complete kd-tree, a tree deeper
+ * than 62 levels, more than 4096 keypoints (what a device frame holds; both forms), more than uh_fuse_max_points() points.  A walk
+ * stack overflow inside the launch is reported as UH_EINVAL as well, never as a result.
+ * ------------------------------------------------------------------------ */
+#define UH_FUSE_FOUND       0
+#define UH_FUSE_SKIPPED     1
+#define UH_FUSE_NO_PROJECT  2
+#define UH_FUSE_DISTANCE    3
+#define UH_FUSE_VIEW_COS    4
+#define UH_FUSE_NO_KEYPOINT 5
+typedef struct uh_fuse uh_fuse;
+int  uh_fuse_create(uh_ctx* ctx, uh_fuse** out);
+void uh_fuse_destroy(uh_fuse* f);
+int32_t uh_fuse_max_points(void);
+int  uh_fuse_set_points(uh_fuse* f, const uh_map_points* points);
+int  uh_fuse_update_points(uh_fuse* f, int32_t n_rows, const int32_t* rows, const uh_map_points* new_values);
+int  uh_fuse_search(uh_fuse* f, uh_dev_frame* target /* or NULL */, const uh_proj_frame* target_params, const float* pose_f2g /* row-major 4x4 */,
+                    const float* predict_scale_factors, int32_t predict_n_levels, const uint8_t* skip /* n or NULL */, float th, float widen,
+                    float max_desc_dist, int32_t* best_kp_out, float* best_dist_out, uint8_t* status_out);
+int  uh_fuse_search_host(const uh_map_points* points, const uh_proj_frame* target_params, const float* pose_f2g, const float* predict_scale_factors,
+                         int32_t predict_n_levels, const uint8_t* skip /* n or NULL */, float th, float widen, float max_desc_dist,
+                         int32_t* best_kp_out, float* best_dist_out, uint8_t* status_out);
+
 /* test hooks of the device builder (csrc/kdbuild.hpp): the same outputs from the build kernel (n <= 4096; threads 0 = default, 256 or
  * 512), and — host only — the permutation its restatement of libstdc++'s std::sort gives n float keys (compared with std::sort itself) */
 int  uh_kdtree_build_dev(uh_ctx* ctx, const float* xy, int32_t n, int32_t threads, int32_t* n_nodes, void* nodes24_out, uint32_t* leaf_idx_out,

@@ -12,6 +12,7 @@
 // OpenCV, neither of which exists where this repository is built and tested, so they have never been compiled — INTEGRATION.md
 // sections 1 and 4 list them as the binding a maintainer adds inside the reference tree, on top of the classes below.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -694,6 +695,168 @@ std::vector<std::array<float, 3>> Triangulate(Context& ctx, const TrainView& Tra
     for (size_t i = 0; i < out.size(); i++) out[i] = {r.xyz_cam[3 * i], r.xyz_cam[3 * i + 1], r.xyz_cam[3 * i + 2]};
     return out;
 }
+
+// ---- MapManager's search-and-fuse step (utils/mapmanager.cpp, the private vector<uint32_t> member taking Frame&: ORB-SLAM's --------------
+// SearchInNeighbors), between the new map points and local BA.  MapPointFuser::searchInNeighbors(map, cur) is that function: one search per
+// non-bad neighbour keyframe with the points of `cur` (ascending keyframe index), one search of every neighbour's points in `cur`, each
+// search's events applied in point order through the map's own fuseMapPoints / addMapPointObservation before the next search starts.
+//
+// The map type is a template parameter with the reference's member names: TheKpGraph.getNeighbors(idx), keyframes[idx], map_points.is(id) /
+// map_points[id], fuseMapPoints(a, b, false), addMapPointObservation(id, frame, kp), getMapPointsInFrames(begin, end).  A keyframe gives
+// idx, isBad(), pose_f2g (posegraph_pose_ptr), und_kpts (pt.x, pt.y, octave), ids, scaleFactors, imageParams fx() fy() cx() cy(), minXY /
+// maxXY (.x, .y), getMapPoints() and its n x 32 descriptor bytes through frame_desc_ptr(frame); a map point gives id, isBad(), setBad(),
+// frames.count(idx), getCoordinates() / getNormal() (.x .y .z), get{Min,Max}DistanceInvariance() and its 32 descriptor bytes through
+// mappoint_desc_ptr(point).  The overloads below read a `desc` member with data(); for cv::Mat add ones that return m.ptr<uint8_t>().
+template <class Frame> inline auto frame_desc_ptr(const Frame& f) -> decltype(f.desc.data()) { return f.desc.data(); }
+template <class Point> inline auto mappoint_desc_ptr(const Point& p) -> decltype(p.desc.data()) { return p.desc.data(); }
+
+class MapPointFuser {
+   public:
+    explicit MapPointFuser(Context& ctx) : ctx_(&ctx), host_(false) { check(uh_fuse_create(ctx.get(), &h_)); }
+    MapPointFuser() = default;   // host form only: every search through uh_fuse_search_host, no GPU needed
+    ~MapPointFuser() {
+        for (auto& kv : cache_) uh_dev_frame_destroy(kv.second);
+        if (h_) uh_fuse_destroy(h_);
+    }
+    MapPointFuser(const MapPointFuser&) = delete;
+    MapPointFuser& operator=(const MapPointFuser&) = delete;
+
+    // run the searches on the calling core (the fallback of a host without a free GPU; the same results bit for bit)
+    void setHostForm(bool on) { if (!on && !h_) throw std::runtime_error("MapPointFuser: no device context"); host_ = on; }
+    // One uh_dev_frame per keyframe of the window is kept, keyed by keyframe index, and uploaded on first use: a keyframe's keypoints and
+    // descriptors never change.  forget(idx) when a keyframe leaves the map; adopt(idx, frame) hands over the frame the extractor left on the
+    // device (uh_orb_extract_frame_dev) instead of an upload — the fuser destroys it.
+    void forget(uint32_t idx) { auto it = cache_.find(idx); if (it != cache_.end()) { uh_dev_frame_destroy(it->second); cache_.erase(it); } }
+    void adopt(uint32_t idx, uh_dev_frame* frame) { forget(idx); cache_[idx] = frame; }
+    size_t cachedFrames() const { return cache_.size(); }
+
+    template <class Map, class Frame>
+    std::vector<uint32_t> searchInNeighbors(Map& map, Frame& cur, float maxDescDistance, float th = 2.5f) {
+        std::vector<uint32_t> removed;
+        std::vector<uint32_t> targets;   // std::set<uint32_t> of the non-bad neighbours: ascending, unique
+        for (auto n : map.TheKpGraph.getNeighbors(cur.idx))
+            if (!map.keyframes[n].isBad()) targets.push_back((uint32_t)n);
+        std::sort(targets.begin(), targets.end());
+        targets.erase(std::unique(targets.begin(), targets.end()), targets.end());
+        const std::vector<float> predict(cur.scaleFactors.begin(), cur.scaleFactors.end());
+        const std::vector<uint32_t> pts = cur.getMapPoints();
+        std::map<uint32_t, int> row_of;
+        for (size_t r = 0; r < pts.size(); r++) row_of[pts[r]] = (int)r;
+        std::vector<uint8_t> skip(pts.size());
+        std::vector<uint32_t> dirty;
+        bool fresh = true;
+        for (uint32_t t : targets) {
+            auto& KF = map.keyframes[t];
+            for (size_t r = 0; r < pts.size(); r++)
+                skip[r] = !map.map_points.is(pts[r]) || map.map_points[pts[r]].isBad() || map.map_points[pts[r]].frames.count(KF.idx) != 0;
+            search(map, KF, pts, skip, predict, th, 1.4f, maxDescDistance, fresh, dirty, row_of);
+            fresh = false;
+            apply(map, KF, pts, removed, dirty);
+        }
+        const std::vector<uint32_t> cands = map.getMapPointsInFrames(targets.begin(), targets.end());
+        skip.assign(cands.size(), 0);
+        for (size_t r = 0; r < cands.size(); r++) skip[r] = map.map_points[cands[r]].isBad() || map.map_points[cands[r]].frames.count(cur.idx) != 0;
+        dirty.clear();
+        search(map, cur, cands, skip, predict, th, 1.f, maxDescDistance, true, dirty, row_of);
+        apply(map, cur, cands, removed, dirty);
+        return removed;
+    }
+
+   private:
+    struct Table {
+        std::vector<float> pos, nrm, mind, maxd;
+        std::vector<uint8_t> desc;
+        uh_map_points view() const { return uh_map_points{(int32_t)mind.size(), nullptr, pos.data(), nrm.data(), mind.data(), maxd.data(), desc.data()}; }
+    };
+    template <class Map> static void fill(Map& map, const std::vector<uint32_t>& ids, Table& t) {
+        const size_t n = ids.size();
+        t.pos.assign(3 * n, 0.f); t.nrm.assign(3 * n, 0.f); t.mind.assign(n, 0.f); t.maxd.assign(n, 0.f); t.desc.assign(32 * n, 0);
+        for (size_t r = 0; r < n; r++) {
+            if (!map.map_points.is(ids[r])) continue;   // (skipped by the mask: the row is never read)
+            auto& mp = map.map_points[ids[r]];
+            const auto p = mp.getCoordinates();
+            const auto nv = mp.getNormal();
+            t.pos[3 * r] = p.x; t.pos[3 * r + 1] = p.y; t.pos[3 * r + 2] = p.z;
+            t.nrm[3 * r] = nv.x; t.nrm[3 * r + 1] = nv.y; t.nrm[3 * r + 2] = nv.z;
+            t.mind[r] = mp.getMinDistanceInvariance(); t.maxd[r] = mp.getMaxDistanceInvariance();
+            std::memcpy(&t.desc[32 * r], mappoint_desc_ptr(mp), 32);
+        }
+    }
+    template <class Map, class Frame>
+    void search(Map& map, Frame& KF, const std::vector<uint32_t>& ids, const std::vector<uint8_t>& skip, const std::vector<float>& predict, float th, float widen,
+                float maxDescDistance, bool fresh, std::vector<uint32_t>& dirty, const std::map<uint32_t, int>& row_of) {
+        const int n = (int)ids.size();
+        bk_.assign(n > 0 ? n : 1, -1); bd_.assign(n > 0 ? n : 1, 0.f); st_.assign(n > 0 ? n : 1, 0);
+        const std::vector<float> scale(KF.scaleFactors.begin(), KF.scaleFactors.end());
+        kps_.resize(KF.und_kpts.size());
+        for (size_t i = 0; i < kps_.size(); i++) {
+            kps_[i] = uh_keypoint{};
+            kps_[i].x = KF.und_kpts[i].pt.x; kps_[i].y = KF.und_kpts[i].pt.y; kps_[i].octave = (int32_t)KF.und_kpts[i].octave;
+        }
+        uh_proj_frame f{};
+        f.und_kpts = kps_.data(); f.n_kpts = (int32_t)kps_.size(); f.desc = frame_desc_ptr(KF);
+        f.scale_factors = scale.data(); f.n_levels = (int32_t)scale.size();
+        f.fx = KF.imageParams.fx(); f.fy = KF.imageParams.fy(); f.cx = KF.imageParams.cx(); f.cy = KF.imageParams.cy();
+        f.min_x = (int32_t)KF.minXY.x; f.min_y = (int32_t)KF.minXY.y; f.max_x = (int32_t)KF.maxXY.x; f.max_y = (int32_t)KF.maxXY.y;
+        const float* pose = posegraph_pose_ptr(KF.pose_f2g);
+        if (host_) {
+            Table t;
+            fill(map, ids, t);
+            const uh_map_points v = t.view();
+            check(uh_fuse_search_host(&v, &f, pose, predict.data(), (int32_t)predict.size(), skip.data(), th, widen, maxDescDistance, bk_.data(), bd_.data(), st_.data()));
+            return;
+        }
+        if (fresh) {
+            Table t;
+            fill(map, ids, t);
+            const uh_map_points v = t.view();
+            check(uh_fuse_set_points(h_, &v));
+        } else if (!dirty.empty()) {   // the rows the last apply step changed
+            std::vector<uint32_t> changed;
+            std::vector<int32_t> rows;
+            for (uint32_t id : dirty) { auto it = row_of.find(id); if (it != row_of.end()) { changed.push_back(id); rows.push_back(it->second); } }
+            if (!rows.empty()) {
+                Table t;
+                fill(map, changed, t);
+                const uh_map_points v = t.view();
+                check(uh_fuse_update_points(h_, (int32_t)rows.size(), rows.data(), &v));
+            }
+        }
+        dirty.clear();
+        auto it = cache_.find((uint32_t)KF.idx);
+        if (it == cache_.end()) {
+            uh_dev_frame* d = nullptr;
+            check(uh_dev_frame_create(ctx_->get(), &d));
+            it = cache_.emplace((uint32_t)KF.idx, d).first;
+            check(uh_dev_frame_upload(d, f.und_kpts, f.n_kpts, f.desc));
+        }
+        check(uh_fuse_search(h_, it->second, &f, pose, predict.data(), (int32_t)predict.size(), skip.data(), th, widen, maxDescDistance, bk_.data(), bd_.data(), st_.data()));
+    }
+    template <class Map, class Frame>
+    void apply(Map& map, Frame& KF, const std::vector<uint32_t>& ids, std::vector<uint32_t>& removed, std::vector<uint32_t>& dirty) {
+        for (size_t r = 0; r < ids.size(); r++) {
+            if (st_[r] != UH_FUSE_FOUND) continue;
+            const uint32_t kp = (uint32_t)bk_[r], held = KF.ids[kp];
+            if (held != 0xFFFFFFFFu) {
+                map.fuseMapPoints(held, ids[r], false);
+                removed.push_back(ids[r]);
+                map.map_points[ids[r]].setBad(true);
+                dirty.push_back(held);
+            } else {
+                map.addMapPointObservation(ids[r], KF.idx, kp);
+                dirty.push_back(ids[r]);
+            }
+        }
+    }
+    Context* ctx_ = nullptr;
+    uh_fuse* h_ = nullptr;
+    bool host_ = true;
+    std::map<uint32_t, uh_dev_frame*> cache_;
+    std::vector<uh_keypoint> kps_;
+    std::vector<int32_t> bk_;
+    std::vector<float> bd_;
+    std::vector<uint8_t> st_;
+};
 
 // ---- ucoslam::FrameExtractor::processStereo / process_rgbd (utils/frameextractor.cpp from :1419), kptImageScaleFactor == 1 --------------
 // Images are non-owning views (for cv::Mat: {m.data, m.cols, m.rows, m.step, m.channels()}).  The frame type is a template parameter shaped
