@@ -1227,6 +1227,83 @@ int uh_pnp_ransac_debug_roots(uh_pnp* pnp, int n, const double* A_nx5, double* r
 int uh_ba_debug_solve(uh_ba* ba, int form, int nfree, const double* S, const double* b, double* x, double* LD, int* failed);
 int uh_posegraph_debug_solve(uh_posegraph* pg, int n, const double* S, const double* b, double* x, double* LD, int* failed);
 
+/* ------------------------------------------------------------------------
+ * Map initialiser: MapInitializer's two-view "initialise" (src/utils/mapinitializer.cpp:152-201, ORB-SLAM's Initializer) — 200 homography
+ * and 200 fundamental hypotheses from 8-point samples, each scored over every match, the model choice RH = SH / (SH + SF) > 0.40, the
+ * decomposition of the chosen model into eight or four (R, t) candidates, and one triangulate-and-check pass (CheckRT) per candidate.
+ * The keypoint route only; what the caller _9813592252344743680 adds (pose = [R | t * min_distance]) is included.
+ *
+ * A match is (train, query): train indexes kp1 (the reference frame), query indexes kp2.  Per hypothesis the eight matches
+ * samples[8 it .. 8 it + 7] give the normalised 8-point system (both normalisations are sequential float sums over ALL keypoints of a frame,
+ * taken on the host), its null vector in double, the de-normalised float model, and the reference's sequential float score in match
+ * order with the inlier mask.  The FIRST hypothesis with the strictly largest score > 0 wins for each model.  States per match of the
+ * winning candidate: 0 not an inlier of the chosen model, 1 rejected by CheckRT, 2 counted with cosine >= 0.99998 (its point is stored,
+ * the keypoint is not marked triangulated), 3 counted and good, 4 non-finite triangulation (the keypoint's flag is CLEARED).  The
+ * per-keypoint scatter runs on the host in match order, so duplicate reference keypoints resolve as in the reference's loop.
+ * The arithmetic, its float conventions, the SIGN RULE for singular vectors and what is UNPINNED are in csrc/mapinit_math.hpp.
+ * One upload, two launches, one download, ONE wait.  n_matches < min_matches: ok = 0 without a launch.  A chosen model without a
+ * winning hypothesis (the reference would hand an empty matrix to OpenCV) gives ok = 0, winner = -1.
+ * Refused with UH_EINVAL before any launch: min_matches < 8, iterations outside [1, UH_MAPINIT_MAX_ITERS], more than
+ * UH_MAPINIT_MAX_MATCHES matches, a match index outside its keypoint array, a sample index outside [0, n_matches), NULL arrays,
+ * non-finite intrinsics or sigma <= 0, a result buffer below its stated size.
+ * uh_mapinit_run_host is the same function on the calling core (no GPU needed): equal bit for bit in everything but the parallaxes
+ * (acos of the host's libm against the device's).
+ * ------------------------------------------------------------------------ */
+#define UH_MAPINIT_MAX_ITERS    1024
+#define UH_MAPINIT_MAX_MATCHES  16384
+#define UH_MAPINIT_NONE         0
+#define UH_MAPINIT_HOMOGRAPHY   1
+#define UH_MAPINIT_FUNDAMENTAL  2
+typedef struct uh_mapinit uh_mapinit;
+typedef struct uh_mapinit_args {
+    const float* intr4;                    /* fx, fy, cx, cy of the undistorted camera */
+    const float* kp1; int32_t n_kp1;       /* n_kp1 x 2  und_kpts of the reference frame */
+    const float* kp2; int32_t n_kp2;       /* n_kp2 x 2  und_kpts of the second frame */
+    const int32_t* matches; int32_t n_matches;   /* n_matches x 2  (trainIdx -> kp1, queryIdx -> kp2) */
+    float sigma;                           /* 1.0 */
+    int32_t iterations;                    /* 200 */
+    int32_t min_matches;                   /* 50 (minNumMatches), at least 8 */
+    float min_parallax;                    /* 1.0 */
+    int32_t min_triangulated;              /* 50 */
+    float min_distance;                    /* Params::minDistance: the baseline the unit translation is scaled to */
+    const int32_t* samples;                /* iterations x 8 indices into the matches, or NULL: drawn as uh_mapinit_samples draws them */
+} uh_mapinit_args;
+typedef struct uh_mapinit_result {
+    int32_t ok, model, winner;             /* model: UH_MAPINIT_*; winner: index of the chosen (R, t) candidate or -1 */
+    int32_t best_h, best_f;                /* winning hypothesis of each model, -1: none scored above 0 */
+    float score_h, score_f, rh;
+    int32_t n_candidates, n_inliers;       /* 8 / 4 (0: ReconstructH's singular-value exit); inliers N of the chosen model */
+    int32_t n_good[8]; float parallax[8];  /* per candidate, in the written order */
+    float R[9], t[3], pose[16];            /* the winner's (unit t); pose = [R | t * min_distance], row-major 4x4; zeros unless ok */
+    int32_t n_out;                         /* surviving matches */
+    int32_t* matches_out;                  /* in: buffer of n_matches x 2 */
+    float* points_out;                     /* in: buffer of n_matches x 3, the survivors' points in match order */
+    uint8_t* triangulated;                 /* in: n_kp1 bytes or NULL (vbTriangulated) */
+    float* p3d;                            /* in: n_kp1 x 3 or NULL (vP3D) */
+    uint8_t* state;                        /* in: n_matches bytes or NULL, the per-match states above */
+    int32_t* index_out;                    /* in: n_matches entries or NULL: each survivor's index into the input matches */
+    int32_t cap_matches;                 /* in: entries of matches_out / points_out / state (>= n_matches) */
+} uh_mapinit_result;
+int  uh_mapinit_create(uh_ctx* ctx, uh_mapinit** out);
+void uh_mapinit_destroy(uh_mapinit* mi);
+int  uh_mapinit_run(uh_mapinit* mi, const uh_mapinit_args* args, uh_mapinit_result* result);
+int  uh_mapinit_run_host(const uh_mapinit_args* args, uh_mapinit_result* result);
+/* Host code: the reference's draw (:167-182).  Calls srand(0) — as the reference does inside this function — and then draws 8 * iterations
+ * numbers from libc rand(): per iteration the available list is reset to the identity and eight times j = rand() % size is taken and
+ * overwritten with the last entry.  SIDE EFFECT: rand()'s state is reseeded and ends where the reference leaves it.  n >= 8. */
+int  uh_mapinit_samples(int32_t n, int32_t iterations, int32_t* samples_out /* iterations x 8 */);
+/* test hook: ONE hypothesis from the device (model UH_MAPINIT_HOMOGRAPHY / _FUNDAMENTAL): the de-normalised matrix taken in double from the
+ * device's double null vector (H21 = T2^-1 Hn T1; F21 = T2^T rank2(Fn) T1), the float matrix the score used, the score and the mask
+ * (ceil(n_matches / 64) words, bit j % 64 of word j / 64 = match j) */
+int  uh_mapinit_debug_hypothesis(uh_mapinit* mi, const uh_mapinit_args* args, int32_t model, int32_t iter, double* M9_double, float* M9_float,
+                                 float* score, uint64_t* mask_words);
+/* test hook: the SECOND launch alone on a planted winner — the float model matrix M9 (H21 or F21) and its inlier mask (words as above) take
+ * the place of the hypotheses' winner (iterations is read as 1; the result's scores are 1 and 0, best_h / best_f are 0 and -1).  It reaches
+ * states no keypoint input can: a non-finite coordinate never is an inlier of a scored hypothesis (its chi-square is inf or NaN, and it
+ * spoils the frame's normalisation), and a finite one triangulates to a finite point.  mi = NULL runs the host form. */
+int  uh_mapinit_debug_reconstruct(uh_mapinit* mi, const uh_mapinit_args* args, int32_t model, const float* M9, const uint64_t* mask_words,
+                                  uh_mapinit_result* result);
+
 #ifdef __cplusplus
 }
 #endif

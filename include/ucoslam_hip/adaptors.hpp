@@ -935,4 +935,84 @@ class FrameExtractor {
     std::vector<float> und_, depth_;
 };
 
+// ------------------------------------------------------------------------------------------------ map initialiser
+// ucoslam::MapInitializer (src/utils/mapinitializer.h), the keypoint route: setParams / reset / setReferenceFrame as there, and
+// initialize(frame2, matches) for what initialize_ does between the matcher and the map — the two-view initialise on the device
+// (uh_mapinit_run).  The caller matches the two frames (FrameMatcher, MODE_ALL) and, on success, turns the result into two keyframes
+// and one map point per surviving match (initialize_ :64-99).  The marker route (ARUCO_initialize) and the one-frame marker route are
+// not built.  Frames are anything shaped like ucoslam::Frame: und_kpts (elements with pt.x, pt.y), imageParams with fx() fy() cx() cy().
+class MapInitializer {
+   public:
+    struct Params {   // the fields of MapInitializer::Params the keypoint route reads, with their defaults
+        float minDistance = 0.1f, minNumMatches = 50;
+        float sigma = 1.0f;
+        int iterations = 200;
+    };
+    struct Result {
+        bool ok = false;
+        std::array<float, 16> pose_f2g{};            // of frame2, row-major 4x4: [R | t * minDistance]; the reference frame's is the identity
+        std::vector<uh_dmatch> matches;              // the survivors, in the order they came
+        std::vector<std::array<float, 3>> points;    // their points, in the reference frame's camera system
+        int model = UH_MAPINIT_NONE;
+        uh_mapinit_result diagnostics{};             // scores, RH, every candidate's nGood and parallax (the buffers inside are not valid)
+    };
+    explicit MapInitializer(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) { check(uh_mapinit_create(ctx_->get(), &mi_)); }
+    ~MapInitializer() { uh_mapinit_destroy(mi_); }
+    MapInitializer(const MapInitializer&) = delete;
+    MapInitializer& operator=(const MapInitializer&) = delete;
+    void setParams(const Params& p) { params_ = p; }
+    void reset() { ref_kp_.clear(); has_ref_ = false; }
+    bool hasReferenceFrame() const { return has_ref_; }
+    template <class Frame> void setReferenceFrame(const Frame& f) {
+        flatten(f, ref_kp_);
+        intr_ = {f.imageParams.fx(), f.imageParams.fy(), f.imageParams.cx(), f.imageParams.cy()};
+        has_ref_ = true;
+    }
+    // matches: trainIdx -> keypoint of the reference frame, queryIdx -> keypoint of frame2
+    template <class Frame> Result initialize(const Frame& frame2, const std::vector<uh_dmatch>& matches) {
+        if (!has_ref_) throw std::runtime_error("MapInitializer::initialize invalid reference frame");
+        Result out;
+        std::vector<float> kp2;
+        flatten(frame2, kp2);
+        const int n = (int)matches.size();
+        std::vector<int32_t> m(2 * (size_t)n), mo(2 * (size_t)std::max(n, 1));
+        std::vector<int32_t> at((size_t)std::max(n, 1));
+        std::vector<float> po(3 * (size_t)std::max(n, 1));
+        for (int i = 0; i < n; i++) { m[2 * i] = matches[i].trainIdx; m[2 * i + 1] = matches[i].queryIdx; }
+        uh_mapinit_args a{};
+        a.intr4 = intr_.data();
+        a.kp1 = ref_kp_.data(); a.n_kp1 = (int32_t)(ref_kp_.size() / 2);
+        a.kp2 = kp2.data(); a.n_kp2 = (int32_t)(kp2.size() / 2);
+        a.matches = m.data(); a.n_matches = n;
+        a.sigma = params_.sigma; a.iterations = params_.iterations;
+        a.min_matches = (int32_t)std::ceil(params_.minNumMatches);   // `matches.size() < minNumMatches` with a float bound
+        a.min_parallax = 1.0f; a.min_triangulated = 50; a.min_distance = params_.minDistance;
+        a.samples = nullptr;
+        uh_mapinit_result r{};
+        r.matches_out = mo.data(); r.points_out = po.data(); r.index_out = at.data(); r.cap_matches = n;
+        check(uh_mapinit_run(mi_, &a, &r));
+        out.ok = r.ok != 0;
+        out.model = r.model;
+        std::memcpy(out.pose_f2g.data(), r.pose, sizeof(r.pose));
+        for (int j = 0; j < r.n_out; j++) {
+            out.matches.push_back(matches[(size_t)at[j]]);
+            out.points.push_back({po[3 * j], po[3 * j + 1], po[3 * j + 2]});
+        }
+        r.matches_out = nullptr; r.points_out = nullptr; r.index_out = nullptr;
+        out.diagnostics = r;
+        return out;
+    }
+   private:
+    template <class Frame> static void flatten(const Frame& f, std::vector<float>& xy) {
+        xy.resize(2 * f.und_kpts.size());
+        for (size_t i = 0; i < f.und_kpts.size(); i++) { xy[2 * i] = f.und_kpts[i].pt.x; xy[2 * i + 1] = f.und_kpts[i].pt.y; }
+    }
+    std::shared_ptr<Context> ctx_;
+    uh_mapinit* mi_ = nullptr;
+    Params params_;
+    std::vector<float> ref_kp_;
+    std::array<float, 4> intr_{};
+    bool has_ref_ = false;
+};
+
 }  // namespace ucoslam_hip
