@@ -1207,6 +1207,73 @@ int uh_pnp_ransac_debug_form(uh_pnp* pnp, int uniform_roots);
 int uh_pnp_ransac_debug_roots(uh_pnp* pnp, int n, const double* A_nx5, double* roots_nx4, int32_t* n_roots);
 
 /* ------------------------------------------------------------------------
+ * System::relocalize's pose search (src/utils/system.cpp ~4950-5500) for ALL candidate keyframes of one lost frame as ONE call
+ * (csrc/relocalize.hpp): what uh_pnp_ransac -> per survivor uh_projmatch_match -> id -> row look-ups -> uh_pnp_solve give one after the
+ * other, bit for bit, on the device between the launches with ONE wait on the context's stream at the end.  The number of launches does
+ * not depend on n_candidates.  Per candidate c, in the caller's order:
+ *   - fewer than min_matches_ransac matches: the candidate takes no part (no RANSAC problem, no samples drawn)      stage UH_RELOC_FEW_MATCHES
+ *   - solvePnPRansac over its matches; the count afterwards is n_inliers when ok, else ALL its matches (the reference ignores the return
+ *     value and a failed call leaves the list untouched); fewer than min_matches_after_ransac stops it              stage UH_RELOC_FEW_AFTER_RANSAC
+ *   - Map::matchFrameToMapPoints over `points` from the RANSAC result's pose (the winner's even when ok == 0; Se3Transform(rt6_in) when no
+ *     hypothesis had an inlier), radius map_radius, after filter_ambiguous_query; fewer than min_matches_map stops it   stage UH_RELOC_FEW_MAP
+ *   - PnPSolver::solvePnp (monocular) from that pose over those matches: p3d = the matched row of `points`, kp = the frame's undistorted
+ *     keypoint, inv_sigma = inv_sigma_levels[its octave], weight = weight[row]; n_good = matches with bad == 0; fewer than min_good stops
+ *     it                                                                                                            stage UH_RELOC_FEW_GOOD
+ *   - else                                                                                                           stage UH_RELOC_SOLVED
+ * best = the solved candidate with the strictly largest n_good (the first on ties), -1 without one; pose / n_matches are its pose_solve / n_good.
+ * Preconditions as uh_track_pose: a device-resident frame (uh_orb_extract_frame_dev or uh_dev_frame_upload, then
+ * uh_projmatch_set_frame_dev with either tree builder) of <= 4096 keypoints; pm and pnp on one context.
+ * samples == NULL: the call draws them itself with the routine behind uh_pnp_ransac_samples, in candidate order and only for candidates
+ * that pass the first gate, so libc rand() ends where the chain of single calls leaves it.
+ * Fields of a stage a candidate never reached keep NEUTRAL values: ok = n_inliers = n_map = solve_inliers = n_good = 0, best_iter = -1,
+ * iters = {0,0,0,0}, rt6 / pose_ransac / pose_solve all zero, nothing written to inliers / matches_map / bad.  (A candidate stopped at
+ * UH_RELOC_FEW_MAP has its matches_map; bad, pose_solve, iters, solve_inliers and n_good are neutral.)
+ * Refused with UH_EINVAL before anything is launched: NULL arrays with n > 0, a query_idx outside the frame's keypoints, cap_map below
+ * min(points->n, keypoints) or cap_inliers below n (with a non-NULL inliers), what uh_pnp_ransac refuses for samples, sizes and intrinsics
+ * (max_iters outside 1..UH_RANSAC_MAX_ITERS, n beyond UH_RANSAC_MAX_MATCHES, n_candidates outside 0..UH_RANSAC_MAX_PROBLEMS), n_levels
+ * outside 1..16, a map_radius <= 0, a frame that is not device-resident or has more than 4096 keypoints.  Non-finite coordinates are not
+ * refused (see uh_pnp_ransac).  n_candidates == 0 is valid: best = -1, nothing is launched.
+ * ------------------------------------------------------------------------ */
+enum { UH_RELOC_FEW_MATCHES = 0, UH_RELOC_FEW_AFTER_RANSAC = 1, UH_RELOC_FEW_MAP = 2, UH_RELOC_FEW_GOOD = 3, UH_RELOC_SOLVED = 4 };
+typedef struct uh_reloc_args {
+    const float* intr4;                 /* fx fy cx cy */
+    const float* inv_sigma_levels;      /* n_levels: 1 / scaleFactor per octave */
+    int32_t n_levels;
+    float map_min_desc_dist;            /* 2 x maxDescDistance */
+    float map_radius;                   /* 2.5 */
+    int32_t max_iters;                  /* 50: RANSAC iterations per candidate */
+    int32_t min_matches_ransac, min_matches_after_ransac, min_matches_map, min_good;   /* 25, 15, 30, 30: a count BELOW the gate stops the candidate */
+} uh_reloc_args;
+typedef struct uh_reloc_candidate {
+    int32_t n;                          /* matches of the lost frame against this keyframe */
+    const int32_t* query_idx;           /* n: DMatch::queryIdx, the frame's keypoint */
+    const float* p3d;                   /* n x 3: the matched map point's coordinates */
+    const float* normal;                /* n x 3: its normal */
+    const float* rt6_in;                /* the keyframe's pose_f2g as (rvec, tvec) */
+    const int32_t* samples;             /* max_iters x 4, or NULL: drawn by the call */
+    const uh_map_points* points;        /* the candidate's own point list (getNeighborsVLevel2(kf, true)); n == 0 is valid */
+    const float* weight;                /* points->n: the solver weight per point (0.5 for unstable ones); NULL = all 1 */
+} uh_reloc_candidate;
+typedef struct uh_reloc_step {          /* per candidate; in: the buffers and their capacities */
+    int32_t stage;                      /* UH_RELOC_* */
+    int32_t ok, n_inliers, best_iter;   /* solvePnPRansac's result */
+    float rt6[6], pose_ransac[16];
+    int32_t* inliers; int32_t cap_inliers;    /* NULL, or >= n entries: the winner's inliers, ascending */
+    int32_t n_map;                      /* matches of the projection search; trainIdx = the point's id */
+    uh_dmatch* matches_map; uint8_t* bad; int32_t cap_map;   /* >= min(points->n, the frame's keypoints) entries each (may be NULL when that is 0) */
+    float pose_solve[16];
+    int32_t iters[4], solve_inliers, n_good;
+} uh_reloc_step;
+typedef struct uh_reloc_result {
+    int32_t best;                       /* winning candidate or -1 */
+    float pose[16];                     /* its pose_solve (all zero when best == -1) */
+    int32_t n_matches;                  /* its n_good (0 when best == -1) */
+    uh_reloc_step* steps;               /* n_candidates entries */
+} uh_reloc_result;
+int uh_relocalize_pose(uh_projmatch* pm, uh_pnp* pnp, const uh_reloc_args* args, int n_candidates, const uh_reloc_candidate* cands,
+                       uh_reloc_result* result);
+
+/* ------------------------------------------------------------------------
  * Test hooks: ONE reduced-system solve S x = b (fp64 L D L^T without pivoting) in a chosen production form, on a system the caller gives.
  * The hooks load [S; b^T] into the layout the form expects and call the device functions (form 7: the launches) the optimisers call;
  * no problem has to be set.  S is n x n row-major and only its lower triangle is read; n = 6 nfree for the bundle adjustment.

@@ -484,6 +484,91 @@ class ProjectionMatcher {
     uh_projmatch* h_ = nullptr;
 };
 
+// ---- System::relocalize's pose search (utils/system.cpp ~4950-5500) for all candidate keyframes of a lost frame in ONE call -------------
+// (uh_relocalize_pose): solvePnPRansac per candidate, matchFrameToMapPoints from its pose over the candidate's points, solvePnp, the
+// candidate with the most good matches.  The object owns its matcher, solver and the device-resident copy of the lost frame.
+class Relocalizer {
+   public:
+    struct Candidate {
+        std::vector<uh_dmatch> matches;      // queryIdx = the frame's keypoint (trainIdx is not read: the projection search replaces the list)
+        std::vector<float> p3d, normal;      // matches.size() x 3 each: the matched map points' coordinates and normals
+        float rt6[6];                        // the keyframe's pose_f2g as (rvec, tvec)
+        uh_map_points points;                // getNeighborsVLevel2(kf, true), flattened
+        const float* weight = nullptr;       // points.n: 1 / 0.5 (MapPoint::isStable), NULL = all 1
+        const int32_t* samples = nullptr;    // maxIters x 4, or NULL: drawn from libc rand() as the reference draws them
+    };
+    struct Step {
+        int stage = 0, ok = 0, n_inliers = 0, best_iter = -1, solve_inliers = 0, n_good = 0;   // stage: UH_RELOC_*
+        float rt6[6] = {0}, pose_ransac[16] = {0}, pose_solve[16] = {0};
+        int32_t iters[4] = {0, 0, 0, 0};
+        std::vector<int32_t> inliers;        // RANSAC's inliers (indices into matches)
+        std::vector<uh_dmatch> matches_map;  // the projection search's list
+        std::vector<uint8_t> bad;            // the solve's outlier flags over matches_map (empty when the solve did not run)
+    };
+    struct Result { int best = -1; float pose[16] = {0}; int n_matches = 0; std::vector<Step> steps; };
+
+    explicit Relocalizer(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {
+        check(uh_projmatch_create(ctx_->get(), &pm_));
+        check(uh_pnp_create(ctx_->get(), &pnp_));
+        check(uh_dev_frame_create(ctx_->get(), &fr_));
+    }
+    ~Relocalizer() { uh_projmatch_destroy(pm_); uh_pnp_destroy(pnp_); uh_dev_frame_destroy(fr_); }
+    Relocalizer(const Relocalizer&) = delete;
+    Relocalizer& operator=(const Relocalizer&) = delete;
+    // the lost frame: f.und_kpts / f.desc / f.n_kpts (at most 4096) go to the device once, f's camera, scale and bounds fields to the matcher
+    void setFrame(const uh_proj_frame& f) {
+        check(uh_dev_frame_upload(fr_, f.und_kpts, f.n_kpts, f.desc));
+        check(uh_projmatch_set_frame_dev(pm_, fr_, &f));
+        n_kpts_ = f.n_kpts;
+    }
+    // gates: System::relocalize's 25 / 15 / 30 / 30
+    Result relocalize(const float intr4[4], const std::vector<float>& inv_sigma_levels, const std::vector<Candidate>& cands, float maxDescDistance, int maxIters = 50,
+                      int minMatchesRansac = 25, int minMatchesAfterRansac = 15, int minMatchesMap = 30, int minGood = 30) {
+        const uh_reloc_args args{intr4, inv_sigma_levels.data(), (int32_t)inv_sigma_levels.size(), 2 * maxDescDistance, 2.5f, maxIters,
+                                 minMatchesRansac, minMatchesAfterRansac, minMatchesMap, minGood};
+        const size_t C = cands.size();
+        std::vector<std::vector<int32_t>> q(C);
+        std::vector<uh_reloc_candidate> cs(C);
+        std::vector<uh_reloc_step> ss(C);
+        Result out;
+        out.steps.resize(C);
+        for (size_t c = 0; c < C; c++) {
+            const Candidate& k = cands[c];
+            const size_t n = k.matches.size();
+            if (k.p3d.size() != 3 * n || k.normal.size() != 3 * n) throw std::runtime_error("Relocalizer::relocalize: p3d / normal need three floats per match");
+            q[c].resize(n ? n : 1);
+            for (size_t i = 0; i < n; i++) q[c][i] = k.matches[i].queryIdx;
+            cs[c] = uh_reloc_candidate{(int32_t)n, q[c].data(), k.p3d.data(), k.normal.data(), k.rt6, k.samples, &k.points, k.weight};
+            Step& s = out.steps[c];
+            const size_t cap = (size_t)std::max(1, std::min(k.points.n, n_kpts_));
+            s.inliers.assign(n ? n : 1, 0); s.matches_map.assign(cap, uh_dmatch{}); s.bad.assign(cap, 0);
+            ss[c] = uh_reloc_step{};
+            ss[c].inliers = s.inliers.data(); ss[c].cap_inliers = (int32_t)s.inliers.size();
+            ss[c].matches_map = s.matches_map.data(); ss[c].bad = s.bad.data(); ss[c].cap_map = (int32_t)cap;
+        }
+        uh_reloc_result res{};
+        res.steps = ss.data();
+        check(uh_relocalize_pose(pm_, pnp_, &args, (int)C, cs.data(), &res));
+        for (size_t c = 0; c < C; c++) {
+            Step& s = out.steps[c];
+            const uh_reloc_step& r = ss[c];
+            s.stage = r.stage; s.ok = r.ok; s.n_inliers = r.n_inliers; s.best_iter = r.best_iter; s.solve_inliers = r.solve_inliers; s.n_good = r.n_good;
+            std::copy(r.rt6, r.rt6 + 6, s.rt6); std::copy(r.pose_ransac, r.pose_ransac + 16, s.pose_ransac); std::copy(r.pose_solve, r.pose_solve + 16, s.pose_solve);
+            std::copy(r.iters, r.iters + 4, s.iters);
+            s.inliers.resize((size_t)r.n_inliers); s.matches_map.resize((size_t)r.n_map); s.bad.resize(r.stage >= UH_RELOC_FEW_GOOD ? (size_t)r.n_map : 0);
+        }
+        out.best = res.best; out.n_matches = res.n_matches;
+        std::copy(res.pose, res.pose + 16, out.pose);
+        return out;
+    }
+   private:
+    std::shared_ptr<Context> ctx_;
+    uh_projmatch* pm_ = nullptr;
+    uh_pnp* pnp_ = nullptr;
+    uh_dev_frame* fr_ = nullptr;
+    int n_kpts_ = 0;
+};
+
 // ---- ucoslam::loopClosurePathOptimizationg2o (optimization/graphoptsim3.cpp:74-168) ---------------------------------------
 // The pose type is a template parameter (the reference's is cv::Mat, CV_32F 4x4): posegraph_pose_ptr(pose) must give its 16
 // row-major floats; the overloads below cover anything with data() — for cv::Mat add one that returns m.ptr<float>().

@@ -210,6 +210,14 @@ namespace uh {
 struct PnpDecide { int min_inliers; float r_tracked, r_lost; float* dyn17; float* pose_map; int* tracked; };
 // the match arrays of a pose-only solve (device-visible, one entry per match); depth: NULL, or Frame::getDepth per match with the baseline bl
 struct PnpMatches { const float* p3d; const float* kp; const float* inv_sigma; const float* weight; const float* depth; float bl; };
+// one solve of a batch (uh_relocalize_pose, relocalize.hpp): everything device-visible, the match count (at most n_cap) in device memory
+struct PnpBatchItem { const float* d_pose; int n_cap; const int* d_n; PnpMatches m; float* d_pose_out; unsigned char* d_bad_out; int* d_result5; };
+// the relocalisation RANSAC's result record per problem (pnp_ransac.hip), as uh_relocalize_pose's launches read it from device memory
+struct RansacOut { int ok, n_inliers, best_iter, pad; float rt6[6]; float pose[16]; };
+// what a staged RANSAC batch (pnp_ransac_stage) leaves for the launches that follow it on the stream: per live problem (n >= 4, caller
+// order) its record, and its inlier indices in d_inliers behind those of the live problems before it (n entries each); d_kp: the matches'
+// keypoints, concatenated likewise (kp_on_device: filled by a launch of the caller between the upload and pnp_ransac_launch)
+struct RansacStaged { int live; const RansacOut* d_out; const int* d_inliers; float* d_kp; };
 }  // namespace uh
 
 #define UH_LAUNCH(ctx, kernel, grid, block, shmem, ...)                                        \

@@ -24,6 +24,8 @@
 namespace uh {
 uh_ctx* pnp_ctx(uh_pnp* p);
 void** pnp_ransac_slot(uh_pnp* p, void (*free_fn)(void*));
+int pnp_ransac_stage(const char* fn, uh_pnp* p, const float* intr4, int n_problems, const uh_ransac_problem* problems, uh_ransac_result* results, bool kp_on_device,
+                     RansacStaged* sg);
 }
 
 namespace {
@@ -269,6 +271,11 @@ struct PrState {
     uh::DevBuf d_in, d_work, d_out;
     uh::PinBuf h_in, h_out;
     bool uniform_roots = false;   // measurement hook (uh_pnp_ransac_debug_form)
+    // the staged batch (pnp_ransac_stage): the launches' arguments, where the blocks' parts lie, the upload's status
+    PrArgs a{};
+    int live = 0, max_iters = 0;
+    size_t i_prob = 0, r_bytes = 0, r_out = 0, r_cnt = 0, r_inl = 0;
+    hipError_t e = hipSuccess;
 };
 void pr_free(void* s) { delete static_cast<PrState*>(s); }
 PrState* pr_state(uh_pnp* p) {
@@ -287,11 +294,11 @@ int check_intr(const char* fn, const float* intr4) {
 }
 
 // what uh_pnp_ransac and the debug hook check of one problem before anything is launched
-int check_problem(const char* fn, int j, const uh_ransac_problem& q) {
+int check_problem(const char* fn, int j, const uh_ransac_problem& q, bool kp_on_device = false) {
     UH_REQUIRE(q.n >= 0 && q.n <= UH_RANSAC_MAX_MATCHES, "%s: problem %d: %d matches outside [0, %d]", fn, j, q.n, UH_RANSAC_MAX_MATCHES);
     UH_REQUIRE(q.iters >= 1 && q.iters <= UH_RANSAC_MAX_ITERS, "%s: problem %d: %d iterations outside [1, %d]", fn, j, q.iters, UH_RANSAC_MAX_ITERS);
     UH_REQUIRE(q.rt6_in, "%s: problem %d: NULL rt6_in", fn, j);
-    if (q.n > 0) UH_REQUIRE(q.p3d && q.normal && q.kp, "%s: problem %d: NULL match arrays with n = %d", fn, j, q.n);
+    if (q.n > 0) UH_REQUIRE(q.p3d && q.normal && (q.kp || kp_on_device), "%s: problem %d: NULL match arrays with n = %d", fn, j, q.n);
     if (q.n < 4) return UH_OK;
     UH_REQUIRE(q.samples, "%s: problem %d: NULL samples", fn, j);
     for (int it = 0; it < q.iters; it++) {
@@ -311,43 +318,66 @@ void host_pose(const float* rt6, float* pose16) {
     std::memcpy(pose16, v, sizeof(v));
 }
 
-}  // namespace
 
-extern "C" {
-
-int uh_pnp_ransac_samples(int n, int iters, int32_t* samples_out) {
-    UH_REQUIRE(n >= 4 && iters >= 0 && samples_out, "uh_pnp_ransac_samples: n = %d (at least 4), iters = %d, or a NULL output", n, iters);
-    std::vector<int32_t> idx((size_t)n);
-    for (int i = 0; i < n; i++) idx[i] = i;
-    for (int it = 0; it < iters; it++) {
-        // std::random_shuffle of libstdc++ (stl_algo.h): for i = first + 1 .. last - 1: j = first + rand() % (i - first + 1); if (i != j) iter_swap(i, j)
-        for (int i = 1; i < n; i++) {
-            const int j = std::rand() % (i + 1);
-            if (i != j) std::swap(idx[i], idx[j]);
-        }
-        for (int k = 0; k < 4; k++) samples_out[4 * (size_t)it + k] = idx[k];
-    }
-    return UH_OK;
+// the two launches of a staged batch
+hipError_t pr_launch(uh_pnp* p, PrState* st) {
+    uh_ctx* ctx = uh::pnp_ctx(p);
+    const PrArgs& a = st->a;
+    const dim3 grid(uh_div_up(st->max_iters, kHypWaves), st->live);
+    if (st->uniform_roots) UH_LAUNCH(ctx, pr_hypothesis_kernel<true>, grid, dim3(kHypThreads), 0, a);
+    else UH_LAUNCH(ctx, pr_hypothesis_kernel<false>, grid, dim3(kHypThreads), 0, a);
+    UH_LAUNCH(ctx, pr_select_kernel, dim3(st->live), dim3(kSelThreads), 0, a);
+    return hipGetLastError();
 }
 
-int uh_pnp_ransac(uh_pnp* p, const float* intr4, int n_problems, const uh_ransac_problem* problems, uh_ransac_result* results) {
+// the results of the live problems (n >= 4) from the pinned result block
+void pr_unpack(PrState* st, int n_problems, const uh_ransac_problem* problems, uh_ransac_result* results) {
+    const char* ho = st->h_out.as<char>();
+    const PrProblemDev* hp = (const PrProblemDev*)(st->h_in.as<char>() + st->i_prob);
+    const PrOut* out = (const PrOut*)(ho + st->r_out);
+    const int* cnt = (const int*)(ho + st->r_cnt);
+    const int* inl = (const int*)(ho + st->r_inl);
+    for (int j = 0, l = 0; j < n_problems; j++) {
+        const uh_ransac_problem& q = problems[j];
+        if (q.n < 4) continue;
+        const PrProblemDev& d = hp[l];
+        const PrOut& o = out[l++];
+        uh_ransac_result& r = results[j];
+        r.ok = o.ok; r.n_inliers = o.n_inliers; r.best_iter = o.best_iter;
+        std::memcpy(r.rt6, o.rt6, sizeof(r.rt6));
+        std::memcpy(r.pose, o.pose, sizeof(r.pose));
+        if (o.n_inliers > 0 && r.inliers) std::memcpy(r.inliers, inl + d.m_off, sizeof(int) * (size_t)o.n_inliers);
+        if (r.counts) std::memcpy(r.counts, cnt + d.h_off, sizeof(int) * (size_t)q.iters);
+    }
+}
+
+}  // namespace
+
+namespace uh {
+
+// uh_pnp_ransac up to its upload, for `fn`: every check, the results of the problems below four matches, the packed block and its copy to
+// the device enqueued (the copy's status stays in the state: the caller drains the stream on a failure, as it does for its launches).
+// kp_on_device: the problems carry no keypoints; the caller fills d_kp on the stream before pnp_ransac_launch.  results may then be NULL.
+int pnp_ransac_stage(const char* fn, uh_pnp* p, const float* intr4, int n_problems, const uh_ransac_problem* problems, uh_ransac_result* results, bool kp_on_device,
+                     RansacStaged* sg) {
+    *sg = RansacStaged{};
     // ---- everything the kernels will trust is checked here, before anything is launched (and before the solver object is touched)
     int rc;
-    if ((rc = check_intr("uh_pnp_ransac", intr4))) return rc;
-    UH_REQUIRE(n_problems >= 0 && n_problems <= UH_RANSAC_MAX_PROBLEMS, "uh_pnp_ransac: %d problems outside [0, %d]", n_problems, UH_RANSAC_MAX_PROBLEMS);
+    if ((rc = check_intr(fn, intr4))) return rc;
+    UH_REQUIRE(n_problems >= 0 && n_problems <= UH_RANSAC_MAX_PROBLEMS, "%s: %d problems outside [0, %d]", fn, n_problems, UH_RANSAC_MAX_PROBLEMS);
     if (n_problems == 0) return UH_OK;
-    UH_REQUIRE(problems && results, "uh_pnp_ransac: NULL problem or result array");
+    UH_REQUIRE(problems && (results || kp_on_device), "%s: NULL problem or result array", fn);
     size_t N = 0, H = 0, Wd = 0;
     int live = 0, max_iters = 0;
     for (int j = 0; j < n_problems; j++) {
         const uh_ransac_problem& q = problems[j];
-        if ((rc = check_problem("uh_pnp_ransac", j, q))) return rc;
-        UH_REQUIRE(results[j].cap >= q.n && (q.n == 0 || results[j].inliers), "uh_pnp_ransac: problem %d: inlier buffer of %d entries for %d matches", j, results[j].cap, q.n);
+        if ((rc = check_problem(fn, j, q, kp_on_device))) return rc;
+        if (results) UH_REQUIRE(results[j].cap >= q.n && (q.n == 0 || results[j].inliers), "%s: problem %d: inlier buffer of %d entries for %d matches", fn, j, results[j].cap, q.n);
         if (q.n < 4) continue;
         live++; N += (size_t)q.n; H += (size_t)q.iters; Wd += (size_t)q.iters * (size_t)uh_div_up(q.n, 64);
         max_iters = std::max(max_iters, q.iters);
     }
-    for (int j = 0; j < n_problems; j++) {   // a problem below four matches: `matches_io.size() < 4 -> return false`, nothing is touched
+    for (int j = 0; results && j < n_problems; j++) {   // a problem below four matches: `matches_io.size() < 4 -> return false`, nothing is touched
         const uh_ransac_problem& q = problems[j];
         if (q.n >= 4) continue;
         uh_ransac_result& r = results[j];
@@ -357,7 +387,7 @@ int uh_pnp_ransac(uh_pnp* p, const float* intr4, int n_problems, const uh_ransac
         if (r.counts) for (int it = 0; it < q.iters; it++) r.counts[it] = -1;
     }
     if (live == 0) return UH_OK;
-    UH_REQUIRE(p, "uh_pnp_ransac: NULL solver");
+    UH_REQUIRE(p, "%s: NULL solver", fn);
     PrState* st = pr_state(p);
     uh_ctx* ctx = uh::pnp_ctx(p);
 
@@ -389,7 +419,7 @@ int uh_pnp_ransac(uh_pnp* p, const float* intr4, int n_problems, const uh_ransac
         std::memcpy(d.rt6_in, q.rt6_in, sizeof(d.rt6_in));
         std::memcpy(hi + i_p3d + 12 * m_off, q.p3d, 12 * (size_t)q.n);
         std::memcpy(hi + i_nrm + 12 * m_off, q.normal, 12 * (size_t)q.n);
-        std::memcpy(hi + i_kp + 8 * m_off, q.kp, 8 * (size_t)q.n);
+        if (!kp_on_device) std::memcpy(hi + i_kp + 8 * m_off, q.kp, 8 * (size_t)q.n);
         std::memcpy(hi + i_smp + 16 * h_off, q.samples, 16 * (size_t)q.iters);
         m_off += (size_t)q.n; h_off += (size_t)q.iters; w_off += (size_t)q.iters * (size_t)d.words;
     }
@@ -402,41 +432,63 @@ int uh_pnp_ransac(uh_pnp* p, const float* intr4, int n_problems, const uh_ransac
     a.p3d = (const float*)(di + i_p3d); a.normal = (const float*)(di + i_nrm); a.kp = (const float*)(di + i_kp); a.samples = (const int*)(di + i_smp);
     a.mask = (unsigned long long*)(dw + w_mask); a.hyp_rt6 = (float*)(dw + w_rt);
     a.out = (PrOut*)(dout + r_out); a.counts = (int*)(dout + r_cnt); a.inliers = (int*)(dout + r_inl);
+    st->a = a; st->live = live; st->max_iters = max_iters;
+    st->i_prob = i_prob; st->r_bytes = r_bytes; st->r_out = r_out; st->r_cnt = r_cnt; st->r_inl = r_inl;
+    st->e = hipMemcpyAsync(di, hi, i_bytes, hipMemcpyHostToDevice, ctx->stream);
+    static_assert(sizeof(RansacOut) == sizeof(PrOut), "RansacOut is PrOut as other units read it");
+    sg->live = live; sg->d_out = reinterpret_cast<const RansacOut*>(a.out); sg->d_inliers = a.inliers; sg->d_kp = (float*)(di + i_kp);
+    return UH_OK;
+}
 
+// the staged batch's two launches (its upload's status first); on a failure the caller drains the stream
+int pnp_ransac_launch(uh_pnp* p) {
+    PrState* st = pr_state(p);
+    hipError_t e = st->e;
+    if (e == hipSuccess) e = pr_launch(p, st);
+    if (e != hipSuccess) { uh::set_error("uh_pnp_ransac: %s", hipGetErrorString(e)); return UH_ENODEVICE; }
+    return UH_OK;
+}
+
+void pnp_ransac_host_pose(const float* rt6, float* pose16) { host_pose(rt6, pose16); }
+
+}  // namespace uh
+
+extern "C" {
+
+int uh_pnp_ransac_samples(int n, int iters, int32_t* samples_out) {
+    UH_REQUIRE(n >= 4 && iters >= 0 && samples_out, "uh_pnp_ransac_samples: n = %d (at least 4), iters = %d, or a NULL output", n, iters);
+    std::vector<int32_t> idx((size_t)n);
+    for (int i = 0; i < n; i++) idx[i] = i;
+    for (int it = 0; it < iters; it++) {
+        // std::random_shuffle of libstdc++ (stl_algo.h): for i = first + 1 .. last - 1: j = first + rand() % (i - first + 1); if (i != j) iter_swap(i, j)
+        for (int i = 1; i < n; i++) {
+            const int j = std::rand() % (i + 1);
+            if (i != j) std::swap(idx[i], idx[j]);
+        }
+        for (int k = 0; k < 4; k++) samples_out[4 * (size_t)it + k] = idx[k];
+    }
+    return UH_OK;
+}
+
+int uh_pnp_ransac(uh_pnp* p, const float* intr4, int n_problems, const uh_ransac_problem* problems, uh_ransac_result* results) {
+    uh::RansacStaged sg;
+    int rc;
+    if ((rc = uh::pnp_ransac_stage("uh_pnp_ransac", p, intr4, n_problems, problems, results, false, &sg))) return rc;
+    if (sg.live == 0) return UH_OK;
+    PrState* st = pr_state(p);
     // ---- one chain on the context's stream, one wait.  After the first enqueue every failure drains the stream before it returns:
     // the pinned blocks are rewritten by the next call.
-    char* ho = st->h_out.as<char>();
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(di, hi, i_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        const dim3 grid(uh_div_up(max_iters, kHypWaves), live);
-        if (st->uniform_roots) UH_LAUNCH(ctx, pr_hypothesis_kernel<true>, grid, dim3(kHypThreads), 0, a);
-        else UH_LAUNCH(ctx, pr_hypothesis_kernel<false>, grid, dim3(kHypThreads), 0, a);
-        UH_LAUNCH(ctx, pr_select_kernel, dim3(live), dim3(kSelThreads), 0, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(ho, dout, r_bytes, hipMemcpyDeviceToHost, s);
+    hipStream_t s = uh::pnp_ctx(p)->stream;
+    hipError_t e = st->e;
+    if (e == hipSuccess) e = pr_launch(p, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->h_out.p, st->d_out.p, st->r_bytes, hipMemcpyDeviceToHost, s);
     const hipError_t es = hipStreamSynchronize(s);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) {
         uh::set_error("uh_pnp_ransac: %s", hipGetErrorString(e));
         return UH_ENODEVICE;
     }
-    const PrOut* out = (const PrOut*)(ho + r_out);
-    const int* cnt = (const int*)(ho + r_cnt);
-    const int* inl = (const int*)(ho + r_inl);
-    for (int j = 0, l = 0; j < n_problems; j++) {
-        const uh_ransac_problem& q = problems[j];
-        if (q.n < 4) continue;
-        const PrProblemDev& d = hp[l];
-        const PrOut& o = out[l++];
-        uh_ransac_result& r = results[j];
-        r.ok = o.ok; r.n_inliers = o.n_inliers; r.best_iter = o.best_iter;
-        std::memcpy(r.rt6, o.rt6, sizeof(r.rt6));
-        std::memcpy(r.pose, o.pose, sizeof(r.pose));
-        if (o.n_inliers > 0) std::memcpy(r.inliers, inl + d.m_off, sizeof(int) * (size_t)o.n_inliers);
-        if (r.counts) std::memcpy(r.counts, cnt + d.h_off, sizeof(int) * (size_t)q.iters);
-    }
+    pr_unpack(st, n_problems, problems, results);
     return UH_OK;
 }
 

@@ -243,7 +243,7 @@ struct uh_track_state {
     uh::DevBuf d_clk;      // UH_TRK_CLK (measurement)
 };
 
-uh_projmatch::~uh_projmatch() { delete track; }
+uh_projmatch::~uh_projmatch() { delete track; if (reloc && reloc_free) reloc_free(reloc); }
 
 namespace {
 
